@@ -6,7 +6,7 @@ resident in HBM: the backward and the forward pass for all N targets, one
 launch of 2N workgroups (replacing the loop of pipeline/Paint.cpp:81-87 in the
 reference).
 
-    python bench.py [--gpus N --steps K --warmup W] [--haplotypes 5000 --snps 500000]
+    python bench.py [--gpus N --steps K --warmup W] [--haplotypes 5000 --snps 500000] [--dump-outputs DIR]
 
 With --gpus N > 1 there is one rank per GPU: launched by torch.distributed.run (the
 driver's way), or -- when no launcher set RANK -- by bench.py itself as a child
@@ -30,8 +30,31 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
-HBM_PEAK_GBS = 8000.0  # /opt/skills/guides/MI355X_MICROARCH.md: HBM3E 8 TB/s
+HBM_PEAK_GBS = 8000.0  # MI355X HBM3E 8 TB/s
 FP64_PEAK_TINSTR = 39.3  # FP64 vector peak 78.6 TFLOP/s (256 CUs x 4 SIMDs x 16 lanes x 2.4 GHz x 2 for an FMA): 39.3e12 lane-instructions/s
+DUMP_BYTES = 60 * 2 ** 20  # --dump-outputs: what all ranks write together (.npy headers included) stays under 64 MB
+DUMP_WINDOWS = 4  # windows whose alpha / beta rows --dump-outputs samples
+
+
+_phase = ["start", time.time()]
+
+
+def phase(name):
+    """progress on stderr (stdout carries the one result line only): the phase now starting"""
+    _phase[:] = [name, time.time()]
+    print("bench: %s" % name, file=sys.stderr, flush=True)
+
+
+def heartbeat(every_s=60.0):
+    """a line a minute on stderr while a phase lasts: the chunk wall-clock children alone run for minutes without
+    output, and a run that stays silent that long cannot be told from a hung one"""
+    import threading
+
+    def beat():
+        while True:
+            time.sleep(every_s)
+            print("bench: %s, %.0f s" % (_phase[0], time.time() - _phase[1]), file=sys.stderr, flush=True)
+    threading.Thread(target=beat, daemon=True).start()
 
 
 def make_chunk(N, L, seed, memory_gb):
@@ -144,6 +167,45 @@ def reference_baseline(N, L, seq, r, rpos, wb, o, d, per_target, seconds_target)
                        "of which %.1f s start-up (chunk files read) taken off" % (len(targets), N, targets, t_all, t_load))
 
 
+def dump_outputs(out_dir, ctxs, chunk_ids, world):
+    """--dump-outputs: the stepping stones the last timed Paint left for its caller (Context.stones), float32 .npy
+    files under out_dir, prefixed chunk<c>_ by chunk id (unique over ranks): ls_alpha / ls_beta [windows, targets], the
+    log scales of every window, and alpha / beta [DUMP_WINDOWS, rows, N], the full rows of a fixed seeded sample of
+    windows and targets.  The sample depends on the chunk's shape only, so runs with the same arguments write the same
+    entries; its indices go into the result line."""
+    from relate_amd import api
+    lib = api.lib()
+    os.makedirs(out_dir, exist_ok=True)
+    budget = DUMP_BYTES // (world * len(ctxs)) - 4 * 128  # (four .npy headers of at most 128 bytes)
+    sample = {}
+    for c, cx in zip(chunk_ids, ctxs):
+        N, W = cx.N, cx.W
+        k0, k1 = cx.target_range()
+        n = k1 - k0
+        rng = np.random.default_rng(1000 + c)
+        # log scales of all targets when they take at most half the budget, else of a seeded sample of targets
+        ls_rows = np.arange(n) if 8 * W * n <= budget // 2 else np.sort(rng.choice(n, budget // 2 // (8 * W), replace=False))
+        wins = np.sort(rng.choice(W, min(W, DUMP_WINDOWS), replace=False))
+        rows = min(n, (budget - 8 * W * len(ls_rows)) // (8 * N * len(wins)))
+        assert len(ls_rows) > 0 and rows > 0, "--dump-outputs: no room for a sample within %d bytes" % DUMP_BYTES
+        tgts = np.sort(rng.choice(n, rows, replace=False))
+        la, lb = np.empty(n, np.float32), np.empty(n, np.float32)
+        ls_a, ls_b = np.empty((W, len(ls_rows)), np.float32), np.empty((W, len(ls_rows)), np.float32)
+        for w in range(W):  # (NULL alpha / beta: the log scales alone come back)
+            api._check(lib.rl_get_stones(C.c_void_p(cx._h), w, None, None, api._p(la), api._p(lb), None, None))
+            ls_a[w], ls_b[w] = la[ls_rows], lb[ls_rows]
+        alpha = np.empty((len(wins), rows, N), np.float32)
+        beta = np.empty((len(wins), rows, N), np.float32)
+        for i, w in enumerate(wins):
+            st = cx.stones(int(w))
+            alpha[i], beta[i] = st["alpha"][tgts], st["beta"][tgts]
+        for name, a in (("ls_alpha", ls_a), ("ls_beta", ls_b), ("alpha", alpha), ("beta", beta)):
+            np.save(os.path.join(out_dir, "chunk%d_%s.npy" % (c, name)), a)
+        sample["chunk%d" % c] = {"ls_targets": "all" if len(ls_rows) == n else (k0 + ls_rows).tolist(),
+                                 "windows": wins.tolist(), "targets": (k0 + tgts).tolist()}
+    return sample
+
+
 def chunk_wallclock_full():
     """The metric's other half MEASURED: the whole C3 chunk -- Paint + BuildTopology of all 267 sections, files in ->
     .anc / .mut files out -- through `Relate --mode PaintBuildTopology` in a child process (tools/chunk_c3_fused.py).
@@ -158,6 +220,7 @@ def chunk_wallclock_full():
     results = []
     try:
         for i in range(runs):
+            phase("whole C3 chunk, run %d of %d (child process)" % (i + 1, runs))
             env = dict(os.environ)
             if i > 0:
                 env["C3_NO_TIMING"] = "1"
@@ -289,7 +352,12 @@ def main():
                     help="chunks (default, the contract's weak scaling): one chunk per GPU, no collective. "
                          "targets: ONE chunk for all ranks, each paints a range of target haplotypes (strong "
                          "scaling; BASELINE.json config #5) and the ranks all-gather one distance matrix's rows")
+    ap.add_argument("--dump-outputs", dest="dump_dir", metavar="DIR",
+                    help="after the timed steps, write a seeded sample of the stepping stones the last one computed "
+                         "as DIR/<name>.npy (float32, at most 64 MB in all)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     if args.gpus > 1 and "RANK" not in os.environ:
         # `python bench.py --gpus N` without a launcher: start the N ranks here (one process per GPU) as a CHILD --
@@ -317,10 +385,14 @@ def main():
     world = int(os.environ.get("WORLD_SIZE", "1"))
     # the chunk wall-clock sample runs in child processes BEFORE this process touches the GPU: the tree builder's
     # long-running workgroups are time-sliced against every other process that holds hardware queues on the device
+    if rank == 0:
+        heartbeat()
     chunk_sample = chunk_full = chunk_host = None
     if world == 1 and args.n == 5000 and args.workload == "c3" and not args.skip_chunk:
+        phase("chunk wall-clock sample (child process)")
         chunk_sample = chunk_wallclock_sample()
         if args.with_host and not args.skip_host:
+            phase("chunk wall-clock sample, host builder (child process)")
             chunk_host = chunk_wallclock_sample(host_builder=True)
         if not args.skip_full:
             chunk_full = chunk_wallclock_full()
@@ -344,6 +416,7 @@ def main():
     # the chunks of this rank: its own chunk (c3), or its deal of the job's chunk list (c4: chunk ids
     # 0 .. world * chunks_per_gpu - 1 dealt round-robin, relate_amd.dist.shard -- no data-path collective)
     my_chunks = [rank] if args.workload == "c3" else rdist.shard(list(range(world * args.cpg)), rank, world)
+    phase("generating and uploading the synthetic chunk%s" % ("s" if len(my_chunks) > 1 else ""))
     ctxs = []
     for c in my_chunks:
         bits, r, rpos, wb = make_chunk(N, L, seed=1 if by_target else 1 + c, memory_gb=args.memory)
@@ -392,8 +465,14 @@ def main():
             b += bb
         return f, b
 
+    phase("%d warm-up and %d timed steps" % (args.warmup, args.steps))
     dt, kernel_ms = timed(mode, args.steps, args.warmup)
     total_updates, dt = rdist.job_stats(updates, dt)  # sum of units, max of seconds over ranks
+    # (before anything below paints again: split_times and the other summation modes overwrite the stones)
+    if args.dump_dir:
+        phase("writing the outputs of the last timed step to %s" % args.dump_dir)
+    dumped = dump_outputs(args.dump_dir, ctxs, my_chunks, world) if args.dump_dir else None
+    phase("secondary measurements")
     fwd_ms, bwd_ms = split_times(mode) if rank == 0 else (0.0, 0.0)
 
     # the other summation modes on the same chunk (config.other_modes): `lanes` (re-associated sums, FP64 state) and
@@ -561,7 +640,10 @@ def main():
         }
         if roofline_k2 is not None:
             out["roofline_k2"] = roofline_k2
+        if dumped is not None:
+            out["dump_outputs"] = {"dir": args.dump_dir, "sum_mode": args.mode, "sample": dumped}
         if not args.no_cpu and world == 1:  # (the CPU baseline is a one-GPU-run item: rank 0 at N=1 only)
+            phase("CPU baseline")
             out["cpu_baseline"] = cpu_baseline(N, L, bits, r, rpos, wb)
         if chunk_sample is not None:
             out["config"]["chunk_wallclock_sample"] = chunk_sample

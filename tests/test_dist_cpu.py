@@ -249,7 +249,8 @@ def test_launcher_really_starts_two_ranks(tmp_path):
     with socket.socket() as sk:
         sk.bind(("127.0.0.1", 0))
         port = sk.getsockname()[1]
-    env = dict(os.environ, PYTHONPATH=os.pathsep.join([ROOT, os.path.join(ROOT, "tests")]))
+    # (GPUs hidden: the ranks take the gloo route on a machine with GPUs too, as the stub stages need no device)
+    env = dict(os.environ, PYTHONPATH=os.pathsep.join([ROOT, os.path.join(ROOT, "tests")]), HIP_VISIBLE_DEVICES="-1")
     p = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
                         "--master-addr", "127.0.0.1", "--master-port", str(port), "-m", "relate_amd.dist", str(out),
                         "--stages", "stubs.stub_stages"], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, env=env,
@@ -280,7 +281,8 @@ def test_launcher_by_targets_three_ranks(tmp_path):
     with socket.socket() as sk:
         sk.bind(("127.0.0.1", 0))
         port = sk.getsockname()[1]
-    env = dict(os.environ, PYTHONPATH=os.pathsep.join([ROOT, os.path.join(ROOT, "tests")]))
+    # (GPUs hidden: the ranks take the gloo route on a machine with GPUs too, as the stub stages need no device)
+    env = dict(os.environ, PYTHONPATH=os.pathsep.join([ROOT, os.path.join(ROOT, "tests")]), HIP_VISIBLE_DEVICES="-1")
     p = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "3",
                         "--master-addr", "127.0.0.1", "--master-port", str(port), "-m", "relate_amd.dist", str(out),
                         "--by-targets", "--in-flight", "2", "--stages", "stubs.stub_stages"], stdout=subprocess.PIPE,

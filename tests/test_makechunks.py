@@ -16,6 +16,8 @@ from golden_util import Fixture
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CLI = os.path.join(ROOT, "relate_amd", "Relate")
+# the reference's bundled example data (example/data/example.haps.gz, example.sample.gz), stored unchanged
+EXAMPLE = os.path.join(ROOT, "tests", "golden", "example_data")
 
 
 def write_synth_haps(work, N, L, seed):
@@ -93,12 +95,10 @@ def test_makechunks_matches_committed_reference_outputs(tmp_path, tag, memory, e
         assert "chunk_2.hap" in want  # several overlapping chunks
 
 
-@pytest.mark.skipif(not os.path.exists("/root/reference/example/data/example.haps.gz"),
-                    reason="reference example data not present")
 def test_makechunks_example_data_matches_fixture(tmp_path):
     # the example8 fixture's chunk files were produced by the reference's MakeChunks
     # from the first 3000 SNPs of example/data with a uniform 1 cM/Mb map (tools/make_golden.py)
-    src = "/root/reference/example/data"
+    src = EXAMPLE
     work = str(tmp_path)
     lines = []
     with gzip.open(os.path.join(src, "example.haps.gz"), "rt") as f:
@@ -123,11 +123,10 @@ def test_makechunks_example_data_matches_fixture(tmp_path):
 
 
 @pytest.mark.ref
-@pytest.mark.skipif(not rlutil.have_ref() or not os.path.exists("/root/reference/example/data/example.haps.gz"),
-                    reason="oracle/_ref or the reference example data not present")
+@pytest.mark.skipif(not rlutil.have_ref(), reason="oracle/_ref not built (no /root/reference)")
 def test_makechunks_gz_example_matches_reference(tmp_path):
     # the full bundled example (gzip input, N=8), cut into several chunks by a small --memory
-    src = "/root/reference/example/data"
+    src = EXAMPLE
     work = str(tmp_path)
     with open(os.path.join(work, "ex.map"), "w") as f:
         f.write("pos COMBINED_rate Genetic_Map\n")
