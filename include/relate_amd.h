@@ -135,11 +135,23 @@ int rl_paint_times(const rl_ctx *ctx, float *fwd_ms, float *bwd_ms);
  * per target (relate_amd/csrc/launch.h) -- which kernel instantiation runs. */
 int rl_register_tile(const rl_ctx *ctx, int *S, int *waves);
 
-/* Test hook: `batch` arrays of n doubles each are summed, one wavefront per
- * array, with the summation machinery of the painting kernels (sum_mode as
- * for rl_paint); out[b] receives the sum of array b.  RL_SUM_EXACT and
- * RL_SUM_EXACT_SERIAL must return the left-to-right IEEE sum bit for bit. */
+/* Test hook: `batch` arrays of n doubles each are summed with the summation
+ * machinery of the painting kernels (sum_mode as for rl_paint); out[b]
+ * receives the sum of array b.  RL_SUM_EXACT and RL_SUM_EXACT_SERIAL must
+ * return the left-to-right IEEE sum bit for bit.  1 <= n <= 10240: an array
+ * gets the waves a target of N = n donors gets (two for n > 5120).
+ * rl_debug_wave_sum_ex: one workgroup sums rows_per_group consecutive arrays
+ * in order (batch a multiple of it), as a step loop of the kernels does.
+ * mismatch == NULL: the terms are x; else (uint8 [batch][n]) they are
+ * (mismatch ? th : nth) * x, read through a lane-mask panel as in the
+ * backward passes.  stats8 (may be NULL) receives the path counters of
+ * RL_SUM_EXACT, counted per wave: sums, serial fallbacks, walked lanes,
+ * multi-binade reruns, then four cycle counts.  Bad arguments: RL_EINVAL
+ * before any device work. */
 int rl_debug_wave_sum(const double *x, int n, int batch, int sum_mode, double *out);
+int rl_debug_wave_sum_ex(const double *x, int n, int batch, int rows_per_group, int sum_mode,
+                         const uint8_t *mismatch, double th, double nth, double *out,
+                         unsigned long long *stats8);
 
 /* Experiment builds only (kernels compiled with -DRL_STATS and
  * RELATE_AMD_STATS set): 16 event counters of the last rl_paint. */

@@ -71,6 +71,23 @@ def device_count():
     return lib().rl_device_count()
 
 
+def debug_wave_sum(x, sum_mode, rows_per_group=1, mismatch=None, th=0.001, nth=0.999):
+    """rl_debug_wave_sum_ex: the kernels' sum of each row of x [batch][n] (terms (mismatch ? th : nth) * x if
+    mismatch is given) -> (sums [batch], stats), stats = the RL_SUM_EXACT path counters, counted per wave"""
+    x = np.ascontiguousarray(x, dtype=np.float64)
+    batch, n = x.shape
+    if mismatch is not None:
+        mismatch = np.ascontiguousarray(mismatch, dtype=np.uint8)
+        assert mismatch.shape == x.shape
+    out = np.empty(batch, np.float64)
+    st = np.zeros(8, np.uint64)
+    f = lib().rl_debug_wave_sum_ex
+    f.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_double, C.c_double, C.c_void_p,
+                  C.c_void_p]
+    _check(f(_p(x), n, batch, rows_per_group, sum_mode, _p(mismatch), th, nth, _p(out), _p(st)))
+    return out, {"sums": int(st[0]), "fallbacks": int(st[1]), "walked": int(st[2]), "reruns": int(st[3])}
+
+
 class Context:
     """One chunk on one GPU (rl_ctx)."""
 

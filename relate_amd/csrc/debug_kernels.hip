@@ -1,67 +1,170 @@
 // debug_kernels.hip -- test hook: the wavefront sums of paint_device.h /
-// exact_sum.h applied to caller-supplied arrays (one wave per array), so that
-// tests can drive sum_exact_fast with adversarial inputs (ties, terms spanning
-// many binades, totals next to powers of two) and compare with a literal
-// left-to-right sum.
+// exact_sum.h applied to caller-supplied arrays, so that tests can drive
+// sum_exact_fast with adversarial inputs (ties, terms spanning many binades,
+// totals next to powers of two) and compare with a literal left-to-right sum.
+//
+// The hook runs at the kernels' real geometry: an array of n terms gets
+// target_waves(n) waves (two for n > 5120, meeting in LDS through one
+// WaveLink), and a workgroup sums several arrays back to back on that WaveLink,
+// as a step loop of K1 does.  The terms are the registers themselves (RegTerm,
+// the forward passes) or (mismatch ? th : nth) * x under the EXEC masks of a
+// lane-mask panel (MaskTerm, the backward passes).
+//
+// This translation unit alone is compiled with the path counters of exact_sum.h
+// (RL_STATS); the Makefile has no -fgpu-rdc, so the paint and repaint objects
+// stay free of them.
+#define RL_STATS 1
 #include "paint_device.h"
 #include "exact_sum.h"
 #include "launch.h"
 #include "common.h"
 
+#include <vector>
+
 namespace rl {
 
-template <int S, int MODE>
-__global__ void __launch_bounds__(64) sum_kernel(const double *__restrict__ x, int n, double *__restrict__ out) {
-  __shared__ __attribute__((aligned(16))) float stage[16 * 64];
-  (void)stage;
-  const int lane = threadIdx.x & 63, q = n / 64, rem = n % 64;  // the kernels' layout over n terms
-  const int start = lane * q + (lane < rem ? lane : rem), len = q + (lane < rem ? 1 : 0);
-  const double *xb = x + (size_t)blockIdx.x * n;
-  double a[S];
+constexpr int SUM_STATS = 8;  // exact_sum.h RL_STAT: sums, fallbacks, walked lanes, reruns, then 4 cycle counts
+
+template <int S, int MODE, int WAVES, bool MASK>
+__global__ void __launch_bounds__(64 * WAVES) sum_kernel(const double *__restrict__ x, int n, int rows_per_group,
+                                                         const unsigned long long *__restrict__ masks, double th,
+                                                         double nth, double *__restrict__ out,
+                                                         unsigned long long *__restrict__ stats) {
+  __shared__ WaveLinkStorage link;
+  __shared__ unsigned long long lstats[SUM_STATS];
+  WaveLink<WAVES> lk;
+  lk.s = &link;
+  lk.w = WAVES > 1 ? __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)) : 0;
+  if (threadIdx.x < SUM_STATS) lstats[threadIdx.x] = 0;
+  __syncthreads();
+  // the kernels' layout over n terms (make_layout(n, WAVES), PaintLane::init)
+  const int q = n / (64 * WAVES), rem = n % (64 * WAVES), vl = 64 * lk.w + (threadIdx.x & 63);
+  const int start = vl * q + (vl < rem ? vl : rem), len = q + (vl < rem ? 1 : 0);
+  for (int r = 0; r < rows_per_group; r++) {
+    const size_t row = (size_t)blockIdx.x * rows_per_group + r;
+    const double *xb = x + row * n;
+    double a[S];
 #pragma unroll
-  for (int i = 0; i < S; i++) a[i] = (i < len) ? xb[start + i] : 0.0;
-  const RegTerm<S> t{a};
-  const double r = wave_sum<MODE, S>(t, local_sum<S>(t));
-  if (lane == 0) out[blockIdx.x] = r;
+    for (int i = 0; i < S; i++) a[i] = (i < len) ? xb[start + i] : 0.0;
+    double sum;
+    if constexpr (MASK) {
+      const MaskTerm<S> t{(MaskRow)(masks + (row * WAVES + lk.w) * S), a, th, nth, lstats};
+      sum = wave_sum<MODE, S, WAVES>(t, local_sum<S>(t), lk);
+    } else {
+      const RegTerm<S> t{a, 0.0, 0.0, lstats};
+      sum = wave_sum<MODE, S, WAVES>(t, local_sum<S>(t), lk);
+    }
+    if (threadIdx.x == 0) out[row] = sum;
+  }
+  __syncthreads();
+  if (threadIdx.x < SUM_STATS && lstats[threadIdx.x]) atomicAdd(&stats[threadIdx.x], lstats[threadIdx.x]);
+}
+
+template <int S, int MODE, int WAVES>
+static hipError_t launch_sum_t(const double *x, int n, int groups, int rows_per_group, const unsigned long long *masks,
+                               double th, double nth, double *out, unsigned long long *stats) {
+  if (masks)
+    hipLaunchKernelGGL((sum_kernel<S, MODE, WAVES, true>), dim3(groups), dim3(64 * WAVES), 0, nullptr, x, n,
+                       rows_per_group, masks, th, nth, out, stats);
+  else
+    hipLaunchKernelGGL((sum_kernel<S, MODE, WAVES, false>), dim3(groups), dim3(64 * WAVES), 0, nullptr, x, n,
+                       rows_per_group, masks, th, nth, out, stats);
+  return hipGetLastError();
 }
 
 template <int MODE>
-static hipError_t launch_sum(const double *x, int n, int batch, double *out, int S, hipStream_t st) {
-  switch (S) {
-#define RL_CASE(s, t)                                                                         \
-  case s:                                                                                     \
-    hipLaunchKernelGGL((sum_kernel<s, MODE>), dim3(batch), dim3(64), 0, st, x, n, out); \
-    return hipGetLastError();
-    RL_FOR_EACH_S(RL_CASE)
+static hipError_t launch_sum(int S, int waves, const double *x, int n, int groups, int rows_per_group,
+                             const unsigned long long *masks, double th, double nth, double *out,
+                             unsigned long long *stats) {
+  if (waves == 1) {
+    switch (S) {
+#define RL_CASE(s, t) \
+  case s:             \
+    return launch_sum_t<s, MODE, 1>(x, n, groups, rows_per_group, masks, th, nth, out, stats);
+      RL_FOR_EACH_S(RL_CASE)
 #undef RL_CASE
+    }
+  } else {
+#ifndef RL_ONLY_S
+    switch (S) {
+#define RL_CASE(s, t) \
+  case s:             \
+    return launch_sum_t<s, MODE, 2>(x, n, groups, rows_per_group, masks, th, nth, out, stats);
+      RL_FOR_EACH_S_2WAVES(RL_CASE)
+#undef RL_CASE
+    }
+#endif
   }
   return hipErrorInvalidValue;
 }
 
 }  // namespace rl
 
-extern "C" int rl_debug_wave_sum(const double *x, int n, int batch, int sum_mode, double *out) {
+extern "C" int rl_debug_wave_sum_ex(const double *x, int n, int batch, int rows_per_group, int sum_mode,
+                                    const uint8_t *mismatch, double th, double nth, double *out,
+                                    unsigned long long *stats8) {
   using namespace rl;
-  if (!x || !out || n < 1 || batch < 1) return RL_EINVAL;
-  const Layout lay = make_layout(n);
-  const int S = choose_S(lay);
-  if (!S) {
-    set_error("rl_debug_wave_sum: n too large");
+  if (!x || !out) {
+    set_error("rl_debug_wave_sum_ex: null x or out");
     return RL_EINVAL;
   }
-  DevBuf dx, dout;
+  if (n < 1 || n > 2 * 80 * 64) {
+    set_error("rl_debug_wave_sum_ex: n=%d outside 1..%d", n, 2 * 80 * 64);
+    return RL_EINVAL;
+  }
+  if (rows_per_group < 1 || batch < 1 || batch % rows_per_group) {
+    set_error("rl_debug_wave_sum_ex: batch=%d must be a positive multiple of rows_per_group=%d", batch,
+              rows_per_group);
+    return RL_EINVAL;
+  }
+  const int waves = target_waves(n);
+  const Layout lay = make_layout(n, waves);
+  const int S = choose_S(lay);  // (two waves: 48, 64 or 80, the RL_FOR_EACH_S_2WAVES set)
+  if (!S) {
+    set_error("rl_debug_wave_sum_ex: no register tile for n=%d", n);
+    return RL_EINVAL;
+  }
+  // the lane-mask panel of the mismatches (launch_lane_masks' format): per row, `waves` consecutive runs of S words;
+  // bit l of word j of wave w = register j of virtual lane 64w + l holds a mismatch
+  std::vector<unsigned long long> masks;
+  if (mismatch) {
+    masks.assign((size_t)batch * waves * S, 0ull);
+    for (size_t b = 0; b < (size_t)batch; b++)
+      for (int vl = 0; vl < 64 * waves; vl++) {
+        const int start = vl * lay.q + (vl < lay.rem ? vl : lay.rem), len = lay.q + (vl < lay.rem ? 1 : 0);
+        unsigned long long *words = &masks[(b * waves + vl / 64) * S];
+        for (int j = 0; j < len; j++)
+          if (mismatch[b * n + start + j]) words[j] |= 1ull << (vl & 63);
+      }
+  }
+  DevBuf dx, dout, dmask, dstats;
   int rc;
   if ((rc = dx.alloc(sizeof(double) * (size_t)n * batch))) return rc;
   if ((rc = dout.alloc(sizeof(double) * batch))) return rc;
+  if ((rc = dstats.alloc(sizeof(unsigned long long) * SUM_STATS))) return rc;
+  if (mismatch && (rc = dmask.alloc(sizeof(unsigned long long) * masks.size()))) return rc;
   RL_HIP(hipMemcpy(dx.p, x, sizeof(double) * (size_t)n * batch, hipMemcpyHostToDevice));
+  RL_HIP(hipMemset(dstats.p, 0, sizeof(unsigned long long) * SUM_STATS));
+  if (mismatch)
+    RL_HIP(hipMemcpy(dmask.p, masks.data(), sizeof(unsigned long long) * masks.size(), hipMemcpyHostToDevice));
+  const unsigned long long *dm = mismatch ? dmask.as<unsigned long long>() : nullptr;
+  const int groups = batch / rows_per_group;
   hipError_t e;
   switch (kernel_mode(sum_mode)) {
-    case 0: e = launch_sum<0>(dx.as<double>(), n, batch, dout.as<double>(), S, nullptr); break;
-    case 1: e = launch_sum<1>(dx.as<double>(), n, batch, dout.as<double>(), S, nullptr); break;
-    default: e = launch_sum<2>(dx.as<double>(), n, batch, dout.as<double>(), S, nullptr); break;
+#define RL_ARGS S, waves, dx.as<double>(), n, groups, rows_per_group, dm, th, nth, dout.as<double>(), \
+                dstats.as<unsigned long long>()
+    case 0: e = launch_sum<0>(RL_ARGS); break;
+    case 1: e = launch_sum<1>(RL_ARGS); break;
+    default: e = launch_sum<2>(RL_ARGS); break;
+#undef RL_ARGS
   }
   RL_HIP(e);
   RL_HIP(hipDeviceSynchronize());
   RL_HIP(hipMemcpy(out, dout.p, sizeof(double) * batch, hipMemcpyDeviceToHost));
+  if (stats8) RL_HIP(hipMemcpy(stats8, dstats.p, sizeof(unsigned long long) * SUM_STATS, hipMemcpyDeviceToHost));
   return RL_OK;
+}
+
+extern "C" int rl_debug_wave_sum(const double *x, int n, int batch, int sum_mode, double *out) {
+  return rl_debug_wave_sum_ex(x, n, batch, 1, sum_mode, nullptr, 0.0, 0.0, out, nullptr);
 }

@@ -390,7 +390,12 @@ RL_DEV double sum_exact_fast(const T &term, double L, WaveLink<WAVES> &lk) {
   while (todo) {
     const int q = __builtin_ctzll(todo);
     todo &= todo - 1;
-    {  // tie-free lanes since the previous walked lane (composite sits in lane q-1)
+    // tie-free lanes since the previous walked lane (composite sits in lane q-1).  Only wave 1 can walk its lane 0
+    // (virtual lane 64 enters at wave 0's total, and its run can hold a tie or a two-binade jump): nothing of this
+    // wave lies before it, and delta is already its entry offset -- lane q-1 = -1 would read lane 63 (the lane select
+    // keeps 6 bits), the composite of this wave's trailing lanes.  Lane 0 of wave 0 enters at exactly +0.0 and is
+    // never walked.
+    if (WAVES == 1 || q > 0) {
       const int K = __builtin_amdgcn_readlane(sK, q - 1), C = __builtin_amdgcn_readlane(sC, q - 1);
       const int sft = __builtin_amdgcn_readlane(sS, q - 1) & 63;
       delta = ((delta + K) >> sft) + C;

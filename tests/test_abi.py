@@ -64,6 +64,30 @@ def test_synth_panel_deterministic_and_chunk_files_roundtrip(tmp_path):
     assert np.array_equal(c.seq, a.seq) and np.array_equal(c.wb, a.wb)
 
 
+def test_debug_wave_sum_refuses_bad_arguments():
+    """rl_debug_wave_sum_ex: RL_EINVAL with a message before any device work (so also without a GPU)"""
+    lib = api.lib()
+    f = lib.rl_debug_wave_sum_ex
+    f.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_double, C.c_double, C.c_void_p,
+                  C.c_void_p]
+    x = np.ones(4 * 10241)
+    out = np.zeros(4)
+    px, po = x.ctypes.data_as(C.c_void_p), out.ctypes.data_as(C.c_void_p)
+    bad = [((None, 8, 1, 1, 0, po), "null"), ((px, 8, 1, 1, 0, None), "null"),
+           ((px, 0, 1, 1, 0, po), "n=0"), ((px, -5, 1, 1, 0, po), "n=-5"), ((px, 10241, 1, 1, 0, po), "n=10241"),
+           ((px, 8, 4, 0, 0, po), "rows_per_group=0"), ((px, 8, 4, 3, 0, po), "rows_per_group=3"),
+           ((px, 8, 0, 1, 0, po), "batch=0")]
+    for (xp, n, batch, rpg, mode, op), msg in bad:
+        rc = f(xp, n, batch, rpg, mode, None, 0.001, 0.999, op, None)
+        assert rc == -1, (n, batch, rpg)  # RL_EINVAL
+        err = lib.rl_last_error().decode()
+        assert err.startswith("rl_debug_wave_sum_ex:") and msg in err, err
+    # the old entry is the special case: the same checks
+    assert lib.rl_debug_wave_sum(px, 10241, 1, 0, po) == -1
+    assert b"n=10241" in lib.rl_last_error()
+    assert not out.any()
+
+
 def test_stage_opts_that_never_saw_init_are_refused():
     """a zeroed rl_stage_opts (size 0) must not silently run with the defaults: RL_EINVAL before any
     device work, from all three *_ex stages"""
