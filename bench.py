@@ -6,7 +6,13 @@ resident in HBM: the backward and the forward pass for all N targets, one
 launch of 2N workgroups (replacing the loop of pipeline/Paint.cpp:81-87 in the
 reference).
 
-    python bench.py [--gpus N --steps K --warmup W] [--haplotypes 5000 --snps 500000] [--dump-outputs DIR]
+    python bench.py [--gpus N --steps K --warmup W] [--haplotypes 5000 --snps 500000] [--dump-outputs DIR] [--full]
+
+A plain run does what the headline figure needs and nothing else: it makes and uploads the chunk, warms up, times the
+steps, writes --dump-outputs and prints the line.  --full adds every secondary measurement to the same line: the chunk
+wall-clock sample and the whole C3 chunk through the CLI (child processes, before this process touches the GPU), each
+pass alone, the other summation modes, RePaint and the distance matrix of one window (or the gathered matrix of
+--shard targets) and the CPU baseline; the --skip-* options leave single ones out of such a run.
 
 With --gpus N > 1 there is one rank per GPU: launched by torch.distributed.run (the
 driver's way), or -- when no launcher set RANK -- by bench.py itself as a child
@@ -209,7 +215,7 @@ def dump_outputs(out_dir, ctxs, chunk_ids, world):
 def chunk_wallclock_full():
     """The metric's other half MEASURED: the whole C3 chunk -- Paint + BuildTopology of all 267 sections, files in ->
     .anc / .mut files out -- through `Relate --mode PaintBuildTopology` in a child process (tools/chunk_c3_fused.py).
-    BENCH_C3_RUNS runs (default 2 -- a third would take the default bench past ten minutes; BENCH_C3_RUNS=3 for
+    BENCH_C3_RUNS runs (default 2 -- a third would take `--full` past ten minutes; BENCH_C3_RUNS=3 for
     minimum / median / maximum; ~3 minutes each with the chunk's generation; profiles/r05_c3_runs.json holds sixty): the first with the stage's timing lines (RELATE_AMD_TIMING:
     trees built, RePaint busy seconds, `stage_lines`), the others without; every run's seconds are reported.  Before
     this process touches the GPU."""
@@ -326,6 +332,9 @@ def main():
     ap.add_argument("--snps", dest="l", type=int, default=500000, help="SNPs")
     ap.add_argument("--memory", type=float, default=20.0, help="--memory of MakeChunks (window rule), GB")
     ap.add_argument("--mode", default="exact", choices=["exact", "lanes", "lanes32"])
+    ap.add_argument("--full", action="store_true",
+                    help="also take every secondary measurement (chunk wall-clock runs, each pass alone, the other "
+                         "summation modes, RePaint / matrix, CPU baseline; ~9 minutes at C3) into the result line")
     ap.add_argument("--skip-cpu", dest="no_cpu", action="store_true")
     ap.add_argument("--skip-alt", dest="no_alt", action="store_true", help="skip timing the other summation mode")
     ap.add_argument("--skip-k23", dest="skip_k23", action="store_true", help="skip the RePaint / matrix measurement")
@@ -388,7 +397,7 @@ def main():
     if rank == 0:
         heartbeat()
     chunk_sample = chunk_full = chunk_host = None
-    if world == 1 and args.n == 5000 and args.workload == "c3" and not args.skip_chunk:
+    if args.full and world == 1 and args.n == 5000 and args.workload == "c3" and not args.skip_chunk:
         phase("chunk wall-clock sample (child process)")
         chunk_sample = chunk_wallclock_sample()
         if args.with_host and not args.skip_host:
@@ -472,8 +481,9 @@ def main():
     if args.dump_dir:
         phase("writing the outputs of the last timed step to %s" % args.dump_dir)
     dumped = dump_outputs(args.dump_dir, ctxs, my_chunks, world) if args.dump_dir else None
-    phase("secondary measurements")
-    fwd_ms, bwd_ms = split_times(mode) if rank == 0 else (0.0, 0.0)
+    if args.full:
+        phase("secondary measurements")
+    fwd_ms, bwd_ms = split_times(mode) if rank == 0 and args.full else (0.0, 0.0)
 
     # the other summation modes on the same chunk (config.other_modes): `lanes` (re-associated sums, FP64 state) and
     # `lanes32` (the fast mode: packed-FP32 state, paint32_kernels.hip) next to the bit-exact default.  Useful
@@ -485,7 +495,7 @@ def main():
         fast_report = json.load(open(sorted(glob.glob(os.path.join(ROOT, "profiles", "r*_fast_modes.json")))[-1]))
     except Exception:
         pass
-    if not args.no_alt:
+    if args.full and not args.no_alt:
         for name, other in MODES.items():
             if other == mode:
                 continue
@@ -510,7 +520,7 @@ def main():
     # secondary kernels of the path on the same chunk (reported under config, not timed steps):
     # K2 RePaintSection of one window for all targets, K3 one N x N distance matrix
     gather = None
-    if by_target:  # every rank: rows of one distance matrix -> all-gather (RCCL) -> N x N on every rank
+    if args.full and by_target:  # every rank: rows of one distance matrix -> all-gather (RCCL) -> N x N on every rank
         w = (len(wb) - 1) // 2
         win = ctx.open_window(w, None, int(wb[w]), mode)
         k0, k1 = ctx.target_range()
@@ -537,7 +547,7 @@ def main():
                 break
         except Exception:
             pmc = None
-    if rank == 0 and not args.skip_k23 and not by_target:
+    if args.full and rank == 0 and not args.skip_k23 and not by_target:
         try:
             w = (len(wb) - 1) // 2
             ctx.open_window(w, None, int(wb[w]), mode).close()   # first launch loads the kernel's code object
@@ -638,11 +648,15 @@ def main():
                                        "peak_Tinstr_per_s": FP64_PEAK_TINSTR,
                                        "frac": useful / FP64_PEAK_TINSTR}},
         }
+        if not args.full:  # (a plain run measures none of these)
+            for k in ("fwd_alone_ms", "bwd_alone_ms", "other_mode", "other_modes", "repaint_and_matrix",
+                      "target_shard_matrix"):
+                del out["config"][k]
         if roofline_k2 is not None:
             out["roofline_k2"] = roofline_k2
         if dumped is not None:
             out["dump_outputs"] = {"dir": args.dump_dir, "sum_mode": args.mode, "sample": dumped}
-        if not args.no_cpu and world == 1:  # (the CPU baseline is a one-GPU-run item: rank 0 at N=1 only)
+        if args.full and not args.no_cpu and world == 1:  # (the CPU baseline is a one-GPU-run item: rank 0 at N=1 only)
             phase("CPU baseline")
             out["cpu_baseline"] = cpu_baseline(N, L, bits, r, rpos, wb)
         if chunk_sample is not None:

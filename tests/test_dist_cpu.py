@@ -310,3 +310,15 @@ def test_bench_self_launch_command():
     assert cmd[1:4] == ["-m", "torch.distributed.run", "--nnodes=1"]
     assert cmd[cmd.index("--nproc-per-node") + 1] == "4" and cmd[cmd.index("--master-addr") + 1] == "127.0.0.1"
     assert cmd[-4:] == ["--gpus", "4", "--steps", "3"] and cmd[-5].endswith("bench.py")
+
+
+def test_bench_full_reaches_the_ranks():
+    """--full (the secondary measurements) is an option of every rank: the self-launch hands it on"""
+    import json
+    import subprocess
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--full", "--print-launch"],
+                       stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=300,
+                       env={k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK")})
+    assert p.returncode == 0, p.stderr.decode()[-1500:]
+    cmd = json.loads(p.stdout.decode().strip().split("\n")[-1])
+    assert cmd[-3:] == ["--gpus", "2", "--full"] and cmd[-4].endswith("bench.py")

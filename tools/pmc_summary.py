@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """HBM traffic (rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE, separate passes, tools/gpu_r06_i.sh)
-of the Paint and RePaint kernels of `python3 bench.py --steps 1 --warmup 0 --skip-cpu --skip-chunk --skip-alt`.
+of the Paint and RePaint kernels of `python3 bench.py --full --steps 1 --warmup 0 --skip-cpu --skip-chunk --skip-alt`.
 rocprofv3 reports both counters in KB per dispatch (MI355X_MICROARCH.md, HBM section); the guide's gfx950 correction:
 FETCH_SIZE under-reports loads that bypass the VGPRs (`global_load_lds_dwordx4`, 16 B per lane) by 2x -- applied to
 the checkpoint rows the backward RePaint kernel reads that way (stated separately, `fetch_bytes_corrected`)."""
