@@ -401,6 +401,36 @@ int rl_stage_paint_build_topology(const char *out_dir, int chunk_index,
                             int use_painting, double theta, double rho,
                             int flags, int fb, int sum_mode, int device);
 
+/* ---------------------------------------------------- OptimizeParameters */
+/* `Relate --mode OptimizeParameters` (pipeline/OptimizeParameters.cpp:22-206): for every (theta, recombination factor)
+ * of a grid, the number of SNPs that do not map onto the tree built at that very SNP.
+ *   rl_optimize_section replaces AncesTreeBuilder::OptimizeParameters (src/anc_builder.cpp:821-973) for one section
+ *     of a context whose stepping stones are painted (rl_paint): RePaintSection with theta and r = stored r *
+ *     rec_factor (OptimizeParameters.cpp:151-157; the stones are NOT re-painted, as in the reference, where
+ *     Paint(options, c) at :159 reads the chunk files afresh), then a tree at every SNP from the matrix with the SNP
+ *     cancelled (:869-882), MinMatch::QuickBuild without a prior, MapMutation without random flipping (:1064-1139);
+ *     *count receives the SNPs whose mapping came back > 1.  The reference's `seed` argument seeds a generator the
+ *     path never draws from: there is none here.  Trees on the context's GPU (RELATE_AMD_GPU_BUILD=0: on the host).
+ *     The context KEEPS the grid point's theta and factor as its painting parameters afterwards: a later rl_paint
+ *     would paint with them -- call rl_set_painting first if the stones are to be painted again.
+ *   rl_stage_optimize_parameters replaces the loop over grid points and sections of ONE chunk
+ *     (OptimizeParameters.cpp:142-177): the chunk is painted once (opts: --painting, sum_mode, device and the
+ *     stage's knobs), every pair runs all sections under the BuildTopology stage's admission rule, and
+ *     counts[i * n_factor + j] is ADDED TO (the caller sums over chunks, :172).  theta in (0,1), factor > 0
+ *     (:92-95, :103-106), else RL_EINVAL with the reference's message. */
+int rl_optimize_section(rl_ctx *ctx, int section, float theta, float rec_factor, int *count);
+int rl_stage_optimize_parameters(const char *out_dir, int chunk_index, const float *theta, int n_theta,
+                                 const float *factor, int n_factor, const rl_stage_opts *opts, int *counts);
+/* Test hook (host only): AncesTreeBuilder::MapMutation without random flipping (src/anc_builder.cpp:1064-1139,
+ * PropagateMutationGlobal :1237-1341) for the tree `parent` (2N-1 entries, root = -1, a parent's label above its
+ * children's, as MinMatch numbers them) and N carrier flags: 1 = maps, 2 = maps flipped, 3 = does not map. */
+int rl_debug_map_mutation(int N, const int *parent, const char *carriers);
+/* Test hook: the per-tree pass of the mode over a distance matrix on the GPU (relate_amd/csrc/optimize_kernels.hip
+ * cancel_rowmin_kernel): d (N*N floats, in place) gets the cancellation of src/anc_builder.cpp:869-882 for the
+ * carriers, rowmin (N floats) the minimum of every row off its diagonal as the rows then are
+ * (src/tree_builder.cpp:59-146 starts from them).  2 <= N <= 10240. */
+int rl_debug_cancel_rowmin(float *d, int N, const char *carriers, float log_ratio, float *rowmin);
+
 /* ------------------------------------- one chunk sharded by target haplotype */
 /* BASELINE.json config #5 (N = 10,000 x L = 200k: 8 N^2 W = 288 GB of stepping stones, more than one GPU holds).
  * The reference's unit is the section (scripts/RelateParallel/RelateParallel.sh:231-257): each BuildTopology process

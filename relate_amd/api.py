@@ -54,6 +54,15 @@ def lib():
                                     C.c_void_p]
         L.rl_set_painting.argtypes = [C.c_void_p, C.c_double, C.c_double]
         L.rl_window_matrix_rows_device.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+        L.rl_optimize_section.restype = C.c_int
+        L.rl_optimize_section.argtypes = [C.c_void_p, C.c_int, C.c_float, C.c_float, C.POINTER(C.c_int)]
+        L.rl_stage_optimize_parameters.restype = C.c_int
+        L.rl_stage_optimize_parameters.argtypes = [C.c_char_p, C.c_int, C.POINTER(C.c_float), C.c_int,
+                                                   C.POINTER(C.c_float), C.c_int, C.c_void_p, C.POINTER(C.c_int)]
+        L.rl_debug_map_mutation.restype = C.c_int
+        L.rl_debug_map_mutation.argtypes = [C.c_int, C.c_void_p, C.c_void_p]
+        L.rl_debug_cancel_rowmin.restype = C.c_int
+        L.rl_debug_cancel_rowmin.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_float, C.c_void_p]
         _lib = L
     return _lib
 
@@ -212,6 +221,14 @@ class Context:
         buf = C.create_string_buffer(n.value)
         _check(lib().rl_paint_record(C.c_void_p(self._h), int(w), int(k), buf, C.c_size_t(n.value), C.byref(n)))
         return buf.raw[:n.value]
+
+    def optimize_section(self, section, theta, rec_factor):
+        """rl_optimize_section: SNPs of `section` that do not map onto the tree built at them, for one grid point of
+        `--mode OptimizeParameters` (the context must be painted)"""
+        n = C.c_int(0)
+        _check(lib().rl_optimize_section(C.c_void_p(self._h), int(section), float(theta), float(rec_factor),
+                                         C.byref(n)))
+        return n.value
 
     def open_window(self, w, paint_file=None, first_snp=None, sum_mode=RL_SUM_EXACT, max_rows=0):
         """max_rows > 0: keep at most that many posterior rows resident (rl_window_open_bounded)"""
@@ -485,6 +502,49 @@ def stage_build_topology_ex(out_dir, chunk_index, first_section, last_section, o
     f = lib().rl_stage_paint_build_topology_ex if fused else lib().rl_stage_build_topology_ex
     f.argtypes = [C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_void_p]
     _check(f(out_dir.encode(), chunk_index, first_section, last_section, C.byref(opts)))
+
+
+# the grid `Relate --mode OptimizeParameters` tries without --input (pipeline/OptimizeParameters.cpp:76-77)
+OPTIMIZE_THETAS = (1e-4, 1e-3, 1e-2, 1e-1)
+OPTIMIZE_FACTORS = (0.001, 0.1, 1, 10, 100)
+
+
+def optimize_parameters(out_dir, chunk, thetas=OPTIMIZE_THETAS, factors=OPTIMIZE_FACTORS, opts=None):
+    """rl_stage_optimize_parameters on one chunk of a MakeChunks directory: the chunk is painted once, every
+    (theta, recombination factor) pair re-paints and builds a tree at every SNP of every section
+    -> int array [len(thetas)][len(factors)]: SNPs that do not map onto their tree (sum over chunks for the
+    reference's .opt).  opts: a StageOpts (painting, sum_mode, device, the stage's knobs)."""
+    th = np.ascontiguousarray(thetas, dtype=np.float32)
+    fa = np.ascontiguousarray(factors, dtype=np.float32)
+    counts = np.zeros((len(th), len(fa)), np.int32)
+    _check(lib().rl_stage_optimize_parameters(out_dir.encode(), int(chunk), th.ctypes.data_as(C.POINTER(C.c_float)),
+                                              len(th), fa.ctypes.data_as(C.POINTER(C.c_float)), len(fa),
+                                              C.byref(opts) if opts is not None else None,
+                                              counts.ctypes.data_as(C.POINTER(C.c_int))))
+    return counts
+
+
+def map_mutation(parent, carriers):
+    """rl_debug_map_mutation: 1 / 2 / 3 (maps / maps flipped / does not map) for a tree given by its parent array"""
+    parent = np.ascontiguousarray(parent, dtype=np.int32)
+    carriers = np.ascontiguousarray(carriers, dtype=np.uint8)
+    N = len(carriers)
+    assert len(parent) == 2 * N - 1
+    r = lib().rl_debug_map_mutation(N, _p(parent), _p(carriers))
+    if r < 0:
+        _check(r)
+    return r
+
+
+def debug_cancel_rowmin(d, carriers, log_ratio):
+    """rl_debug_cancel_rowmin: cancel_rowmin_kernel on a copy of the N x N float32 matrix d -> (matrix, row minima)"""
+    d = np.array(d, dtype=np.float32, order="C")
+    N = d.shape[0]
+    carriers = np.ascontiguousarray(carriers, dtype=np.uint8)
+    assert d.shape == (N, N) and len(carriers) == N
+    rowmin = np.empty(N, np.float32)
+    _check(lib().rl_debug_cancel_rowmin(_p(d), N, _p(carriers), float(np.float32(log_ratio)), _p(rowmin)))
+    return d, rowmin
 
 
 def stage_find_equivalent_branches(out_dir, chunk_index=0):

@@ -185,6 +185,8 @@ struct rl_ctx {
 namespace rl {
 int build_plan(rl_ctx *ctx);
 int upload_plan(rl_ctx *ctx);
+// theta / rho of RePaint's plan changed under the painted stones (context.cpp; --mode OptimizeParameters)
+int replan_painting(rl_ctx *ctx, double theta, double rho);
 int host_threads();
 int local_world_size();  // ranks of the job on this host (LOCAL_WORLD_SIZE), 1 outside a launcher
 int local_rank();

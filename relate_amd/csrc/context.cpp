@@ -349,6 +349,61 @@ int build_plan(rl_ctx *ctx) {
   return RL_OK;
 }
 
+// `--mode OptimizeParameters` tries a grid of (theta, recombination factor) on ONE painting: the reference paints every
+// grid point from a Data of its own (pipeline/Paint.cpp:17-35 reads the chunk files again), so the grid's values reach
+// RePaintSection only (pipeline/OptimizeParameters.cpp:147-159, src/anc_builder.cpp:49-78).  Here: the painted stepping
+// stones stay where they are; of the plan only what depends on theta and on the recombination distances is made again
+// -- the constants, the interval coefficients (the same sums in the same order as build_plan's step 3) and the initial
+// beta sums -- and, when the plan is on the device, copied over what is there.  The site lists, the window slices and
+// the launch order depend on the panel alone.  No window of the context may be open.
+int replan_painting(rl_ctx *ctx, double theta, double rho) {
+  if (!ctx || !ctx->have_chunk || !(theta > 0.0 && theta < 1.0) || !(rho > 0.0)) {
+    set_error("replan_painting: theta in (0,1) and a positive factor on a loaded chunk");
+    return RL_EINVAL;
+  }
+  ctx->theta = theta;
+  ctx->rho = rho;
+  if (!ctx->plan.valid) return build_plan(ctx);
+  const int N = ctx->N, L = ctx->L, rw = ctx->row_words;
+  Plan &pl = ctx->plan;
+  ctx->consts = make_consts(N, theta);
+  const PaintConsts c = ctx->consts;
+  std::vector<double> r(ctx->r);
+  if (rho != 1.0)
+    for (auto &x : r) x *= rho;  // OptimizeParameters.cpp:154-157
+  const uint32_t *bits = ctx->bits.data();
+  const int k0 = ctx->k0, k1 = ctx->k0 + ctx->nloc;
+  parallel_for(N, [&](int k) {
+    if (k < k0 || k >= k1) return;
+    const int64_t o = pl.off[k];
+    const int D = (int)(pl.off[k + 1] - o);
+    for (int i = 0; i < D; i++) {
+      const int s0 = pl.sites[o + i] & 0x7fffffff;
+      double acc = r[s0];
+      if (i + 1 < D) {
+        const int s1 = pl.sites[o + i + 1] & 0x7fffffff;
+        for (int s = s0 + 1; s < s1; s++) acc += r[s];
+      }
+      interval_coeffs(c, N, acc, &pl.cf[o + i], &pl.nxt[o + i]);
+    }
+    const bool seqk = pl.sites[o + D - 1] < 0;
+    const uint32_t *row = bits + (size_t)(L - 1) * rw;
+    double B = 0.0;
+    for (int n = 0; n < N; n++) {
+      const bool dn = (row[n >> 5] >> (n & 31)) & 1u;
+      B += (seqk && !dn) ? c.theta : c.ntheta;
+    }
+    B -= c.ntheta;
+    pl.binit[k] = B;
+  });
+  if (!ctx->plan_on_device) return RL_OK;
+  RL_HIP(hipSetDevice(ctx->device));
+  int rc;
+  if ((rc = ctx->d_cf.upload(pl.cf)) || (rc = ctx->d_nxt.upload(pl.nxt)) || (rc = ctx->d_binit.upload(pl.binit)))
+    return rc;
+  return RL_OK;
+}
+
 int upload_plan(rl_ctx *ctx) {
   if (ctx->plan_on_device) return RL_OK;
   if (!ctx->plan.valid) {

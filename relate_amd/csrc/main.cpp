@@ -4,20 +4,26 @@
 //   Relate --mode Paint         --chunk_index c -o out [--painting theta,rho]
 //   Relate --mode BuildTopology --chunk_index c --first_section a --last_section b -o out
 //          [--painting theta,rho] [--seed s] [--fb x] [--no_consistency]
+//   Relate --mode OptimizeParameters --haps x.haps --sample x.sample --map x.map [--memory 5] [--dist f]
+//          [-i grid.txt] [--painting theta,rho] -o out      (writes out.opt: `theta factor not-mapping-SNPs` per pair)
 // Same options, files and stderr banners as include/pipeline/Relate.cpp:19-115,
 // Paint.cpp, BuildTopology.cpp of the reference; every other --mode is refused
 // (use the reference binary for them).  Extra options: --device n,
 // --sum_mode exact|lanes|lanes32, --find_equivalent_branches (with PaintBuildTopology / BuildTopology over all
 // sections of a chunk: the stage downstream fused in, every .anc written once).
 #include <sys/resource.h>
+#include <unistd.h>
 
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <iomanip>
+#include <fstream>
 #include <iostream>
 #include <map>
+#include <sstream>
 #include <string>
+#include <vector>
 
 #include "relate_amd.h"
 
@@ -27,6 +33,128 @@ static void usage_line() {
   std::cerr << "CPU Time spent: " << usage.ru_utime.tv_sec << "." << std::setfill('0') << std::setw(6)
             << usage.ru_utime.tv_usec << "s; Max Memory usage: " << usage.ru_maxrss / 1000.0 << "Mb." << std::endl;
   std::cerr << "---------------------------------------------------------" << std::endl << std::endl;
+}
+
+static const char *kModes = "MakeChunks|Paint|BuildTopology|PaintBuildTopology|FindEquivalentBranches|OptimizeParameters";
+
+// `Relate --mode OptimizeParameters` (pipeline/OptimizeParameters.cpp:22-206): MakeChunks, then for every chunk the
+// grid of (theta, recombination factor) through rl_stage_optimize_parameters, the temporary files removed as the
+// reference's Clean leaves them (pipeline/Clean.cpp:16-138), and <output>.opt next to (not inside) the directory.
+static int optimize_parameters(std::map<std::string, std::string> &opt, rl_stage_opts &so) {
+  if (!opt.count("haps") || !opt.count("sample") || !opt.count("map") || !opt.count("output") || opt.count("help")) {
+    if (!opt.count("help")) {
+      std::cout << "Not enough arguments supplied." << std::endl;
+      std::cout << "Needed: haps, sample, map, output. Optional: dist." << std::endl;
+    }
+    std::cout << "Usage: Relate --mode " << kModes << " [options]" << std::endl;
+    std::cout << "  OptimizeParameters: --haps x.haps --sample x.sample --map x.map -o out [--memory GB] [--dist f] "
+                 "[-i,--input grid] [--painting theta,rho]" << std::endl;
+    std::cout << "Use to make smaller chunks from the data." << std::endl;
+    return 0;  // (exit(0), OptimizeParameters.cpp:30-34)
+  }
+  const std::string out = opt["output"];
+  std::cerr << "############" << std::endl;
+  std::cerr << "Optimizing Parameters..." << std::endl;
+  std::cerr << "---------------------------------------------------------" << std::endl;
+  std::cerr << "Using:" << std::endl;
+  std::cerr << "  " << opt["haps"] << std::endl;
+  std::cerr << "  " << opt["sample"] << std::endl;
+  std::cerr << "  " << opt["map"] << std::endl;
+  {  // (printed whether or not the options are given, OptimizeParameters.cpp:49-53; neither is read by the mode)
+    const float mu = opt.count("mutation_rate") ? std::stof(opt["mutation_rate"]) : 0.0f;
+    std::cerr << "with mu = " << mu << " and ";
+    if (!opt.count("coal")) std::cerr << "2Ne = " << (opt.count("effectiveN") ? std::stof(opt["effectiveN"]) : 0.0f) << "." << std::endl;
+    else std::cerr << "coal = " << opt["coal"] << "." << std::endl;
+  }
+  std::cerr << "---------------------------------------------------------" << std::endl << std::endl;
+  std::cerr << "---------------------------------------------------------" << std::endl;
+  std::cerr << "Parsing data.." << std::endl;
+  const float memory = opt.count("memory") ? std::stof(opt["memory"]) : 5.0f;
+  if (rl_stage_make_chunks(opt["haps"].c_str(), opt["sample"].c_str(), opt["map"].c_str(),
+                           opt.count("dist") ? opt["dist"].c_str() : nullptr, out.c_str(),
+                           opt.count("transversion") ? 1 : 0, memory) != 0) {
+    std::cerr << rl_last_error() << std::endl;
+    return 1;
+  }
+  usage_line();
+  int N = 0, L = 0, num_chunks = 0;
+  double memory_size = 0.0;
+  {
+    FILE *fp = fopen((out + "/parameters.bin").c_str(), "rb");
+    const bool ok = fp && fread(&N, 4, 1, fp) == 1 && fread(&L, 4, 1, fp) == 1 && fread(&num_chunks, 4, 1, fp) == 1 &&
+                    fread(&memory_size, 8, 1, fp) == 1;
+    if (fp) fclose(fp);
+    if (!ok) {
+      std::cerr << "Error: cannot read " << out << "/parameters.bin" << std::endl;
+      return 1;
+    }
+  }
+  std::cerr << "---------------------------------------------------------" << std::endl;
+  std::cerr << "Read " << N << " haplotypes with " << L << " SNPs per haplotype." << std::endl;
+  std::cerr << "Expected minimum memory usage: " << memory_size << "Gb." << std::endl;
+  std::cerr << "---------------------------------------------------------" << std::endl << std::endl;
+  std::vector<float> theta = {1e-4, 1e-3, 1e-2, 1e-1};       // :76
+  std::vector<float> rec_factor = {0.001, 0.1, 1, 10, 100};  // :77
+  if (opt.count("input")) {  // line 1: thetas, line 2: factors (:81-112)
+    std::ifstream is(opt["input"]);
+    theta.clear();
+    rec_factor.clear();
+    std::string line;
+    float val;
+    getline(is, line);
+    std::istringstream itheta(line);
+    while (itheta >> val) {
+      if (val >= 1.0 || val <= 0) {
+        std::cerr << "Error: theta value has to be in (0,1)" << std::endl;
+        return 1;
+      }
+      theta.push_back(val);
+    }
+    line.clear();
+    getline(is, line);
+    std::istringstream irec(line);
+    while (irec >> val) {
+      if (val <= 0) {
+        std::cerr << "Error: rho value has to be positive" << std::endl;
+        return 1;
+      }
+      rec_factor.push_back(val);
+    }
+  }
+  std::vector<int> counts(theta.size() * rec_factor.size(), 0);
+  for (int c = 0; c < num_chunks; c++) {
+    std::cerr << "---------------------------------------------------------" << std::endl;
+    std::cerr << "Starting chunk " << c << " of " << num_chunks - 1 << "." << std::endl;
+    std::cerr << "---------------------------------------------------------" << std::endl << std::endl;
+    if (counts.empty()) continue;
+    if (rl_stage_optimize_parameters(out.c_str(), c, theta.data(), (int)theta.size(), rec_factor.data(),
+                                     (int)rec_factor.size(), &so, counts.data()) != 0) {
+      std::cerr << "Error: " << rl_last_error() << std::endl;
+      return 1;
+    }
+  }
+  // Clean (pipeline/Clean.cpp:31-120) for what this mode leaves: the chunk files (and the bit-packed panel of this
+  // build's MakeChunks), the parameter files, the directories if a stage made them
+  std::cerr << "---------------------------------------------------------" << std::endl;
+  std::cerr << "Cleaning directory..." << std::endl;
+  for (int c = 0; c < num_chunks; c++) {
+    const std::string cs = std::to_string(c), base = out + "/chunk_" + cs;
+    for (const char *ext : {".hap", ".r", ".rpos", ".state", ".dist", ".bp", ".bits"}) std::remove((base + ext).c_str());
+    std::remove((out + "/parameters_c" + cs + ".bin").c_str());
+    (void)rmdir((base + "/paint").c_str());
+    (void)rmdir(base.c_str());
+  }
+  std::remove((out + "/parameters.bin").c_str());
+  std::remove((out + "/props.bin").c_str());
+  (void)rmdir(out.c_str());
+  usage_line();
+  std::ofstream os(out + ".opt");  // :183-189 (operator<< of float / int)
+  for (size_t i = 0; i < theta.size(); i++)
+    for (size_t j = 0; j < rec_factor.size(); j++)
+      os << theta[i] << " " << rec_factor[j] << " " << counts[i * rec_factor.size() + j] << std::endl;
+  os.close();
+  usage_line();
+  return 0;
 }
 
 int main(int argc, char **argv) {
@@ -45,6 +173,7 @@ int main(int argc, char **argv) {
       {"output", true}, {"painting", true}, {"seed", true}, {"fb", true}, {"sample_ages", true},
       {"no_consistency", false}, {"device", true}, {"sum_mode", true}, {"help", false},
       {"find_equivalent_branches", false},  // (PaintBuildTopology / BuildTopology of a whole chunk: the next stage fused in)
+      {"input", true},  // (OptimizeParameters: the grid, Relate.cpp:43)
       // accepted and ignored by these two modes in the reference as well
       {"haps", true}, {"sample", true}, {"map", true}, {"mutation_rate", true}, {"effectiveN", true},
       {"memory", true}, {"dist", true}, {"annot", true}, {"coal", true}, {"transversion", false}};
@@ -55,6 +184,7 @@ int main(int argc, char **argv) {
     else if (s == "-m") name = "mutation_rate";
     else if (s == "-N") name = "effectiveN";
     else if (s == "-h") name = "help";
+    else if (s == "-i") name = "input";
     else if (s.rfind("--", 0) == 0) name = s.substr(2);
     else {
       std::cerr << "Unexpected argument " << s << std::endl;
@@ -75,11 +205,21 @@ int main(int argc, char **argv) {
       opt[name] = "1";
     }
   }
-  if (opt.count("help") || !opt.count("mode")) {
-    std::cerr << "Usage: Relate --mode Paint|BuildTopology --chunk_index c -o out [options]" << std::endl;
+  if ((opt.count("help") && !(opt.count("mode") && opt["mode"] == "OptimizeParameters")) || !opt.count("mode")) {
+    std::cerr << "Usage: Relate --mode " << kModes << " [--chunk_index c] -o out [options]" << std::endl;
     return opt.count("help") ? 0 : 1;
   }
   const std::string mode = opt["mode"];
+  if (mode == "OptimizeParameters" && opt.count("output") && opt["output"].find('/') != std::string::npos) {
+    std::cerr << "Output needs to be in working directory." << std::endl;  // Relate.cpp:50-58
+    return 1;
+  }
+  if (mode == "OptimizeParameters" && (!opt.count("haps") || !opt.count("sample") || !opt.count("map") ||
+                                       !opt.count("output") || opt.count("help"))) {
+    rl_stage_opts none;
+    rl_stage_opts_init(&none);
+    return optimize_parameters(opt, none);  // (the reference's two lines and the help, exit status 0)
+  }
   if (!opt.count("output")) {
     std::cerr << "Not enough arguments supplied." << std::endl;
     std::cerr << "Needed: output." << std::endl;
@@ -109,7 +249,7 @@ int main(int argc, char **argv) {
     usage_line();
     return 0;
   }
-  if (!opt.count("chunk_index")) {
+  if (!opt.count("chunk_index") && mode != "OptimizeParameters") {
     std::cerr << "Not enough arguments supplied." << std::endl;
     std::cerr << "Needed: chunk_index, output." << std::endl;
     return 1;
@@ -162,7 +302,9 @@ int main(int argc, char **argv) {
   const std::string ages = opt.count("sample_ages") ? opt["sample_ages"] : std::string();
   so.sample_ages_path = ages.empty() ? nullptr : ages.c_str();  // BuildTopology.cpp:93-108
   so.find_equivalent_branches = opt.count("find_equivalent_branches") ? 1 : 0;
-  if (mode == "Paint") {
+  if (mode == "OptimizeParameters") {
+    return optimize_parameters(opt, so);
+  } else if (mode == "Paint") {
     std::cerr << "---------------------------------------------------------" << std::endl;
     std::cerr << "Painting sequences..." << std::endl;
     rc = rl_stage_paint_ex(out.c_str(), chunk, &so);
@@ -183,8 +325,8 @@ int main(int argc, char **argv) {
                                     atoi(opt["last_section"].c_str()), &so);
     if (rc == 1) return 1;  // first_section >= num_windows (BuildTopology.cpp:45)
   } else {
-    std::cerr << "Mode " << mode << " is not part of this build: it replaces --mode MakeChunks, Paint, BuildTopology and FindEquivalentBranches "
-              << "only; run the reference Relate for the other stages." << std::endl;
+    std::cerr << "Mode " << mode << " is not part of this build: it replaces --mode MakeChunks, Paint, BuildTopology, FindEquivalentBranches and "
+              << "OptimizeParameters only; run the reference Relate for the other stages." << std::endl;
     return 1;
   }
   if (rc != 0) {

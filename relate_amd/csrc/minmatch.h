@@ -235,6 +235,9 @@ class DeviceMinMatch {
   float *rowmin_device();
   void rowmin_is_ready();
   int apply_penalty(const char *member, float val);
+  // `--mode OptimizeParameters`: the SNP cancelled in the staged matrix (anc_builder.cpp:869-882) and, of the rows as
+  // they then are, the row minima of the build -- one pass (optimize_kernels.hip cancel_rowmin_kernel)
+  int apply_cancel(const char *member, float log_ratio);
   int apply_prior(const HostTree &previous, float val);
   int build_resident(MinMatch &tb, bool with_prior, HostTree &tree);
 

@@ -2823,6 +2823,31 @@ int DeviceMinMatch::apply_penalty(const char *member, float val) {
   return 0;
 }
 
+hipError_t launch_cancel_rowmin(float *D, int N, const unsigned char *member, float log_ratio, float *rowmin,
+                                hipStream_t stream);  // (optimize_kernels.hip)
+
+int DeviceMinMatch::apply_cancel(const char *member, float log_ratio) {
+  Impl &m = *impl;
+  const int N = m.N;
+  if (!m.staging) return -1;
+  RL_HIP(hipSetDevice(m.device));
+  if (!m.stream) RL_HIP(make_stream(&m.stream, false, true));
+  if (m.d_member.alloc((size_t)N)) return -1;
+  const size_t tab_ints = (size_t)6 * (2 * N - 1) + N;  // (the block apply_penalty keeps its flags in)
+  if (!m.h_tab && !(m.h_tab = static_cast<int *>(pinned_cache_alloc(tab_ints * 4 + (size_t)N, &m.h_tab_bytes)))) {
+    set_error("tree builder: no pinned host memory for the carrier flags");
+    return -1;
+  }
+  char *flags = reinterpret_cast<char *>(m.h_tab + tab_ints);
+  for (int i = 0; i < N; i++) flags[i] = member[i] ? 1 : 0;
+  if (m.d_f.alloc((size_t)8 * N * 4)) return -1;  // (reserve()'s: the row minima live at 6N and 7N)
+  RL_HIP(hipMemcpyAsync(m.d_member.p, flags, (size_t)N, hipMemcpyHostToDevice, m.stream));
+  RL_HIP(launch_cancel_rowmin(m.staging->D.as<float>(), N, m.d_member.as<unsigned char>(), log_ratio,
+                              m.d_f.as<float>() + 6 * (size_t)N, m.stream));
+  m.rowmin_d_ready = true;
+  return 0;
+}
+
 int DeviceMinMatch::apply_prior(const HostTree &t, float val) {
   Impl &m = *impl;
   const int N = m.N, T = 2 * N - 1;

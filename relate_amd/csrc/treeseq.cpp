@@ -23,6 +23,7 @@
 #include <cstring>
 #include <iomanip>
 #include <iostream>
+#include <limits>
 #include <memory>
 #include <mutex>
 #include <sstream>
@@ -798,15 +799,106 @@ static std::vector<double> read_sample_ages(const char *fn, int N) {
   return ages;
 }
 
+// ---- `--mode OptimizeParameters`: one section (AncesTreeBuilder::OptimizeParameters, anc_builder.cpp:821-973) ------
+// A tree at EVERY SNP start..end of the section, each from the distance matrix with the SNP "cancelled" (:869-882,
+// :926-939) and without a prior (MinMatch::QuickBuild, tree_builder.cpp:1061-1303), by ONE MinMatch whose generator and
+// carried state run on from tree to tree (:848); the SNP is then mapped onto its own tree (MapMutation without random
+// flipping, :1064-1139) and counted when it comes back flipped or not mapping (> 1, :886, :962).  The tree is thrown
+// away.  The cursors advance at every SNP after the first, the section's last included (:898-907 -- BuildTopology
+// stops one short, :487-495), and the last SNP has its carriers like any other.  The first SNP's matrix is computed
+// twice by the reference (:837, :867): the same matrix, once here.  The `seed` argument seeds a generator the path
+// never draws from (:831), so there is none.
+struct OptRun {
+  float log_ratio = 0.0f;            // (float) log(theta / ntheta), :852
+  std::atomic<long long> count{0};   // SNPs of the sections that did not map
+  std::atomic<long long> trees{0}, gpu_trees{0}, host_trees{0};  // built in all, by the device's workers, by the host
+};
+
+// the cancellation on the host (the fallback's matrix; the device's is optimize_kernels.hip cancel_rowmin_kernel)
+static void cancel_snp_host(float *d, int N, const char *member, float log_ratio) {
+  for (int i = 0; i < N; i++) {
+    if (!member[i]) continue;
+    float *row = d + (size_t)i * N;
+    float mn = std::numeric_limits<float>::infinity();
+    for (int j = 0; j < N; j++) {
+      if (!member[j]) row[j] += log_ratio;
+      if (mn > row[j]) mn = row[j];
+    }
+    for (int j = 0; j < N; j++) row[j] -= mn;
+  }
+}
+
+static int optimize_section(rl_treeseq *ts, int start, int end, rl_window *win, OptRun &run) {
+  const int N = ts->N;
+  MinMatch tb(N, ts->theta);
+  DeviceMinMatch *dev = nullptr;
+  if (ts->build_device >= 0 && N <= 10240) {
+    if (!ts->dev_builder) ts->dev_builder = new DeviceMinMatch(N, ts->build_device);
+    dev = ts->dev_builder;
+  }
+  const bool resident = dev && ts->matrix_dev;
+  MatrixBuf d;  // (the host's matrix: only when a tree is the host's)
+  SnpInfo si;
+  HostTree tree;
+  int rc, not_mapping = 0;
+  long long on_gpu = 0, on_host = 0;
+  for (int snp = start; snp <= end; snp++) {
+    ts->num_carriers = 0;
+    for (int i = 0; i < N; i++) {
+      ts->member[i] = ts->derived(snp, i) ? 1 : 0;
+      ts->num_carriers += ts->member[i];
+    }
+    if (snp > start && (rc = rl_window_advance(win, snp))) return rc;
+    bool built = false;
+    if (resident) {  // matrix, cancellation + row minima and the build on the device: no matrix crosses PCIe
+      float *dd = dev->device_matrix();
+      if (!dd) return RL_ENOMEM;
+      if ((rc = ts->matrix_dev(win, snp, dd))) return rc;
+      int st = dev->apply_cancel(ts->member.data(), run.log_ratio);
+      st = st ? st : dev->build_resident(tb, false, tree);
+      if (st < 0) {
+        set_error("tree builder on the device failed at SNP %d", snp);
+        return RL_EHIP;
+      }
+      built = st == 0;  // (> 0: this tree is the host's -- the symmetric fallback; tb untouched, the matrix again)
+      if (built) on_gpu++;
+    }
+    if (!built) {
+      if (d.empty()) d.resize((size_t)N * N);
+      if ((rc = rl_window_matrix(win, snp, d.data(), nullptr))) return rc;
+      cancel_snp_host(d.data(), N, ts->member.data(), run.log_ratio);
+      int st = 1;
+      if (dev && !resident) {
+        st = dev->build(tb, d.data(), nullptr, tree);
+        if (st < 0) return RL_EHIP;
+        if (st == 0) on_gpu++;
+      }
+      if (st > 0) {
+        on_host++;
+        tb.quick_build(d.data(), nullptr, tree);
+      }
+    }
+    float misfit = 0.0f;
+    if (map_mutation(*ts, tree, si, misfit, true) > 1) not_mapping++;
+  }
+  run.count += not_mapping;
+  run.trees += end - start + 1;
+  run.gpu_trees += on_gpu;
+  run.host_trees += on_host;
+  ts->gpu_trees += on_gpu;
+  ts->host_trees += on_host;
+  return RL_OK;
+}
+
 static int build_sections(rl_ctx *ctx, const char *out_dir, int chunk_index, int first_section, int last_section,
-                          const rl_stage_opts &o, bool from_files) {
+                          const rl_stage_opts &o, bool from_files, OptRun *opt = nullptr) {
   int rc = RL_OK;
   const int flags = o.flags, fb = o.fb, sum_mode = o.sum_mode, device = o.device;
   const char *sample_ages_file = (o.sample_ages_path && *o.sample_ages_path) ? o.sample_ages_path : nullptr;
   const auto entry_t0 = std::chrono::steady_clock::now();
   const int W = ctx->W, L = ctx->L;
   if (first_section >= W) {  // BuildTopology.cpp:45
-    rl_destroy(ctx);
+    if (!opt) rl_destroy(ctx);
     return 1;
   }
   last_section = std::min(W - 1, last_section);
@@ -837,26 +929,28 @@ static int build_sections(rl_ctx *ctx, const char *out_dir, int chunk_index, int
     return RL_OK;
   };
   if ((rc = read_ints(od + "/chunk_" + c + ".bp", bp)) || (rc = read_ints(od + "/chunk_" + c + ".state", state))) {
-    rl_destroy(ctx);
+    if (!opt) rl_destroy(ctx);
     return rc;
   }
   // rl_stage_opts.find_equivalent_branches: checked before any device or builder set-up
   const bool want_feb = knob("RELATE_AMD_FUSED_FEB", o.find_equivalent_branches, true, 0) != 0;
   if (want_feb && (first_section != 0 || last_section != W - 1 || W < 2)) {
     set_error("find_equivalent_branches needs a call that covers all %d sections of the chunk (and at least two)", W);
-    rl_destroy(ctx);
+    if (!opt) rl_destroy(ctx);
     return RL_EINVAL;
   }
-  std::cerr << "---------------------------------------------------------" << std::endl;
-  std::cerr << "Estimating topologies of AncesTrees in sections " << first_section << "-" << last_section << "..."
-            << std::endl;
+  if (!opt) {
+    std::cerr << "---------------------------------------------------------" << std::endl;
+    std::cerr << "Estimating topologies of AncesTrees in sections " << first_section << "-" << last_section << "..."
+              << std::endl;
+  }
   // How many sections are open at once is bounded by host threads and by HBM: a window's posterior rows (sum_n D_n
   // rows of S*64*waves floats, 20 GB at N = 5000) stay resident while its trees are built.  When the sections the
   // host could work on do not fit, every window keeps a part of its rows and repaints as its builder moves on
   // (rl_window_open_bounded; RELATE_AMD_WINDOW_ROWS sets the rows per window by hand).  Every open is admitted
   // against the HBM that is free at that moment (window_bytes below); the estimate here sizes the thread pools.
   if ((!ctx->plan.valid && build_plan(ctx)) || upload_plan(ctx)) {  // (before the section threads open their windows)
-    rl_destroy(ctx);
+    if (!opt) rl_destroy(ctx);
     return RL_EINVAL;
   }
   const double row_bytes = 4.0 * ctx->S * 64 * ctx->waves;
@@ -886,7 +980,7 @@ static int build_sections(rl_ctx *ctx, const char *out_dir, int chunk_index, int
   const double fixed_bytes = 4.0 * max_rows + 48e6 + (from_files || ctx->h_alpha ? 8.0 * ctx->N * ctx->nloc : 0.0) +
                              (gpu_build && ctx->nloc == ctx->N ? 0.0 : 4.0 * ctx->N * ctx->nloc);
   if (gpu_build && device_builder_reserve_shared(device, ctx->N)) {  // the pools now: the admission sees what is left
-    rl_destroy(ctx);
+    if (!opt) rl_destroy(ctx);
     return RL_ENOMEM;
   }
   // (a bounded window also keeps one state of RePaint's backward pass per target, doubles: window.cpp)
@@ -903,7 +997,7 @@ static int build_sections(rl_ctx *ctx, const char *out_dir, int chunk_index, int
   {
     const size_t strips = repaint_scratch_bytes((int64_t)max_rows, ctx->nloc, ctx->S, ctx->waves);
     if (ctx->d_k2_scratch.alloc(strips)) {
-      rl_destroy(ctx);
+      if (!opt) rl_destroy(ctx);
       return RL_ENOMEM;
     }
     size_t free_b = 0, total_b = 0;
@@ -1134,7 +1228,8 @@ static int build_sections(rl_ctx *ctx, const char *out_dir, int chunk_index, int
       }
       int r = win ? RL_OK : (first_error.load() ? first_error.load() : open_rc);
       const double t_open = std::chrono::duration<double>(std::chrono::steady_clock::now() - stage_t0).count();
-      if (!r) r = rl_treeseq_build(ts, start, end, win_matrix, win_advance, win, flags, fb);
+      if (!r && opt) r = optimize_section(ts, start, end, win, *opt);  // (--mode OptimizeParameters: counts, no files)
+      else if (!r) r = rl_treeseq_build(ts, start, end, win_matrix, win_advance, win, flags, fb);
       if (getenv("RELATE_AMD_TIMING"))  // (when the sections start and end: the stage's ramp and tail)
         fprintf(stderr, "[section %d] turn %d, %d SNPs: window open %.1f s after the stage began, trees built at %.1f s\n",
                 section, turn, end - start + 1, t_open,
@@ -1144,7 +1239,7 @@ static int build_sections(rl_ctx *ctx, const char *out_dir, int chunk_index, int
         rl_window_close(win);
         open_sections--;
       }
-      if (!r) {
+      if (!r && !opt) {
         const std::string b = od + "/chunk_" + c + "/" + base + "_" + std::to_string(section);
         // (fused FindEquivalentBranches: the .anc is written at the end, once, with what that stage carries across)
         r = rl_treeseq_write(ts, feb ? nullptr : (b + ".anc").c_str(), (b + ".mut").c_str());
@@ -1154,8 +1249,10 @@ static int build_sections(rl_ctx *ctx, const char *out_dir, int chunk_index, int
         fail(r);
         break;
       }
-      std::cerr << "[" << section << "/" << last_section << "]\r";
-      std::cerr.flush();
+      if (!opt) {
+        std::cerr << "[" << section << "/" << last_section << "]\r";
+        std::cerr.flush();
+      }
     }
     rl_treeseq_destroy(ts);
     if (pinned) sched_setaffinity(0, sizeof(before), &before);
@@ -1183,11 +1280,11 @@ static int build_sections(rl_ctx *ctx, const char *out_dir, int chunk_index, int
             ctx->repaint_launches.load(), 1e-6 * (double)ctx->repaint_us.load(), gpu_build ? "GPU" : "host", asked_workers,
             std::chrono::duration<double>(std::chrono::steady_clock::now() - stage_t0).count());
   const auto destroy_t0 = std::chrono::steady_clock::now();
-  rl_destroy(ctx);
+  if (!opt) rl_destroy(ctx);
   if (getenv("RELATE_AMD_TIMING"))
     fprintf(stderr, "[stage] context released in %.3f s\n",
             std::chrono::duration<double>(std::chrono::steady_clock::now() - destroy_t0).count());
-  if (!rc) {
+  if (!rc && !opt) {
     rusage usage;
     getrusage(RUSAGE_SELF, &usage);
     std::cerr << "CPU Time spent: " << usage.ru_utime.tv_sec << "." << std::setfill('0') << std::setw(6)
@@ -1317,6 +1414,158 @@ int rl_stage_paint_build_topology_ex(const char *out_dir, int chunk_index, int f
     return rc;
   }
   return build_sections(ctx, out_dir, chunk_index, first_section, last_section, o, false);
+}
+
+// ---- `--mode OptimizeParameters` (pipeline/OptimizeParameters.cpp:22-206) ------------------------------------------
+// (float arguments as the reference's grid holds them, :76-77; data.theta / data.r are doubles made from them, :151-155)
+static float opt_log_ratio(float theta) {
+  const double th = theta, nth = 1.0 - th;  // :151-152
+  return (float)std::log(th / nth);          // anc_builder.cpp:852
+}
+
+int rl_optimize_section(rl_ctx *ctx, int section, float theta, float rec_factor, int *count) {
+  if (!ctx || !count || !ctx->have_chunk || section < 0 || section >= ctx->W) {
+    set_error("rl_optimize_section: bad arguments");
+    return RL_EINVAL;
+  }
+  if (!ctx->painted) {
+    set_error("rl_optimize_section: rl_paint has not run (the grid point re-paints from the stepping stones in HBM)");
+    return RL_ESTATE;
+  }
+  if (!(theta > 0.0f && theta < 1.0f) || !(rec_factor > 0.0f)) {
+    set_error("rl_optimize_section: theta has to be in (0,1) and the recombination factor positive");
+    return RL_EINVAL;
+  }
+  int rc = RL_OK;
+  if (ctx->theta != (double)theta || ctx->rho != (double)rec_factor) rc = replan_painting(ctx, theta, rec_factor);
+  if (rc) return rc;
+  const int L = ctx->L, start = ctx->wb[section];
+  const int end = std::min(L - 1, (section < ctx->W - 1 ? ctx->wb[section + 1] : L) - 1);
+  std::vector<int> bp(L, 0), state(L, 1);  // (neither is read by this mode)
+  rl_treeseq *ts = treeseq_borrowing(ctx->N, L, ctx->bits.data(), ctx->row_words, ctx->rpos.data(), bp.data(),
+                                     state.data(), ctx->theta);
+  if (knob("RELATE_AMD_GPU_BUILD", 1, true, 1) != 0 && ctx->nloc == ctx->N) {
+    rl_treeseq_set_build_device(ts, ctx->device);
+    rl_treeseq_set_device_matrix(ts, win_matrix_dev);
+  }
+  rl_window *win = rl_window_open(ctx, section, nullptr, start, ctx->paint_mode >= 0 ? ctx->paint_mode : RL_SUM_EXACT, nullptr);
+  OptRun run;
+  run.log_ratio = opt_log_ratio(theta);
+  rc = win ? optimize_section(ts, start, end, win, run) : RL_EHIP;
+  if (win) rl_window_close(win);
+  rl_treeseq_destroy(ts);
+  if (!rc) *count = (int)run.count.load();
+  if (!rc && getenv("RELATE_AMD_TIMING"))
+    fprintf(stderr, "[optimize] section %d: %lld trees (%lld on the GPU, %lld on the host)\n", section, run.trees.load(),
+            run.gpu_trees.load(), run.host_trees.load());
+  return rc;
+}
+
+int rl_stage_optimize_parameters(const char *out_dir, int chunk_index, const float *theta, int n_theta,
+                                 const float *factor, int n_factor, const rl_stage_opts *opts, int *counts) {
+  if (!out_dir || !theta || !factor || !counts || n_theta < 1 || n_factor < 1) {
+    set_error("rl_stage_optimize_parameters: bad arguments");
+    return RL_EINVAL;
+  }
+  for (int i = 0; i < n_theta; i++)
+    if (!(theta[i] > 0.0f && theta[i] < 1.0f)) {
+      set_error("theta value has to be in (0,1)");  // OptimizeParameters.cpp:92-95
+      return RL_EINVAL;
+    }
+  for (int j = 0; j < n_factor; j++)
+    if (!(factor[j] > 0.0f)) {
+      set_error("rho value has to be positive");  // :103-106
+      return RL_EINVAL;
+    }
+  rl_stage_opts o;
+  if (int orc = rl_internal_resolve_opts(opts, &o)) return orc;
+  o.find_equivalent_branches = 0;
+  o.sample_ages_path = nullptr;  // (the mode builds without sample ages: `sample_ages` of a fresh AncesTreeBuilder, :163)
+  rl_ctx *ctx = rl_create(o.device);
+  if (!ctx) return RL_ENODEVICE;
+  const auto t0 = std::chrono::steady_clock::now();
+  int rc = rl_load_chunk(ctx, out_dir, chunk_index);
+  // The stepping stones of EVERY grid point are painted with the chunk's stored recombination distances and the default
+  // theta -- or --painting's, Paint.cpp:38-61 --: Paint(options, c) at OptimizeParameters.cpp:159 reads the chunk files
+  // into a Data of its own (Paint.cpp:35), the grid's data.theta / data.r (:151-157) never reach it.  So the stones are
+  // painted ONCE per chunk and stay in HBM, as in the fused stage; a grid point rebuilds the RePaint plan only.
+  if (!rc && o.use_painting) rc = rl_set_painting(ctx, o.theta, o.rho);
+  if (!rc) rc = rl_paint(ctx, o.sum_mode, nullptr);
+  const auto tpaint1 = std::chrono::steady_clock::now();
+  if (!rc) ctx->stones_disposable = true;  // (no paint files from this context: a window quantises its slice once, in place)
+  long long trees = 0, gpu_trees = 0, host_trees = 0;
+  double t_replan = 0.0;
+  const double t_paint = std::chrono::duration<double>(tpaint1 - t0).count();
+  for (int i = 0; i < n_theta && !rc; i++)
+    for (int j = 0; j < n_factor && !rc; j++) {
+      // the grid point's r is the STORED r times the factor (:146, :155), whatever --painting did to the stones' r
+      // (the reference's Paint prints its banner for every grid point, Paint.cpp:63-64)
+      std::cerr << "---------------------------------------------------------" << std::endl;
+      std::cerr << "Painting sequences..." << std::endl;
+      const auto tp = std::chrono::steady_clock::now();
+      rc = replan_painting(ctx, theta[i], factor[j]);
+      t_replan += std::chrono::duration<double>(std::chrono::steady_clock::now() - tp).count();
+      OptRun run;
+      run.log_ratio = opt_log_ratio(theta[i]);
+      if (!rc) rc = build_sections(ctx, out_dir, chunk_index, 0, ctx->W - 1, o, false, &run);
+      if (!rc) counts[(size_t)i * n_factor + j] += (int)run.count.load();
+      trees += run.trees.load();
+      gpu_trees += run.gpu_trees.load();
+      host_trees += run.host_trees.load();
+    }
+  if (getenv("RELATE_AMD_TIMING")) {
+    const double sec = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    fprintf(stderr, "[optimize] chunk %d: %d grid points, %lld trees (%lld on the GPU, %lld on the host) in %.2f s: %.0f "
+            "trees per second; chunk files + Paint %.2f s, plan per grid point %.3f s\n", chunk_index, n_theta * n_factor,
+            trees, gpu_trees, host_trees, sec, (double)trees / std::max(sec, 1e-9), t_paint, t_replan / (n_theta * n_factor));
+  }
+  rl_destroy(ctx);
+  return rc;
+}
+
+// Test hook (host only): AncesTreeBuilder::MapMutation without random flipping (anc_builder.cpp:1064-1139 with
+// PropagateMutationGlobal, :1237-1341) on a tree given by its parent array.
+int rl_debug_map_mutation(int N, const int *parent, const char *carriers) {
+  if (N < 2 || !parent || !carriers) {
+    set_error("rl_debug_map_mutation: bad arguments");
+    return RL_EINVAL;
+  }
+  const int T = 2 * N - 1;
+  HostTree t;
+  t.reset(N);
+  for (int v = 0; v < T; v++) {
+    const int p = parent[v];
+    if (v == T - 1 ? p != -1 : (p <= v || p < N || p >= T)) {  // (MinMatch's labels: a parent above its children)
+      set_error("rl_debug_map_mutation: node %d has parent %d", v, p);
+      return RL_EINVAL;
+    }
+    t.parent[v] = p;
+    if (p < 0) continue;
+    if (t.child_left[p] < 0) t.child_left[p] = v;
+    else if (t.child_right[p] < 0) t.child_right[p] = v;
+    else {
+      set_error("rl_debug_map_mutation: node %d has more than two children", p);
+      return RL_EINVAL;
+    }
+  }
+  for (int v = N; v < T; v++)
+    if (t.child_right[v] < 0) {
+      set_error("rl_debug_map_mutation: internal node %d has fewer than two children", v);
+      return RL_EINVAL;
+    }
+  std::vector<uint32_t> no_panel((size_t)((N + 31) / 32) * 2, 0u);
+  std::vector<double> rpos(3, 0.0);
+  std::vector<int> zeros(2, 0);
+  rl_treeseq *ts = treeseq_borrowing(N, 2, no_panel.data(), (N + 31) / 32, rpos.data(), zeros.data(), zeros.data(), 0.001);
+  for (int i = 0; i < N; i++) {
+    ts->member[i] = carriers[i] ? 1 : 0;
+    ts->num_carriers += ts->member[i];
+  }
+  SnpInfo si;
+  float misfit = 0.0f;
+  const int r = map_mutation(*ts, t, si, misfit, true);
+  rl_treeseq_destroy(ts);
+  return r;
 }
 
 int rl_stage_paint_build_topology(const char *out_dir, int chunk_index, int first_section, int last_section,
