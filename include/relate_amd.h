@@ -105,6 +105,21 @@ int rl_set_painting(rl_ctx *ctx, double theta, double rho);
 int rl_set_target_range(rl_ctx *ctx, int k_begin, int k_end);
 int rl_target_range(const rl_ctx *ctx, int *k_begin, int *k_end);
 
+/* Window range of ONE chunk: rl_paint keeps the stepping stones of windows w_first .. w_last only (default: all W).
+ * The reference deals a chunk out by section range, one BuildTopology process per range
+ * (scripts/RelateParallel/RelateParallel.sh:231-257), and section w reads window w alone: the alpha stone at its begin
+ * boundary and the beta stone at its end boundary (DistanceMeasure::GetTopologyWithRepaint, src/anc_builder.cpp:49-78;
+ * written at src/fast_painting.cpp:354-374 and :559-578).  A range other than the default one also ends the passes
+ * where their last stone is written: the forward pass of target k at the begin boundary of w_last, the backward pass at
+ * the end boundary of w_first.  The stone buffers hold w_last - w_first + 1 windows; every entry point that takes a
+ * window (rl_get_stones, rl_paint_record, rl_write_paint_file, rl_window_open* without a paint file) refuses one
+ * outside the painted range with RL_ESTATE and a message naming the range, and rl_write_paint_files, which writes
+ * every window, refuses any range but the default.  A bad range is RL_EINVAL before the device is touched.  Call after
+ * rl_set_chunk / rl_load_chunk; after rl_paint it marks the context unpainted, as rl_set_target_range does, but the
+ * plan and its uploads (rl_prepare) stay: they do not depend on the range. */
+int rl_set_window_range(rl_ctx *ctx, int w_first, int w_last);
+int rl_window_range(const rl_ctx *ctx, int *w_first, int *w_last);
+
 int rl_chunk_dims(const rl_ctx *ctx, int *N, int *L, int *W);
 /* sum_k D_k: visited (target, site) pairs of the chunk; 2*N*this is the
  * number of directional haplotype-pair.SNP updates of one Paint. */
@@ -131,6 +146,12 @@ int rl_set_paint_split(rl_ctx *ctx, int split);
 /* HIP-event durations of the last rl_paint's two launches (forward kernel,
  * backward kernel), in milliseconds; both 0 unless rl_set_paint_split(ctx, 1). */
 int rl_paint_times(const rl_ctx *ctx, float *fwd_ms, float *bwd_ms);
+/* What the last rl_paint was launched with: fwd_steps / bwd_steps, the steps of the forward loop
+ * (src/fast_painting.cpp:262-376) and of the backward loop (:457-580) summed over the context's targets -- sum_k D_k - 1
+ * each for the default window range, sum_k stone_ia[k][w_last] and sum_k D_k - 1 - stone_ie[k][w_first] under
+ * rl_set_window_range --, and stone_bytes, the stone storage it asked for (2 * windows * targets * N floats).  Any
+ * pointer may be NULL. */
+int rl_paint_account(const rl_ctx *ctx, long long *fwd_steps, long long *bwd_steps, long long *stone_bytes);
 /* Register tile of the loaded chunk: S doubles per lane, `waves` wavefronts
  * per target (relate_amd/csrc/launch.h) -- which kernel instantiation runs. */
 int rl_register_tile(const rl_ctx *ctx, int *S, int *waves);
@@ -369,6 +390,9 @@ typedef struct rl_stage_opts {
                                still build, every .anc is written ONCE, as that stage would leave it (same bytes as
                                BuildTopology followed by rl_stage_find_equivalent_branches).  Only for a call that covers
                                all sections of the chunk; host memory: ~0.3 MB per tree at N = 5000                  */
+  int paint_windows;        /* fused stage (rl_stage_paint_build_topology_ex): 1 / -1 (default): Paint keeps the windows of
+                               [first_section, min(last_section, W-1)] only (rl_set_window_range), what one process of
+                               scripts/RelateParallel/RelateParallel.sh:231-257 reads; 0: every window, as before            */
 } rl_stage_opts;
 void rl_stage_opts_init(rl_stage_opts *opts);
 int rl_stage_paint_ex(const char *out_dir, int chunk_index, const rl_stage_opts *opts);

@@ -155,6 +155,21 @@ class Context:
         _check(lib().rl_target_range(C.c_void_p(self._h), C.byref(a), C.byref(b)))
         return a.value, b.value
 
+    def set_window_range(self, w_first, w_last):
+        """paint() keeps the stepping stones of windows w_first .. w_last only (rl_set_window_range)"""
+        _check(lib().rl_set_window_range(C.c_void_p(self._h), int(w_first), int(w_last)))
+
+    def window_range(self):
+        a, b = C.c_int(), C.c_int()
+        _check(lib().rl_window_range(C.c_void_p(self._h), C.byref(a), C.byref(b)))
+        return a.value, b.value
+
+    def paint_account(self):
+        """-> (forward steps, backward steps, stone bytes) of the last paint() (rl_paint_account)"""
+        f, b, n = C.c_longlong(0), C.c_longlong(0), C.c_longlong(0)
+        _check(lib().rl_paint_account(C.c_void_p(self._h), C.byref(f), C.byref(b), C.byref(n)))
+        return f.value, b.value, n.value
+
     def total_sites(self):
         v = lib().rl_total_sites(C.c_void_p(self._h))
         if v < 0:
@@ -478,7 +493,7 @@ class StageOpts(C.Structure):
                 ("sample_ages_path", C.c_char_p), ("gpu_build", C.c_int), ("window_rows", C.c_longlong),
                 ("window_parts", C.c_int), ("section_threads", C.c_int), ("workers", C.c_int),
                 ("repaint_lanes", C.c_int), ("park_stones", C.c_int), ("pin_threads", C.c_int),
-                ("find_equivalent_branches", C.c_int)]
+                ("find_equivalent_branches", C.c_int), ("paint_windows", C.c_int)]
 
 
 def stage_opts(**kw):

@@ -139,6 +139,10 @@ struct rl_ctx {
   hipEvent_t ev0 = nullptr, ev1 = nullptr, ev2 = nullptr;
   int N = 0, L = 0, W = 0;
   int k0 = 0, nloc = 0;  // targets of this context (rl_set_target_range), default all
+  // windows whose stepping stones rl_paint keeps (rl_set_window_range), default all: the stone buffers below hold
+  // w_last - w_first + 1 windows, window w at row w - w_first (rl::stone_row)
+  int w_first = 0, w_last = -1;
+  long long acc_fwd = 0, acc_bwd = 0, acc_bytes = 0;  // rl_paint_account: the last rl_paint's steps and stone bytes
   rl::Layout lay{};  // all N donors in 64*waves balanced runs
   int S = 0;         // register tile (doubles per lane) = words per row of the lane-mask panel
   int waves = 1;     // wavefronts per target: 2 for N > 5120 (launch.h target_waves)
@@ -183,6 +187,16 @@ struct rl_ctx {
 };
 
 namespace rl {
+// row of window w in the context's stone buffers, or -1 with an error that names the painted range: a window outside
+// it was never painted, and its neighbour's row is not an answer
+inline long long stone_row(const rl_ctx *ctx, int w, const char *who) {
+  if (w < ctx->w_first || w > ctx->w_last) {
+    set_error("%s: window %d is outside the painted window range [%d, %d] (rl_set_window_range)", who, w, ctx->w_first,
+              ctx->w_last);
+    return -1;
+  }
+  return w - ctx->w_first;
+}
 int build_plan(rl_ctx *ctx);
 int upload_plan(rl_ctx *ctx);
 // theta / rho of RePaint's plan changed under the painted stones (context.cpp; --mode OptimizeParameters)

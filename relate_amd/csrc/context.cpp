@@ -338,7 +338,12 @@ int build_plan(rl_ctx *ctx) {
     pl.binit[k] = B;
   });
 
-  // 4. launch order: longest target first
+  // 4. launch order: longest target first -- by D_k, under a window range (rl_set_window_range) too.  The steps a
+  // workgroup then runs are ia[k][w_last] forward and D_k - 1 - ie[k][w_first] backward: the sites of target k before
+  // and behind a boundary of the chunk, a share of D_k that is nearly the same for every target (the derived sites of a
+  // haplotype spread over the chunk like everybody's), so the order by D_k is the order by steps up to neighbours
+  // swapping.  An order of its own per range and direction would make the plan depend on the range, which is what lets
+  // a context go from range to range without a new rl_prepare.
   pl.order.resize(ctx->nloc);
   std::iota(pl.order.begin(), pl.order.end(), k0);
   std::stable_sort(pl.order.begin(), pl.order.end(), [&](int a, int b) {
@@ -628,7 +633,7 @@ void rl_destroy(rl_ctx *ctx) {
 int rl_park_stones(rl_ctx *ctx) {
   if (!ctx || !ctx->painted || ctx->h_alpha || !ctx->d_alpha.p) return RL_OK;
   (void)hipSetDevice(ctx->device);
-  const size_t bytes = (size_t)(ctx->wb.size() - 1) * ctx->nloc * ctx->N * sizeof(float);
+  const size_t bytes = (size_t)(ctx->w_last - ctx->w_first + 1) * ctx->nloc * ctx->N * sizeof(float);  // the painted range
   float *a = nullptr, *b = nullptr;
   if (hipHostMalloc(reinterpret_cast<void **>(&a), bytes, hipHostMallocDefault) != hipSuccess ||
       hipHostMalloc(reinterpret_cast<void **>(&b), bytes, hipHostMallocDefault) != hipSuccess) {
@@ -655,9 +660,11 @@ int rl_park_stones(rl_ctx *ctx) {
 // #5 with all targets on one GPU: 2 x 144 GB): then they are painted straight into pinned host memory, the kernel's
 // stores crossing PCIe (seconds, once per chunk), and every window of the stage copies its slice in when it opens,
 // as it does for stones parked by rl_park_stones.  (The stores are the only traffic: nothing of the stones is read
-// back by the painting.)
+// back by the painting.)  Only the windows of the context's range (rl_set_window_range) get rows, here and there: one
+// section of config #5 is 2 x 0.4 GB and stays in HBM.
 static int alloc_stones(rl_ctx *ctx) {
-  const size_t bytes = (size_t)ctx->W * ctx->nloc * ctx->N * sizeof(float);
+  const size_t bytes = (size_t)(ctx->w_last - ctx->w_first + 1) * ctx->nloc * ctx->N * sizeof(float);
+  ctx->acc_bytes = 2 * (long long)bytes;
   if (ctx->h_alpha) {  // (stones of an earlier pass parked on the host)
     (void)hipHostFree(ctx->h_alpha);
     (void)hipHostFree(ctx->h_beta);
@@ -708,6 +715,7 @@ static int set_common(rl_ctx *ctx, int N, int L, const double *r, const double *
   }
   ctx->N = N; ctx->L = L; ctx->W = W; ctx->lay = lay; ctx->S = S; ctx->waves = waves;
   ctx->k0 = 0; ctx->nloc = N;  // all targets until rl_set_target_range
+  ctx->w_first = 0; ctx->w_last = W - 1;  // all windows until rl_set_window_range
   ctx->r.assign(r, r + L);
   ctx->rpos.assign(rpos, rpos + L + 1);
   ctx->wb.assign(wb, wb + W + 1);
@@ -878,6 +886,43 @@ int rl_target_range(const rl_ctx *ctx, int *k_begin, int *k_end) {
   return RL_OK;
 }
 
+int rl_set_window_range(rl_ctx *ctx, int w_first, int w_last) {
+  if (!ctx || !ctx->have_chunk) {
+    set_error("rl_set_window_range: no chunk loaded");
+    return RL_ESTATE;
+  }
+  if (w_first < 0 || w_last >= ctx->W || w_first > w_last) {
+    set_error("rl_set_window_range: [%d, %d] is not a range of the chunk's %d windows", w_first, w_last, ctx->W);
+    return RL_EINVAL;
+  }
+  ctx->w_first = w_first;
+  ctx->w_last = w_last;
+  ctx->painted = false;  // (the plan stays: it does not depend on the range)
+  ctx->stone_quantised.clear();
+  return RL_OK;
+}
+
+int rl_window_range(const rl_ctx *ctx, int *w_first, int *w_last) {
+  if (!ctx || !ctx->have_chunk) {
+    set_error("no chunk loaded");
+    return RL_ESTATE;
+  }
+  if (w_first) *w_first = ctx->w_first;
+  if (w_last) *w_last = ctx->w_last;
+  return RL_OK;
+}
+
+int rl_paint_account(const rl_ctx *ctx, long long *fwd_steps, long long *bwd_steps, long long *stone_bytes) {
+  if (!ctx || !ctx->painted) {
+    set_error("rl_paint_account: call rl_paint first");
+    return RL_ESTATE;
+  }
+  if (fwd_steps) *fwd_steps = ctx->acc_fwd;
+  if (bwd_steps) *bwd_steps = ctx->acc_bwd;
+  if (stone_bytes) *stone_bytes = ctx->acc_bytes;
+  return RL_OK;
+}
+
 int rl_chunk_dims(const rl_ctx *ctx, int *N, int *L, int *W) {
   if (!ctx || !ctx->have_chunk) {
     set_error("no chunk loaded");
@@ -903,10 +948,10 @@ int rl_prepare(rl_ctx *ctx) {
   RL_HIP(hipSetDevice(ctx->device));
   int rc = upload_plan(ctx);
   if (rc) return rc;
-  const size_t N = ctx->N, W = ctx->W, nloc = ctx->nloc;  // stones: this context's target rows only
+  const size_t nloc = ctx->nloc, Wr = ctx->w_last - ctx->w_first + 1;  // stones: this context's target rows and windows only
   if ((rc = alloc_stones(ctx))) return rc;
-  if ((rc = ctx->d_lsa.alloc(W * nloc * sizeof(float)))) return rc;
-  if ((rc = ctx->d_lsb.alloc(W * nloc * sizeof(float)))) return rc;
+  if ((rc = ctx->d_lsa.alloc(Wr * nloc * sizeof(float)))) return rc;
+  if ((rc = ctx->d_lsb.alloc(Wr * nloc * sizeof(float)))) return rc;
   RL_HIP(hipDeviceSynchronize());
   return RL_OK;
 }
@@ -923,10 +968,10 @@ int rl_paint(rl_ctx *ctx, int sum_mode, float *kernel_ms) {
   RL_HIP(hipSetDevice(ctx->device));
   int rc = upload_plan(ctx);
   if (rc) return rc;
-  const size_t N = ctx->N, W = ctx->W, nloc = ctx->nloc;  // stones: this context's target rows only
+  const size_t nloc = ctx->nloc, Wr = ctx->w_last - ctx->w_first + 1;  // stones: this context's target rows and windows only
   if ((rc = alloc_stones(ctx))) return rc;
-  if ((rc = ctx->d_lsa.alloc(W * nloc * sizeof(float)))) return rc;
-  if ((rc = ctx->d_lsb.alloc(W * nloc * sizeof(float)))) return rc;
+  if ((rc = ctx->d_lsa.alloc(Wr * nloc * sizeof(float)))) return rc;
+  if ((rc = ctx->d_lsb.alloc(Wr * nloc * sizeof(float)))) return rc;
 
   PaintParams p;
   p.lay = ctx->lay;
@@ -936,6 +981,18 @@ int rl_paint(rl_ctx *ctx, int sum_mode, float *kernel_ms) {
   p.k0 = ctx->k0;
   p.nloc = ctx->nloc;
   p.S = ctx->S;
+  p.w_first = ctx->w_first;
+  p.w_last = ctx->w_last;
+  {  // rl_paint_account: the steps the passes below are launched with (paint_device.h forward_steps / backward_last)
+    const Plan &pl = ctx->plan;
+    const bool all = ctx->w_first == 0 && ctx->w_last == ctx->W - 1;
+    ctx->acc_fwd = ctx->acc_bwd = 0;
+    for (int k = ctx->k0; k < ctx->k0 + ctx->nloc; k++) {
+      const long long D = pl.off[k + 1] - pl.off[k];
+      ctx->acc_fwd += all ? D - 1 : pl.ia[(size_t)k * ctx->W + ctx->w_last];
+      ctx->acc_bwd += all ? D - 1 : D - 1 - pl.ie[(size_t)k * ctx->W + ctx->w_first];
+    }
+  }
   p.masks = ctx->d_masks.as<unsigned long long>();
   p.plan_off = ctx->d_off.as<int64_t>();
   p.sites = ctx->d_sites.as<int32_t>();
@@ -1047,21 +1104,24 @@ int rl_get_stones(rl_ctx *ctx, int w, float *alpha, float *beta, float *ls_alpha
     set_error("window %d out of range", w);
     return RL_EINVAL;
   }
+  const long long srow = stone_row(ctx, w, "rl_get_stones");
+  if (srow < 0) return RL_ESTATE;
   RL_HIP(hipSetDevice(ctx->device));
   const size_t N = ctx->N, W = ctx->W, nloc = ctx->nloc, k0 = ctx->k0;  // rows of targets k0 .. k0+nloc-1
+  const size_t wr = (size_t)srow;  // the window's row among the painted ones
   if (ctx->h_alpha) {  // (parked on the host: rl_park_stones)
-    if (alpha) memcpy(alpha, ctx->h_alpha + w * nloc * N, nloc * N * 4);
-    if (beta) memcpy(beta, ctx->h_beta + w * nloc * N, nloc * N * 4);
+    if (alpha) memcpy(alpha, ctx->h_alpha + wr * nloc * N, nloc * N * 4);
+    if (beta) memcpy(beta, ctx->h_beta + wr * nloc * N, nloc * N * 4);
   } else {
     if (alpha)
-      RL_HIP(hipMemcpy(alpha, ctx->d_alpha.as<float>() + w * nloc * N, nloc * N * 4, hipMemcpyDeviceToHost));
+      RL_HIP(hipMemcpy(alpha, ctx->d_alpha.as<float>() + wr * nloc * N, nloc * N * 4, hipMemcpyDeviceToHost));
     if (beta)
-      RL_HIP(hipMemcpy(beta, ctx->d_beta.as<float>() + w * nloc * N, nloc * N * 4, hipMemcpyDeviceToHost));
+      RL_HIP(hipMemcpy(beta, ctx->d_beta.as<float>() + wr * nloc * N, nloc * N * 4, hipMemcpyDeviceToHost));
   }
   if (ls_alpha)
-    RL_HIP(hipMemcpy(ls_alpha, ctx->d_lsa.as<float>() + w * nloc, nloc * 4, hipMemcpyDeviceToHost));
+    RL_HIP(hipMemcpy(ls_alpha, ctx->d_lsa.as<float>() + wr * nloc, nloc * 4, hipMemcpyDeviceToHost));
   if (ls_beta)
-    RL_HIP(hipMemcpy(ls_beta, ctx->d_lsb.as<float>() + w * nloc, nloc * 4, hipMemcpyDeviceToHost));
+    RL_HIP(hipMemcpy(ls_beta, ctx->d_lsb.as<float>() + wr * nloc, nloc * 4, hipMemcpyDeviceToHost));
   for (size_t t = 0; t < nloc; t++) {
     if (bsnp_begin) bsnp_begin[t] = ctx->plan.bb[(k0 + t) * W + w];
     if (bsnp_end) bsnp_end[t] = ctx->plan.be[(k0 + t) * W + w];
@@ -1079,6 +1139,9 @@ int rl_paint_record(rl_ctx *ctx, int w, int k, unsigned char *out, size_t cap, s
     set_error("rl_paint_record: window %d / target %d out of range", w, k);
     return RL_EINVAL;
   }
+  const long long srow = stone_row(ctx, w, "rl_paint_record");
+  if (srow < 0) return RL_ESTATE;
+  const size_t wr = (size_t)srow;  // the window's row among the painted ones
   const size_t maxrec = 8 + 2 * (28 + N * 8);
   *len = maxrec;
   if (!out || cap < maxrec) {  // (the bound, for the caller to size its buffer)
@@ -1091,14 +1154,14 @@ int rl_paint_record(rl_ctx *ctx, int w, int k, unsigned char *out, size_t cap, s
   std::vector<float> a(N), b(N);
   float la, lb;
   if (ctx->h_alpha) {
-    memcpy(a.data(), ctx->h_alpha + (w * nloc + t) * N, N * 4);
-    memcpy(b.data(), ctx->h_beta + (w * nloc + t) * N, N * 4);
+    memcpy(a.data(), ctx->h_alpha + (wr * nloc + t) * N, N * 4);
+    memcpy(b.data(), ctx->h_beta + (wr * nloc + t) * N, N * 4);
   } else {
-    RL_HIP(hipMemcpy(a.data(), ctx->d_alpha.as<float>() + (w * nloc + t) * N, N * 4, hipMemcpyDeviceToHost));
-    RL_HIP(hipMemcpy(b.data(), ctx->d_beta.as<float>() + (w * nloc + t) * N, N * 4, hipMemcpyDeviceToHost));
+    RL_HIP(hipMemcpy(a.data(), ctx->d_alpha.as<float>() + (wr * nloc + t) * N, N * 4, hipMemcpyDeviceToHost));
+    RL_HIP(hipMemcpy(b.data(), ctx->d_beta.as<float>() + (wr * nloc + t) * N, N * 4, hipMemcpyDeviceToHost));
   }
-  RL_HIP(hipMemcpy(&la, ctx->d_lsa.as<float>() + w * nloc + t, 4, hipMemcpyDeviceToHost));
-  RL_HIP(hipMemcpy(&lb, ctx->d_lsb.as<float>() + w * nloc + t, 4, hipMemcpyDeviceToHost));
+  RL_HIP(hipMemcpy(&la, ctx->d_lsa.as<float>() + wr * nloc + t, 4, hipMemcpyDeviceToHost));
+  RL_HIP(hipMemcpy(&lb, ctx->d_lsb.as<float>() + wr * nloc + t, 4, hipMemcpyDeviceToHost));
   const int start = ctx->wb[w], end = ctx->wb[w + 1] - 1;  // fast_painting.cpp:591-594
   unsigned char *q = out;
   memcpy(q, &start, 4); q += 4;
@@ -1116,6 +1179,11 @@ int rl_write_paint_files(rl_ctx *ctx, const char *paint_dir) {
     set_error("rl_write_paint_files: call rl_paint first");
     return RL_ESTATE;
   }
+  if (ctx->w_first != 0 || ctx->w_last != ctx->W - 1) {  // (before the first file: no half-written directory)
+    set_error("rl_write_paint_files: writes every window of the chunk, outside the painted window range [%d, %d] "
+              "(rl_set_window_range) too; rl_write_paint_file writes one", ctx->w_first, ctx->w_last);
+    return RL_ESTATE;
+  }
   return write_paint_files(ctx, paint_dir, -1, nullptr);
 }
 
@@ -1128,6 +1196,7 @@ int rl_write_paint_file(rl_ctx *ctx, int w, const char *path) {
     set_error("window %d out of range", w);
     return RL_EINVAL;
   }
+  if (stone_row(ctx, w, "rl_write_paint_file") < 0) return RL_ESTATE;  // (before the file is created)
   return write_paint_files(ctx, nullptr, w, path);
 }
 

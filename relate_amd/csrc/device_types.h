@@ -31,6 +31,8 @@ struct PaintParams {
   int L, W;
   int k0, nloc;             // this context's targets are k0 .. k0+nloc-1 (rl_set_target_range); stones hold those rows
   int S;                    // words per row of the lane-mask panel (= register tile)
+  int w_first, w_last;      // stones are kept for windows w_first .. w_last only (rl_set_window_range; default 0 .. W-1):
+                            // their rows below are relative to w_first, Wr = w_last - w_first + 1 of them
   const unsigned long long *masks;  // [L+2][S] lane-mask panel (paint_device.h), built by panel_kernels.hip
   const int64_t *plan_off;  // [N+1] offsets of target k's visited sites
   const int32_t *sites;     // visited site | (seq_k derived ? 1<<31 : 0)
@@ -40,8 +42,8 @@ struct PaintParams {
   const int32_t *stone_ie;  // [N][W] visited index of boundarySNP_end[w]
   const double *binit;      // [N] beta_sum at the last SNP (serial, host)
   const int32_t *order;     // [nloc] launch order -> target (longest first)
-  float *alpha, *beta;      // [W][nloc][N] stepping stones, donor order
-  float *ls_alpha, *ls_beta;  // [W][nloc]
+  float *alpha, *beta;      // [Wr][nloc][N] stepping stones, donor order
+  float *ls_alpha, *ls_beta;  // [Wr][nloc]
   int sum_mode;             // RL_SUM_EXACT / RL_SUM_LANES / RL_SUM_EXACT_SERIAL
   int merge_order;          // one launch for both directions: 0 = backward blocks first, then forward; 1 = interleaved
   unsigned long long *stats;  // 16 event counters (experiment builds with -DRL_STATS), else null

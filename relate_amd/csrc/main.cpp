@@ -10,7 +10,9 @@
 // Paint.cpp, BuildTopology.cpp of the reference; every other --mode is refused
 // (use the reference binary for them).  Extra options: --device n,
 // --sum_mode exact|lanes|lanes32, --find_equivalent_branches (with PaintBuildTopology / BuildTopology over all
-// sections of a chunk: the stage downstream fused in, every .anc written once).
+// sections of a chunk: the stage downstream fused in, every .anc written once), --paint_all_windows (PaintBuildTopology
+// of a section range paints the range's windows only, RelateParallel.sh:231-257; with it, every window as --mode Paint
+// does, which ignores the section options as in the reference).
 #include <sys/resource.h>
 #include <unistd.h>
 
@@ -173,6 +175,7 @@ int main(int argc, char **argv) {
       {"output", true}, {"painting", true}, {"seed", true}, {"fb", true}, {"sample_ages", true},
       {"no_consistency", false}, {"device", true}, {"sum_mode", true}, {"help", false},
       {"find_equivalent_branches", false},  // (PaintBuildTopology / BuildTopology of a whole chunk: the next stage fused in)
+      {"paint_all_windows", false},  // (PaintBuildTopology of a section range: Paint keeps every window, not the range's)
       {"input", true},  // (OptimizeParameters: the grid, Relate.cpp:43)
       // accepted and ignored by these two modes in the reference as well
       {"haps", true}, {"sample", true}, {"map", true}, {"mutation_rate", true}, {"effectiveN", true},
@@ -302,6 +305,7 @@ int main(int argc, char **argv) {
   const std::string ages = opt.count("sample_ages") ? opt["sample_ages"] : std::string();
   so.sample_ages_path = ages.empty() ? nullptr : ages.c_str();  // BuildTopology.cpp:93-108
   so.find_equivalent_branches = opt.count("find_equivalent_branches") ? 1 : 0;
+  if (opt.count("paint_all_windows")) so.paint_windows = 0;  // (read by PaintBuildTopology alone)
   if (mode == "OptimizeParameters") {
     return optimize_parameters(opt, so);
   } else if (mode == "Paint") {

@@ -212,7 +212,7 @@ RL_DEV void paint32_forward(const PaintParams &p, int k, float *stage, WaveLink<
   pl.init(p.lay, k, wv);
   const PaintConsts &c = p.c;
   const int64_t off = p.plan_off[k];
-  const int D = (int)(p.plan_off[k + 1] - off);
+  const int D = forward_steps(k, (int)(p.plan_off[k + 1] - off));  // (paint_device.h: ends at the range's last stone)
   const int32_t *__restrict__ st = p.sites + off;
   const double *__restrict__ cfp = p.cf + off;
   const double *__restrict__ nx = p.nxt + off;
@@ -249,13 +249,15 @@ RL_DEV void paint32_forward(const PaintParams &p, int k, float *stage, WaveLink<
   int wa = 0;
   auto stone_index = [&](int w) {
     const ColdParams32 cp = cold_params<PaintParams>();
-    return w < cp->W ? cp->stone_ia[(size_t)k * cp->W + w] : -1;
+    return w <= cp->w_last ? cp->stone_ia[(size_t)k * cp->W + w] : -1;
   };
-  auto write_stone = [&]() {
+  auto write_stone = [&]() {  // (the stones below the window range are walked past, not written)
     const ColdParams32 cp = cold_params<PaintParams>();
-    const size_t N = cp->lay.N, row = (size_t)wa * cp->nloc + (k - cp->k0);
-    emit_stone32<S>(pl, a, cp->alpha + row * N, 0.0f, stage);
-    if (pl.lane == 0 && wv == 0) cp->ls_alpha[row] = (float)ls;
+    if (wa >= cp->w_first) {
+      const size_t N = cp->lay.N, row = (size_t)(wa - cp->w_first) * cp->nloc + (k - cp->k0);
+      emit_stone32<S>(pl, a, cp->alpha + row * N, 0.0f, stage);
+      if (pl.lane == 0 && wv == 0) cp->ls_alpha[row] = (float)ls;
+    }
     wa++;
   };
   int next_stone = stone_index(0);
@@ -335,7 +337,7 @@ RL_DEV void paint32_backward(const PaintParams &p, int k, float *stage, WaveLink
   pl.init(p.lay, k, wv);
   const PaintConsts &c = p.c;
   const int64_t off = p.plan_off[k];
-  const int D = (int)(p.plan_off[k + 1] - off);
+  const int D = ((int)(p.plan_off[k + 1] - off));
   const int32_t *__restrict__ st = p.sites + off;
   const double *__restrict__ cfp = p.cf + off;
   const double *__restrict__ nx = p.nxt + off;
@@ -358,13 +360,15 @@ RL_DEV void paint32_backward(const PaintParams &p, int k, float *stage, WaveLink
   int we = p.W - 1;
   auto stone_index = [&](int w) {
     const ColdParams32 cp = cold_params<PaintParams>();
-    return w >= 0 ? cp->stone_ie[(size_t)k * cp->W + w] : -2;
+    return w >= cp->w_first ? cp->stone_ie[(size_t)k * cp->W + w] : -2;
   };
-  auto write_stone = [&](float self_value) {
+  auto write_stone = [&](float self_value) {  // (the stones above the window range are walked past, not written)
     const ColdParams32 cp = cold_params<PaintParams>();
-    const size_t N = cp->lay.N, row = (size_t)we * cp->nloc + (k - cp->k0);
-    emit_stone32<S>(pl, b, cp->beta + row * N, self_value, stage);
-    if (pl.lane == 0 && wv == 0) cp->ls_beta[row] = (float)ls;
+    if (we <= cp->w_last) {
+      const size_t N = cp->lay.N, row = (size_t)(we - cp->w_first) * cp->nloc + (k - cp->k0);
+      emit_stone32<S>(pl, b, cp->beta + row * N, self_value, stage);
+      if (pl.lane == 0 && wv == 0) cp->ls_beta[row] = (float)ls;
+    }
     we--;
   };
   int next_stone = stone_index(we);
@@ -384,7 +388,8 @@ RL_DEV void paint32_backward(const PaintParams &p, int k, float *stage, WaveLink
   float K1 = (float)c.K1;
   asm volatile("" : "+v"(K1));
   const double theta = c.theta, ntheta = c.ntheta;
-  for (int j = D - 2; j >= 0; j--) {
+  const int j_last = backward_last(k);  // (paint_device.h: D and ls above keep the whole pass, the walk ends at the range's first stone)
+  for (int j = D - 2; j >= j_last; j--) {
     retire_touch(touched);
     if (j > 0) touched = touch_row(p.masks, S, s2, pl.lane, WAVES, wv);
     s0 = s1;

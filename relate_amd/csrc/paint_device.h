@@ -205,6 +205,27 @@ RL_DEV const __attribute__((address_space(4))) P *cold_params() {
   asm volatile("" : "+s"(q));
   return q;
 }
+// Trip bounds of the stepping-stone passes under a window range (PaintParams w_first / w_last, rl_set_window_range).
+// Window w reads the alpha stone at its begin boundary and the beta stone at its end boundary alone
+// (anc_builder.cpp:49-78), so the forward pass of target k has nothing left to feed behind visited index
+// stone_ia[k][w_last] and the backward pass nothing below stone_ie[k][w_first].  The default range keeps every step of
+// both passes, as a Paint without a range always ran.  Wave-uniform: read once per pass from the cold parameter block
+// and the stone tables the stone lambdas read anyway, never held across the step loop as anything but its bound.
+// Two-wave workgroups (N > 5120): both waves of a target read the SAME table entries here, so their trip counts -- and
+// with them the WaveLink exchanges of every step's sum -- keep matching.
+RL_DEV bool paints_all_windows(const __attribute__((address_space(4))) PaintParams *cp) {
+  return cp->w_first == 0 && cp->w_last == cp->W - 1;
+}
+// visited indices [0, forward_steps) are walked by the forward pass of target k, D its visited sites
+RL_DEV int forward_steps(int k, int D) {
+  const auto cp = cold_params<PaintParams>();
+  return paints_all_windows(cp) ? D : cp->stone_ia[(size_t)k * cp->W + cp->w_last] + 1;
+}
+// the backward pass walks from D - 1 down to this visited index
+RL_DEV int backward_last(int k) {
+  const auto cp = cold_params<PaintParams>();
+  return paints_all_windows(cp) ? 0 : cp->stone_ie[(size_t)k * cp->W + cp->w_first];
+}
 // a loop constant that the exec-masked asm takes in a VGPR: keep it there
 RL_DEV double in_vgpr(double v) {
   asm volatile("" : "+v"(v));

@@ -64,7 +64,7 @@ RL_DEV void paint_forward(const PaintParams &p, int k, float *stage, WaveLink<WA
   pl.init(p.lay, k, wv);
   const PaintConsts &c = p.c;
   const int64_t off = p.plan_off[k];
-  const int D = (int)(p.plan_off[k + 1] - off);
+  const int D = forward_steps(k, (int)(p.plan_off[k + 1] - off));  // (paint_device.h: ends at the range's last stone)
   // the plan arrays come in by vector loads (vmcnt), requested a step ahead
   const int32_t *__restrict__ st = p.sites + off;
   const double *__restrict__ cfp = p.cf + off;
@@ -89,13 +89,15 @@ RL_DEV void paint_forward(const PaintParams &p, int k, float *stage, WaveLink<WA
   // stone wa of the target: written when the visited index reaches stone_ia[k][wa] (:354-374)
   auto stone_index = [&](int w) {
     const ColdParams cp = cold_params<PaintParams>();
-    return w < cp->W ? cp->stone_ia[(size_t)k * cp->W + w] : -1;
+    return w <= cp->w_last ? cp->stone_ia[(size_t)k * cp->W + w] : -1;
   };
-  auto write_stone = [&]() {
+  auto write_stone = [&]() {  // (the stones below the window range are walked past, not written)
     const ColdParams cp = cold_params<PaintParams>();
-    const size_t N = cp->lay.N, row = (size_t)wa * cp->nloc + (k - cp->k0);
-    emit_stone<S>(pl, a, cp->alpha + row * N, 0.0f, stage);
-    if (pl.lane == 0 && wv == 0) cp->ls_alpha[row] = (float)ls;
+    if (wa >= cp->w_first) {
+      const size_t N = cp->lay.N, row = (size_t)(wa - cp->w_first) * cp->nloc + (k - cp->k0);
+      emit_stone<S>(pl, a, cp->alpha + row * N, 0.0f, stage);
+      if (pl.lane == 0 && wv == 0) cp->ls_alpha[row] = (float)ls;
+    }
     wa++;
   };
   int next_stone = stone_index(0);
@@ -189,7 +191,7 @@ RL_DEV void paint_backward(const PaintParams &p, int k, float *stage, WaveLink<W
   pl.init(p.lay, k, wv);
   const PaintConsts &c = p.c;
   const int64_t off = p.plan_off[k];
-  const int D = (int)(p.plan_off[k + 1] - off);
+  const int D = ((int)(p.plan_off[k + 1] - off));
   const int32_t *__restrict__ st = p.sites + off;
   const double *__restrict__ cfp = p.cf + off;
   const double *__restrict__ nx = p.nxt + off;
@@ -209,13 +211,15 @@ RL_DEV void paint_backward(const PaintParams &p, int k, float *stage, WaveLink<W
   int we = p.W - 1;
   auto stone_index = [&](int w) {
     const ColdParams cp = cold_params<PaintParams>();
-    return w >= 0 ? cp->stone_ie[(size_t)k * cp->W + w] : -2;
+    return w >= cp->w_first ? cp->stone_ie[(size_t)k * cp->W + w] : -2;
   };
-  auto write_stone = [&](float self_value) {
+  auto write_stone = [&](float self_value) {  // (the stones above the window range are walked past, not written)
     const ColdParams cp = cold_params<PaintParams>();
-    const size_t N = cp->lay.N, row = (size_t)we * cp->nloc + (k - cp->k0);
-    emit_stone<S>(pl, b, cp->beta + row * N, self_value, stage);
-    if (pl.lane == 0 && wv == 0) cp->ls_beta[row] = (float)ls;
+    if (we <= cp->w_last) {
+      const size_t N = cp->lay.N, row = (size_t)(we - cp->w_first) * cp->nloc + (k - cp->k0);
+      emit_stone<S>(pl, b, cp->beta + row * N, self_value, stage);
+      if (pl.lane == 0 && wv == 0) cp->ls_beta[row] = (float)ls;
+    }
     we--;
   };
   int next_stone = stone_index(we);
@@ -235,7 +239,8 @@ RL_DEV void paint_backward(const PaintParams &p, int k, float *stage, WaveLink<W
   const double K1 = in_vgpr(c.K1), theta = in_vgpr(c.theta), ntheta = in_vgpr(c.ntheta);
   unsigned long long bseg1 = 0, bseg2 = 0, bseg3 = 0, bseg4 = 0;
   (void)bseg1; (void)bseg2; (void)bseg3; (void)bseg4;
-  for (int j = D - 2; j >= 0; j--) {
+  const int j_last = backward_last(k);  // (paint_device.h: D and ls above keep the whole pass, the walk ends at the range's first stone)
+  for (int j = D - 2; j >= j_last; j--) {
     retire_touch(touched);
     if (j > 0) touched = touch_row(p.masks, S, s2, pl.lane, WAVES, wv);
     s0 = s1;

@@ -1308,6 +1308,7 @@ void rl_stage_opts_init(rl_stage_opts *o) {
   o->rho = 1.0;
   o->gpu_build = -1;
   o->pin_threads = -1;
+  o->paint_windows = -1;
 }
 
 // the caller's struct, whatever its age: fields past its `size` keep their defaults
@@ -1391,12 +1392,25 @@ int rl_stage_paint_build_topology_ex(const char *out_dir, int chunk_index, int f
   int rc = rl_load_chunk(ctx, out_dir, chunk_index);
   lap("read chunk files");
   if (!rc && use_painting) rc = rl_set_painting(ctx, theta, rho);
+  // rl_stage_opts.paint_windows: a section reads its own window's stones alone (anc_builder.cpp:49-78), so a call for
+  // sections a .. b paints windows a .. b -- the passes stop at the range's last stone, the stones take (b - a + 1) / W
+  // of the memory (and of the HBM the admission of build_sections finds free, or of pinned host memory at config #5).
+  // (ranges build_sections refuses or empties -- first_section >= W, :45 -- are left to it; fused
+  // FindEquivalentBranches covers all sections anyway)
+  if (!rc && o.paint_windows != 0) {
+    const int w_last = std::min(last_section, ctx->W - 1);
+    if (first_section >= 0 && first_section <= w_last) rc = rl_set_window_range(ctx, first_section, w_last);
+  }
   if (!rc) {
     std::cerr << "---------------------------------------------------------" << std::endl;
     std::cerr << "Painting sequences (stepping stones stay on the device)..." << std::endl;
     rc = rl_paint(ctx, sum_mode, nullptr);
   }
   lap("plan + uploads + masks + paint kernels");
+  if (!rc && timing)
+    fprintf(stderr, "[fused stage] windows %d-%d of %d painted in %.1f ms: %lld forward + %lld backward steps, %.3f GB of "
+            "stones in %s\n", ctx->w_first, ctx->w_last, ctx->W, ctx->ms_paint, ctx->acc_fwd, ctx->acc_bwd,
+            1e-9 * (double)ctx->acc_bytes, ctx->h_alpha ? "pinned host memory" : "HBM");
   // RELATE_AMD_PARK_STONES=1: the stones to pinned host memory, their HBM to the sections' windows -- for chunks that
   // would not fit otherwise; at C3 (53 GB of stones) it opens 112 sections instead of 91 and the chunk takes 330 s
   // instead of 291 s: past ~90 trees in flight the build kernels slow each other down

@@ -446,6 +446,7 @@ rl_window *rl_window_open_bounded(rl_ctx *ctx, int w, const char *paint_file, in
       set_error("rl_window_open: no paint file given and rl_paint has not run");
       return nullptr;
     }
+    if (stone_row(ctx, w, "rl_window_open") < 0) return nullptr;  // (RL_ESTATE's case: the message names the range)
     // the stones stay in HBM: copied and run through the file's quantisation on the device below
     for (int t = 0; t < nloc; t++) {
       bb[t] = pl.bb[(size_t)(k0 + t) * W + w];
@@ -496,6 +497,7 @@ rl_window *rl_window_open_bounded(rl_ctx *ctx, int w, const char *paint_file, in
   win->maxD = maxD;
   win->sum_mode = sum_mode;
   win->cap_rows = (max_rows > 0 && max_rows < rows) ? std::max<int64_t>(max_rows, 3 * (int64_t)nloc + 64) : rows;
+  const size_t wr = paint_file ? 0 : (size_t)(w - ctx->w_first);  // row of the window among the context's painted ones (checked above)
   win->slab_off.assign(nloc, 0);
   win->slab_base.assign(nloc, 0);
   win->row_lo.assign(nloc, 0);
@@ -511,7 +513,7 @@ rl_window *rl_window_open_bounded(rl_ctx *ctx, int w, const char *paint_file, in
     // nearly equal values replaced by their first (collapsed_matrix.hpp:228-296) -- applied to the context's slice
     // where it lies, once
     const size_t sn = (size_t)nloc * N;
-    float *ca = ctx->d_alpha.as<float>() + (size_t)w * sn, *cb = ctx->d_beta.as<float>() + (size_t)w * sn;
+    float *ca = ctx->d_alpha.as<float>() + wr * sn, *cb = ctx->d_beta.as<float>() + wr * sn;
     std::lock_guard<std::mutex> s0_is_mine(ctx->repaint_mutex);
     if (ctx->stone_quantised.size() != (size_t)W) ctx->stone_quantised.assign((size_t)W, 0);
     if (!ctx->stone_quantised[w]) {
@@ -524,8 +526,8 @@ rl_window *rl_window_open_bounded(rl_ctx *ctx, int w, const char *paint_file, in
     }
     win->ab = ca;
     win->be = cb;
-    win->la = ctx->d_lsa.as<float>() + (size_t)w * nloc;
-    win->lb = ctx->d_lsb.as<float>() + (size_t)w * nloc;
+    win->la = ctx->d_lsa.as<float>() + wr * nloc;
+    win->lb = ctx->d_lsb.as<float>() + wr * nloc;
   } else {
     // the same on a copy: the context's stones stay as painted (rl_write_paint_files may still want them)
     const size_t sn = (size_t)nloc * N;
@@ -541,14 +543,14 @@ rl_window *rl_window_open_bounded(rl_ctx *ctx, int w, const char *paint_file, in
       return hipMemcpyAsync(dst, src, n * 4, hipMemcpyHostToDevice, ctx->s0) == hipSuccess ? 0 : RL_EHIP;
     };
     if (ctx->h_alpha) {  // (parked on the host by the fused stage)
-      rc = rc ? rc : h2d(win->d_ab.p, ctx->h_alpha + (size_t)w * sn, sn);
-      rc = rc ? rc : h2d(win->d_be.p, ctx->h_beta + (size_t)w * sn, sn);
+      rc = rc ? rc : h2d(win->d_ab.p, ctx->h_alpha + wr * sn, sn);
+      rc = rc ? rc : h2d(win->d_be.p, ctx->h_beta + wr * sn, sn);
     } else {
-      rc = rc ? rc : d2d(win->d_ab.p, ctx->d_alpha.as<float>() + (size_t)w * sn, sn);
-      rc = rc ? rc : d2d(win->d_be.p, ctx->d_beta.as<float>() + (size_t)w * sn, sn);
+      rc = rc ? rc : d2d(win->d_ab.p, ctx->d_alpha.as<float>() + wr * sn, sn);
+      rc = rc ? rc : d2d(win->d_be.p, ctx->d_beta.as<float>() + wr * sn, sn);
     }
-    rc = rc ? rc : d2d(win->d_la.p, ctx->d_lsa.as<float>() + (size_t)w * nloc, nloc);
-    rc = rc ? rc : d2d(win->d_lb.p, ctx->d_lsb.as<float>() + (size_t)w * nloc, nloc);
+    rc = rc ? rc : d2d(win->d_la.p, ctx->d_lsa.as<float>() + wr * nloc, nloc);
+    rc = rc ? rc : d2d(win->d_lb.p, ctx->d_lsb.as<float>() + wr * nloc, nloc);
     if (!rc && (launch_quantise(win->d_ab.as<float>(), nloc, N, ctx->s0) != hipSuccess ||
                 launch_quantise(win->d_be.as<float>(), nloc, N, ctx->s0) != hipSuccess ||
                 hipStreamSynchronize(ctx->s0) != hipSuccess)) {
