@@ -521,6 +521,39 @@ int rl_stage_find_equivalent_branches(const char *out_dir, int chunk_index);
 int rl_debug_feb_fused_from_files(const char *out_dir, int chunk_index, const int *order, int n_order,
                                   int pool_threads);
 
+/* -------------------------------------------------------- CompareTopology */
+/* Clade distance (Robinson-Foulds, rooted, unnormalised) between trees on the leaves 0..N-1, each given as the parent
+ * array this library's builder returns (2N-1 ints, root = -1).  The clades of a tree are the leaf sets of its internal
+ * nodes other than the root; d(A,B) = |clades(A) \ clades(B)| + |clades(B) \ clades(A)|, an integer in 0..2(N-2).
+ * No reference counterpart in the pipeline (the sibling is PartitionMetric of the reference's tree_comparer); the
+ * definition is the contract.  Integers throughout: the host and the device return the same numbers.
+ *   A tree must be binary with labels rising from child to parent (parent[v] > v, leaves 0..N-1 childless, node 2N-2
+ *   the root), as MinMatch numbers them; anything else is RL_EINVAL with a message naming the tree and the node.
+ *   rl_compare_trees: parentsA / parentsB hold as many trees as `pairs` refers to (pairs[2k], pairs[2k+1] = index of
+ *     pair k's tree in A / in B, >= 0); out[k] = d.  device >= 0: on that GPU (relate_amd/csrc/compare_kernels.hip,
+ *     one workgroup per pair, 2 <= N <= 10240; RL_ENODEVICE without one); device < 0: the host implementation
+ *     (compare.cpp), one thread, any N >= 2.
+ *   rl_compare_anc: two .anc files position by position.  A file covers the SNPs from its first tree's position to
+ *     the largest SNP_end of its last tree, inclusive (what BuildTopology writes there: the section's last SNP); the
+ *     comparison runs over the SNPs both files cover (none: RL_EINVAL, as are different N).  The positions of the
+ *     trees of both files are merged; every interval [snp_begin, snp_end) of the merge pairs one tree of A with one
+ *     of B.  per_interval_path (may be NULL): a text file, one line `snp_begin snp_end treeA treeB d` per interval.
+ *     summary: see the struct; mean_normalised is summed in double in interval order on the host. */
+typedef struct rl_compare_summary {
+  int N;                  /* leaves                                                            */
+  int trees_a, trees_b;   /* trees in each file                                                */
+  int intervals;          /* intervals of the merge                                            */
+  int snp_begin, snp_end; /* the compared SNPs: [snp_begin, snp_end)                           */
+  int max_distance;       /* largest d of an interval                                          */
+  long long snps_identical; /* SNPs in intervals with d == 0                                   */
+  double mean_normalised; /* sum over intervals of length * d / (2(N-2)), over snp_end - snp_begin (0 for N = 2) */
+  double share_identical; /* snps_identical / (snp_end - snp_begin)                            */
+} rl_compare_summary;
+int rl_compare_trees(const int *parentsA, const int *parentsB, int N, int npairs, const int *pairs, int device,
+                     int *out);
+int rl_compare_anc(const char *ancA, const char *ancB, int device, rl_compare_summary *summary,
+                   const char *per_interval_path_or_null);
+
 /* ------------------------------------------------------------------ tools */
 /* Synthetic block-coalescent panel (stand-in for MakeChunks input,
  * SURVEY.md 8d).  seq_chars (L*N) and/or bits (L*row_words) may be NULL. */

@@ -63,6 +63,10 @@ def lib():
         L.rl_debug_map_mutation.argtypes = [C.c_int, C.c_void_p, C.c_void_p]
         L.rl_debug_cancel_rowmin.restype = C.c_int
         L.rl_debug_cancel_rowmin.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_float, C.c_void_p]
+        L.rl_compare_trees.restype = C.c_int
+        L.rl_compare_trees.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p]
+        L.rl_compare_anc.restype = C.c_int
+        L.rl_compare_anc.argtypes = [C.c_char_p, C.c_char_p, C.c_int, C.c_void_p, C.c_char_p]
         _lib = L
     return _lib
 
@@ -560,6 +564,58 @@ def debug_cancel_rowmin(d, carriers, log_ratio):
     rowmin = np.empty(N, np.float32)
     _check(lib().rl_debug_cancel_rowmin(_p(d), N, _p(carriers), float(np.float32(log_ratio)), _p(rowmin)))
     return d, rowmin
+
+
+class CompareSummary(C.Structure):
+    """rl_compare_summary (include/relate_amd.h)"""
+    _fields_ = [("N", C.c_int), ("trees_a", C.c_int), ("trees_b", C.c_int), ("intervals", C.c_int),
+                ("snp_begin", C.c_int), ("snp_end", C.c_int), ("max_distance", C.c_int),
+                ("snps_identical", C.c_longlong), ("mean_normalised", C.c_double), ("share_identical", C.c_double)]
+
+
+def compare_trees(parents_a, parents_b, pairs=None, device=None):
+    """rl_compare_trees: clade (rooted Robinson-Foulds) distance of pairs of trees given as parent arrays.
+    parents_a, parents_b: [trees][2N-1] (or one tree each); pairs: [npairs][2] indices (tree of A, tree of B), default
+    tree k of A with tree k of B; device: None = the host implementation, an int = that GPU.  -> int32 [npairs]"""
+    pa = np.ascontiguousarray(np.atleast_2d(parents_a), dtype=np.int32)
+    pb = np.ascontiguousarray(np.atleast_2d(parents_b), dtype=np.int32)
+    if pa.shape[1] != pb.shape[1] or pa.shape[1] % 2 == 0:
+        raise RelateError("compare_trees: parent arrays of %d and %d nodes" % (pa.shape[1], pb.shape[1]))
+    N = (pa.shape[1] + 1) // 2
+    if pairs is None:
+        if len(pa) != len(pb):
+            raise RelateError("compare_trees: %d and %d trees and no pairs given" % (len(pa), len(pb)))
+        pairs = np.repeat(np.arange(len(pa)), 2)
+    pairs = np.ascontiguousarray(pairs, dtype=np.int32).reshape(-1, 2)
+    if len(pairs) and (pairs[:, 0].max() >= len(pa) or pairs[:, 1].max() >= len(pb)):
+        raise RelateError("compare_trees: a pair names a tree that was not given")
+    out = np.zeros(len(pairs), np.int32)
+    _check(lib().rl_compare_trees(_p(pa), _p(pb), N, len(pairs), _p(pairs), -1 if device is None else int(device),
+                                  _p(out)))
+    return out
+
+
+def compare_anc(anc_a, anc_b, device=None, per_interval_path=None):
+    """rl_compare_anc: two .anc files position by position -> dict of the summary's fields plus "per_interval": int
+    array [intervals][5] of (snp_begin, snp_end, tree of A, tree of B, d), read back from the text file the library
+    writes (per_interval_path, or a temporary file)"""
+    import tempfile
+    s = CompareSummary()
+    tmp = None
+    if per_interval_path is None:
+        fd, tmp = tempfile.mkstemp(suffix=".cmp")
+        os.close(fd)
+    try:
+        path = per_interval_path or tmp
+        _check(lib().rl_compare_anc(os.fsencode(anc_a), os.fsencode(anc_b), -1 if device is None else int(device),
+                                    C.byref(s), os.fsencode(path)))
+        rows = np.loadtxt(path, dtype=np.int64, ndmin=2).reshape(-1, 5)
+    finally:
+        if tmp:
+            os.remove(tmp)
+    out = {k: getattr(s, k) for k, _ in CompareSummary._fields_}
+    out["per_interval"] = rows
+    return out
 
 
 def stage_find_equivalent_branches(out_dir, chunk_index=0):

@@ -1,0 +1,29 @@
+// anc_file.h -- the binary .anc file (AncesTree::DumpBin / ReadBin of the reference) in memory: read by
+// FindEquivalentBranches (equivalent.cpp), which rewrites it, and by CompareTopology (compare.cpp).
+#pragma once
+#include <string>
+#include <vector>
+
+namespace rl {
+
+struct AncTree {
+  int pos = 0;
+  std::vector<int> parent, snp_begin, snp_end;
+  std::vector<double> branch_length;
+  std::vector<float> num_events;
+  std::vector<int> child_left, child_right;  // as Tree::ReadTreeBin assigns them: first / second child in node order
+};
+
+struct AncFile {
+  bool has_ages = false;
+  unsigned N = 0;
+  std::vector<double> ages;
+  std::vector<AncTree> trees;
+};
+
+// AncesTree::ReadBin (src/anc.cpp:941-968) + Tree::ReadTreeBin (:83-125)
+int read_anc(const std::string &fn, AncFile &a);
+// AncesTree::DumpBin (src/anc.cpp:1104-1167)
+int write_anc(const std::string &fn, const AncFile &a);
+
+}  // namespace rl

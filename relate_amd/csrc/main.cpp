@@ -6,6 +6,10 @@
 //          [--painting theta,rho] [--seed s] [--fb x] [--no_consistency]
 //   Relate --mode OptimizeParameters --haps x.haps --sample x.sample --map x.map [--memory 5] [--dist f]
 //          [-i grid.txt] [--painting theta,rho] -o out      (writes out.opt: `theta factor not-mapping-SNPs` per pair)
+//   Relate --mode CompareTopology -i a.anc,b.anc [-o out] [--device d]
+//          (no reference counterpart: the clade distance of the two files' trees position by position, the summary on
+//           stdout as `key value` lines; with -o, out.cmp: `snp_begin snp_end treeA treeB d` per interval; --device -1:
+//           on the host)
 // Same options, files and stderr banners as include/pipeline/Relate.cpp:19-115,
 // Paint.cpp, BuildTopology.cpp of the reference; every other --mode is refused
 // (use the reference binary for them).  Extra options: --device n,
@@ -37,7 +41,7 @@ static void usage_line() {
   std::cerr << "---------------------------------------------------------" << std::endl << std::endl;
 }
 
-static const char *kModes = "MakeChunks|Paint|BuildTopology|PaintBuildTopology|FindEquivalentBranches|OptimizeParameters";
+static const char *kModes = "MakeChunks|Paint|BuildTopology|PaintBuildTopology|FindEquivalentBranches|OptimizeParameters|CompareTopology";
 
 // `Relate --mode OptimizeParameters` (pipeline/OptimizeParameters.cpp:22-206): MakeChunks, then for every chunk the
 // grid of (theta, recombination factor) through rl_stage_optimize_parameters, the temporary files removed as the
@@ -159,6 +163,33 @@ static int optimize_parameters(std::map<std::string, std::string> &opt, rl_stage
   return 0;
 }
 
+// `Relate --mode CompareTopology -i a.anc,b.anc [-o out] [--device d]` (rl_compare_anc)
+static int compare_topology(std::map<std::string, std::string> &opt) {
+  const std::string in = opt.count("input") ? opt["input"] : std::string();
+  const size_t c = in.find(',');
+  if (c == std::string::npos || c == 0 || c + 1 == in.size()) {
+    std::cerr << "Not enough arguments supplied." << std::endl;
+    std::cerr << "Needed: -i,--input a.anc,b.anc. Optional: output, device." << std::endl;
+    return 1;
+  }
+  const std::string a = in.substr(0, c), b = in.substr(c + 1);
+  const std::string cmp = opt.count("output") ? opt["output"] + ".cmp" : std::string();
+  rl_compare_summary s;
+  if (rl_compare_anc(a.c_str(), b.c_str(), opt.count("device") ? atoi(opt["device"].c_str()) : 0, &s,
+                     cmp.empty() ? nullptr : cmp.c_str()) != 0) {
+    std::cerr << "Error: " << rl_last_error() << std::endl;
+    return 1;
+  }
+  char line[512];
+  snprintf(line, sizeof line,
+           "haplotypes %d\ntrees_a %d\ntrees_b %d\nintervals %d\nsnp_begin %d\nsnp_end %d\nmean_normalised_distance %.17g\n"
+           "max_distance %d\nsnps_identical %lld\nshare_identical %.17g\n",
+           s.N, s.trees_a, s.trees_b, s.intervals, s.snp_begin, s.snp_end, s.mean_normalised, s.max_distance,
+           s.snps_identical, s.share_identical);
+  std::cout << line;
+  return 0;
+}
+
 int main(int argc, char **argv) {
   // BuildTopology keeps several tree-builder launches and window kernels in flight from its section threads: more
   // hardware queues than HIP's default four (read when the runtime starts; an explicit setting wins) -- but not more
@@ -210,9 +241,11 @@ int main(int argc, char **argv) {
   }
   if ((opt.count("help") && !(opt.count("mode") && opt["mode"] == "OptimizeParameters")) || !opt.count("mode")) {
     std::cerr << "Usage: Relate --mode " << kModes << " [--chunk_index c] -o out [options]" << std::endl;
+    std::cerr << "  CompareTopology: -i,--input a.anc,b.anc [-o out] [--device d]" << std::endl;
     return opt.count("help") ? 0 : 1;
   }
   const std::string mode = opt["mode"];
+  if (mode == "CompareTopology") return compare_topology(opt);
   if (mode == "OptimizeParameters" && opt.count("output") && opt["output"].find('/') != std::string::npos) {
     std::cerr << "Output needs to be in working directory." << std::endl;  // Relate.cpp:50-58
     return 1;
