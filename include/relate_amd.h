@@ -554,6 +554,35 @@ int rl_compare_trees(const int *parentsA, const int *parentsB, int N, int npairs
 int rl_compare_anc(const char *ancA, const char *ancB, int device, rl_compare_summary *summary,
                    const char *per_interval_path_or_null);
 
+/* ---------------------------------------------------- PairwiseCoalescence */
+/* The most recent common ancestor (MRCA) of every pair of haplotypes, summed over a tree sequence: for trees on the
+ * leaves 0..N-1 given as CompareTopology takes them (2N-1 parents, binary, parent[v] > v, node 2N-2 the root with
+ * parent -1; anything else is RL_EINVAL with a message naming the tree and the node) and leaves i != j,
+ *   RL_PAIRWISE_SIZE: v_t(i,j) = the number of leaves below MRCA(i,j) in tree t, an integer in 2..N (topology only);
+ *   RL_PAIRWISE_TIME: v_t(i,j) = height(MRCA(i,j)), height(leaf) = 0, height(n) = height(c) + branch_length[c] with c
+ *     n's first child in node order (the child_left of the reference's Tree::ReadTreeBin; the recursion of
+ *     PairwiseTMRCA, src/tree_comparer.cpp:307, which this is the per-tree sibling of), in double, one addition per
+ *     node.  (The reference rounds heights to float and sums nothing over a sequence: the definition is the contract.)
+ *   S(i,j) = sum over the trees, in the order given, of w_t * v_t(i,j); S symmetric, its diagonal 0; W = sum of w_t;
+ *   the mean matrix is S / W.  SIZE: S is uint64, exact.  TIME: S is double, per element and tree
+ *   S = S + (double)w_t * v_t, the product rounded, then the sum (no fused multiply-add), trees strictly in order.
+ *   The host and the device return equal bits for both metrics.
+ *   rl_pairwise_trees: parents [ntrees][2N-1]; branch_length [ntrees][2N-1] (of the branch above each node; required
+ *     for TIME, ignored for SIZE); weights [ntrees], >= 0; sum_out: N*N uint64 (SIZE) or double (TIME), row-major;
+ *     *total_weight = W.  device >= 0: on that GPU (relate_amd/csrc/pairwise_kernels.hip, 2 <= N <= 10240, S kept on
+ *     the device while the trees go up in batches; RL_ENODEVICE without one); device < 0: the host implementation
+ *     (pairwise.cpp), one thread, any N >= 2.
+ *   rl_pairwise_anc: the trees of .anc files, files in the order given and one in memory at a time.  w_t = the SNPs
+ *     the tree covers, by the rule of rl_compare_anc: from its position to the next tree's, the last tree of a file
+ *     up to and including the largest SNP_end of its nodes.  All files must hold the same N (else RL_EINVAL); a file
+ *     with sample ages is RL_EINVAL for TIME (its leaves are not at height 0), fine for SIZE.  *N_out = N; with
+ *     sum_out NULL nothing else happens (N from the first file's header: what the caller sizes sum_out by). */
+enum { RL_PAIRWISE_SIZE = 0, RL_PAIRWISE_TIME = 1 };
+int rl_pairwise_trees(const int *parents, const double *branch_length_or_null, const long long *weights, int N,
+                      int ntrees, int metric, int device, void *sum_out, long long *total_weight);
+int rl_pairwise_anc(const char *const *anc_paths, int npaths, int metric, int device, void *sum_out_or_null,
+                    long long *total_weight, int *N_out);
+
 /* ------------------------------------------------------------------ tools */
 /* Synthetic block-coalescent panel (stand-in for MakeChunks input,
  * SURVEY.md 8d).  seq_chars (L*N) and/or bits (L*row_words) may be NULL. */

@@ -67,6 +67,12 @@ def lib():
         L.rl_compare_trees.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p]
         L.rl_compare_anc.restype = C.c_int
         L.rl_compare_anc.argtypes = [C.c_char_p, C.c_char_p, C.c_int, C.c_void_p, C.c_char_p]
+        L.rl_pairwise_trees.restype = C.c_int
+        L.rl_pairwise_trees.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
+                                        C.c_void_p, C.POINTER(C.c_longlong)]
+        L.rl_pairwise_anc.restype = C.c_int
+        L.rl_pairwise_anc.argtypes = [C.POINTER(C.c_char_p), C.c_int, C.c_int, C.c_int, C.c_void_p,
+                                      C.POINTER(C.c_longlong), C.POINTER(C.c_int)]
         _lib = L
     return _lib
 
@@ -616,6 +622,53 @@ def compare_anc(anc_a, anc_b, device=None, per_interval_path=None):
     out = {k: getattr(s, k) for k, _ in CompareSummary._fields_}
     out["per_interval"] = rows
     return out
+
+
+PAIRWISE_METRICS = {"size": 0, "time": 1}  # RL_PAIRWISE_SIZE, RL_PAIRWISE_TIME
+
+
+def _pairwise_metric(metric):
+    if metric not in PAIRWISE_METRICS:
+        raise RelateError("pairwise: metric %r is neither 'size' nor 'time'" % (metric,))
+    return PAIRWISE_METRICS[metric], np.float64 if metric == "time" else np.uint64
+
+
+def pairwise_trees(parents, weights, branch_length=None, metric="size", device=None):
+    """rl_pairwise_trees: S(i,j) = sum over the trees of weight * (leaves below the MRCA of i and j: metric "size";
+    its height: metric "time", which needs branch_length).  parents, branch_length: [trees][2N-1] (or one tree);
+    weights: [trees] integers >= 0; device: None = the host implementation, an int = that GPU.
+    -> (S [N][N] uint64 or float64, W = the sum of the weights)"""
+    m, dtype = _pairwise_metric(metric)
+    pa = np.ascontiguousarray(np.atleast_2d(parents), dtype=np.int32)
+    w = np.ascontiguousarray(np.atleast_1d(weights), dtype=np.int64)
+    if pa.shape[1] % 2 == 0 or len(w) != len(pa):
+        raise RelateError("pairwise_trees: %d parent arrays of %d nodes, %d weights" % (len(pa), pa.shape[1], len(w)))
+    bl = None
+    if branch_length is not None:
+        bl = np.ascontiguousarray(np.atleast_2d(branch_length), dtype=np.float64)
+        if bl.shape != pa.shape:
+            raise RelateError("pairwise_trees: branch lengths %s for parents %s" % (bl.shape, pa.shape))
+    N = (pa.shape[1] + 1) // 2
+    S = np.zeros((N, N), dtype)
+    W = C.c_longlong(0)
+    _check(lib().rl_pairwise_trees(_p(pa), _p(bl), _p(w), N, len(pa), m, -1 if device is None else int(device), _p(S),
+                                   C.byref(W)))
+    return S, W.value
+
+
+def pairwise_anc(paths, metric="size", device=None):
+    """rl_pairwise_anc: the same sum over the trees of .anc files (one path or a list, in that order), a tree's weight
+    the SNPs it covers -> (S [N][N] uint64 or float64, W = the SNPs covered)"""
+    m, dtype = _pairwise_metric(metric)
+    if isinstance(paths, (str, bytes, os.PathLike)):
+        paths = [paths]
+    arr = (C.c_char_p * len(paths))(*[os.fsencode(p) for p in paths])
+    dev = -1 if device is None else int(device)
+    N, W = C.c_int(0), C.c_longlong(0)
+    _check(lib().rl_pairwise_anc(arr, len(paths), m, dev, None, None, C.byref(N)))
+    S = np.zeros((N.value, N.value), dtype)
+    _check(lib().rl_pairwise_anc(arr, len(paths), m, dev, _p(S), C.byref(W), C.byref(N)))
+    return S, W.value
 
 
 def stage_find_equivalent_branches(out_dir, chunk_index=0):

@@ -1,6 +1,7 @@
 // anc_file.cpp -- reading and writing the binary .anc file (anc_file.h).
 #include "anc_file.h"
 
+#include <algorithm>
 #include <cstdio>
 #include <cstring>
 
@@ -94,6 +95,39 @@ int write_anc(const std::string &fn, const AncFile &a) {
   const bool bad = ferror(fp) != 0;
   if (fclose(fp) != 0 || bad) {  // (a full disc must not pass for a tree file)
     set_error("writing %s failed", fn.c_str());
+    return RL_EIO;
+  }
+  return RL_OK;
+}
+
+int anc_coverage(const AncFile &a, const char *fn, int *first, int *last) {
+  if (a.trees.empty()) {
+    set_error("%s holds no tree", fn);
+    return RL_EFORMAT;
+  }
+  for (size_t t = 1; t < a.trees.size(); t++)
+    if (a.trees[t].pos <= a.trees[t - 1].pos) {
+      set_error("%s: the position of tree %zu (%d) is not above that of the tree before it (%d)", fn, t, a.trees[t].pos, a.trees[t - 1].pos);
+      return RL_EFORMAT;
+    }
+  *first = a.trees.front().pos;
+  const AncTree &z = a.trees.back();
+  *last = std::max(z.pos, *std::max_element(z.snp_end.begin(), z.snp_end.end()));
+  return RL_OK;
+}
+
+int read_anc_header(const std::string &fn, unsigned *N, unsigned *trees, bool *has_ages) {
+  FILE *fp = fopen(fn.c_str(), "rb");
+  if (!fp) {
+    set_error("cannot open %s", fn.c_str());
+    return RL_EIO;
+  }
+  bool ok = fread(has_ages, sizeof(bool), 1, fp) == 1 && fread(N, 4, 1, fp) == 1;
+  if (ok && *has_ages) ok = fseek(fp, (long)*N * 8, SEEK_CUR) == 0;
+  ok = ok && fread(trees, 4, 1, fp) == 1;
+  fclose(fp);
+  if (!ok) {
+    set_error("%s: truncated or malformed .anc file", fn.c_str());
     return RL_EIO;
   }
   return RL_OK;

@@ -1,5 +1,6 @@
 // anc_file.h -- the binary .anc file (AncesTree::DumpBin / ReadBin of the reference) in memory: read by
-// FindEquivalentBranches (equivalent.cpp), which rewrites it, and by CompareTopology (compare.cpp).
+// FindEquivalentBranches (equivalent.cpp), which rewrites it, by CompareTopology (compare.cpp) and by
+// PairwiseCoalescence (pairwise.cpp).
 #pragma once
 #include <string>
 #include <vector>
@@ -25,5 +26,10 @@ struct AncFile {
 int read_anc(const std::string &fn, AncFile &a);
 // AncesTree::DumpBin (src/anc.cpp:1104-1167)
 int write_anc(const std::string &fn, const AncFile &a);
+// the SNPs a file covers: [*first, *last], from its first tree's position to the largest SNP_end of its last tree (a
+// tree covers from its position to the next tree's); RL_EFORMAT for a file without trees or with positions not rising
+int anc_coverage(const AncFile &a, const char *fn, int *first, int *last);
+// the header alone: haplotypes, trees, whether sample ages follow
+int read_anc_header(const std::string &fn, unsigned *N, unsigned *trees, bool *has_ages);
 
 }  // namespace rl

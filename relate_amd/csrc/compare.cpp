@@ -33,8 +33,8 @@ int compare_trees_device(const int *parentsA, int treesA, const int *parentsB, i
                          const int *pairs, int device, int *out);  // compare_kernels.hip
 
 // the shape every tree of this library has (MinMatch numbers a merged cluster after its parts): binary, leaves
-// 0..N-1, parent[v] > v, root 2N-2.  0, or the first node that breaks the rule + 1.
-static int first_bad_node(const int *parent, int N, std::vector<unsigned char> &kids) {
+// 0..N-1, parent[v] > v, root 2N-2.  0, or the first node that breaks the rule + 1.  (pairwise.cpp uses it as well.)
+int first_bad_node(const int *parent, int N, std::vector<unsigned char> &kids) {
   const int nodes = 2 * N - 1;
   kids.assign((size_t)nodes, 0);
   for (int v = 0; v < nodes - 1; v++) {
@@ -157,25 +157,6 @@ extern "C" int rl_compare_trees(const int *parentsA, const int *parentsB, int N,
   return RL_OK;
 }
 
-namespace {
-// the SNPs a file covers: [first, last], from its first tree's position to the largest SNP_end of its last tree
-int covered(const AncFile &a, const char *fn, int *first, int *last) {
-  if (a.trees.empty()) {
-    set_error("%s holds no tree", fn);
-    return RL_EFORMAT;
-  }
-  for (size_t t = 1; t < a.trees.size(); t++)
-    if (a.trees[t].pos <= a.trees[t - 1].pos) {
-      set_error("%s: the position of tree %zu (%d) is not above that of the tree before it (%d)", fn, t, a.trees[t].pos, a.trees[t - 1].pos);
-      return RL_EFORMAT;
-    }
-  *first = a.trees.front().pos;
-  const AncTree &z = a.trees.back();
-  *last = std::max(z.pos, *std::max_element(z.snp_end.begin(), z.snp_end.end()));
-  return RL_OK;
-}
-}  // namespace
-
 extern "C" int rl_compare_anc(const char *ancA, const char *ancB, int device, rl_compare_summary *summary,
                               const char *per_interval_path) {
   if (!ancA || !ancB || !summary) {
@@ -197,7 +178,7 @@ extern "C" int rl_compare_anc(const char *ancA, const char *ancB, int device, rl
   }
   const int N = (int)A.N;
   int a0, a1, b0, b1;
-  if ((rc = covered(A, ancA, &a0, &a1)) || (rc = covered(B, ancB, &b0, &b1))) return rc;
+  if ((rc = anc_coverage(A, ancA, &a0, &a1)) || (rc = anc_coverage(B, ancB, &b0, &b1))) return rc;
   const int begin = std::max(a0, b0), end = std::min(a1, b1) + 1;  // [begin, end)
   if (begin >= end) {
     set_error("CompareTopology: the SNP ranges do not overlap: %s covers %d..%d, %s covers %d..%d", ancA, a0, a1, ancB, b0, b1);

@@ -6,7 +6,8 @@
 // itself (and that the tree is binary) before it uses a label as an index, and answers -1 (tree A) or -2 (tree B)
 // for the pair instead of a distance when it does not hold.
 //
-// Steps of a pair (T threads; "wave 0" steps run on the first wavefront while the others wait at the barrier):
+// Steps of a pair (T threads; "wave 0" steps run on the first wavefront while the others wait at the barrier; steps
+// 1 to 3 are the passes of tree_passes.h, which PairwiseCoalescence runs as well):
 //   1. kids of A, all threads: every node v puts v+1 into its parent's word with atomicMax (low half: the child with
 //      the larger label, the SECOND child), then every other child adds (v+1) << 16 (high half: the FIRST child).  A
 //      parent label that is not above its child's, not internal or out of range, a root with a parent, an internal
@@ -34,45 +35,12 @@
 #include <vector>
 
 #include "common.h"
+#include "tree_passes.h"
 
 namespace rl {
 
 constexpr int kCompareMaxN = 10240;
 constexpr int kCompareSmallN = 1024;  // up to here one wavefront per pair
-
-typedef unsigned short u16;
-
-// step 1 / step 5.  K: ni words; up (may be null): ni parent indices (internal numbering) of the internal nodes.
-// All threads of the workgroup call it; returns the same value to all.
-template <int T>
-__device__ bool build_kids(const int *__restrict__ par, int N, unsigned *K, u16 *up, int *bad) {
-  const int nodes = 2 * N - 1, ni = N - 1;
-  for (int i = threadIdx.x; i < ni; i += T) K[i] = 0u;
-  if (threadIdx.x == 0) *bad = par[nodes - 1] != -1;
-  __syncthreads();
-  for (int v = threadIdx.x; v < nodes - 1; v += T) {
-    const int p = par[v];
-    if (!(p > v && p >= N && p < nodes)) {
-      *bad = 1;
-    } else {
-      atomicMax(&K[p - N], (unsigned)(v + 1));
-      if (up && v >= N) up[v - N] = (u16)(p - N);
-    }
-  }
-  __syncthreads();
-  if (*bad) return false;
-  for (int v = threadIdx.x; v < nodes - 1; v += T) {
-    const int p = par[v];
-    if ((K[p - N] & 0xffffu) != (unsigned)(v + 1)) atomicAdd(&K[p - N], (unsigned)(v + 1) << 16);
-  }
-  __syncthreads();
-  for (int i = threadIdx.x; i < ni; i += T) {
-    const unsigned k = K[i];
-    if ((k & 0xffffu) == 0u || (k >> 16) == 0u) *bad = 1;
-  }
-  __syncthreads();
-  return *bad == 0;
-}
 
 template <int T>
 __global__ void __launch_bounds__(T) clade_distance_kernel(const int *__restrict__ PA, const int *__restrict__ PB, int N,
@@ -101,71 +69,16 @@ __global__ void __launch_bounds__(T) clade_distance_kernel(const int *__restrict
     if (threadIdx.x == 0) out[pair] = -1;
     return;
   }
-  // ---- 2
+  // ---- 2, 3
   if (wave0) {
-    for (int b = 0; b < ni; b += 64) {
-      const int i = b + lane;
-      const bool act = i < ni;
-      int d1 = -1, d2 = -1;  // lanes this one waits for
-      unsigned s1 = 0, s2 = 0;
-      if (act) {
-        const unsigned k = K[i];
-        const int c1 = (int)(k >> 16) - 1, c2 = (int)(k & 0xffffu) - 1;
-        if (c1 < N) s1 = 1;
-        else if (c1 - N < b) s1 = SZA[c1 - N];
-        else d1 = c1 - N - b;
-        if (c2 < N) s2 = 1;
-        else if (c2 - N < b) s2 = SZA[c2 - N];
-        else d2 = c2 - N - b;
+    wave_clade_sizes(K, N, SZA, lane);
+    wave_left_ends(K, SZA, UA, N, lane, [&](int i, unsigned lo, bool second, bool root) {
+      if (!root) {
+        const unsigned r = lo + SZA[i] - 1u;
+        if (second) TAB[lo] = (u16)r;
+        else TAB[r] = (u16)lo;
       }
-      unsigned sz = 0;
-      bool done = !act;
-      for (;;) {
-        const unsigned long long dm = __ballot(done);
-        if (dm == ~0ull) break;
-        const unsigned t1 = __shfl(sz, d1 < 0 ? 0 : d1, 64), t2 = __shfl(sz, d2 < 0 ? 0 : d2, 64);
-        if (!done && (d1 < 0 || ((dm >> d1) & 1)) && (d2 < 0 || ((dm >> d2) & 1))) {
-          sz = (d1 < 0 ? s1 : t1) + (d2 < 0 ? s2 : t2);
-          done = true;
-        }
-      }
-      if (act) SZA[i] = (u16)sz;
-    }
-    // ---- 3
-    for (int b = ((ni - 1) / 64) * 64; b >= 0; b -= 64) {
-      const int i = b + lane;
-      const bool act = i < ni, root = i == ni - 1;
-      int dep = -1;
-      unsigned base = 0, off = 0;
-      bool second = false;
-      if (act && !root) {
-        const int pi = UA[i];
-        const int c1 = (int)(K[pi] >> 16) - 1;  // the parent's first child
-        second = c1 != i + N;
-        if (second) off = c1 < N ? 1u : (unsigned)SZA[c1 - N];
-        if (pi >= b + 64) base = UA[pi];  // (its left end by now: written 64 or more labels ago)
-        else dep = pi - b;
-      }
-      unsigned lo = 0;
-      bool done = !act || root;
-      for (;;) {
-        const unsigned long long dm = __ballot(done);
-        if (dm == ~0ull) break;
-        const unsigned t = __shfl(lo, dep < 0 ? 0 : dep, 64);
-        if (!done && (dep < 0 || ((dm >> dep) & 1))) {
-          lo = (dep < 0 ? base : t) + off;
-          done = true;
-        }
-      }
-      if (act) {
-        UA[i] = (u16)lo;
-        if (!root) {
-          const unsigned r = lo + SZA[i] - 1u;
-          if (second) TAB[lo] = (u16)r;
-          else TAB[r] = (u16)lo;
-        }
-      }
-    }
+    });
   }
   __syncthreads();
   // ---- 4

@@ -10,6 +10,11 @@
 //          (no reference counterpart: the clade distance of the two files' trees position by position, the summary on
 //           stdout as `key value` lines; with -o, out.cmp: `snp_begin snp_end treeA treeB d` per interval; --device -1:
 //           on the host)
+//   Relate --mode PairwiseCoalescence -i a.anc[,b.anc,...] -o out [--metric size|time] [--device d]
+//          (no reference counterpart: for every pair of haplotypes the size (leaves below) or the time (height) of
+//           their most recent common ancestor, SNP-weighted over the files' trees; out.pwc: int32 N, int32 metric
+//           (0 size, 1 time), int64 W (SNPs), then the N x N sums (uint64 / double) row-major; the summary on stdout
+//           as `key value` lines; --device -1: on the host)
 // Same options, files and stderr banners as include/pipeline/Relate.cpp:19-115,
 // Paint.cpp, BuildTopology.cpp of the reference; every other --mode is refused
 // (use the reference binary for them).  Extra options: --device n,
@@ -41,7 +46,7 @@ static void usage_line() {
   std::cerr << "---------------------------------------------------------" << std::endl << std::endl;
 }
 
-static const char *kModes = "MakeChunks|Paint|BuildTopology|PaintBuildTopology|FindEquivalentBranches|OptimizeParameters|CompareTopology";
+static const char *kModes = "MakeChunks|Paint|BuildTopology|PaintBuildTopology|FindEquivalentBranches|OptimizeParameters|CompareTopology|PairwiseCoalescence";
 
 // `Relate --mode OptimizeParameters` (pipeline/OptimizeParameters.cpp:22-206): MakeChunks, then for every chunk the
 // grid of (theta, recombination factor) through rl_stage_optimize_parameters, the temporary files removed as the
@@ -190,6 +195,90 @@ static int compare_topology(std::map<std::string, std::string> &opt) {
   return 0;
 }
 
+// `Relate --mode PairwiseCoalescence -i a.anc[,b.anc,...] -o out [--metric size|time] [--device d]` (rl_pairwise_anc)
+static int pairwise_coalescence(std::map<std::string, std::string> &opt) {
+  std::vector<std::string> files;
+  {
+    std::istringstream in(opt.count("input") ? opt["input"] : std::string());
+    for (std::string f; getline(in, f, ',');)
+      if (!f.empty()) files.push_back(f);
+  }
+  if (files.empty() || !opt.count("output")) {
+    std::cerr << "Not enough arguments supplied." << std::endl;
+    std::cerr << "Needed: -i,--input a.anc[,b.anc,...], output. Optional: metric, device." << std::endl;
+    return 1;
+  }
+  const std::string name = opt.count("metric") ? opt["metric"] : std::string("size");
+  if (name != "size" && name != "time") {
+    std::cerr << "--metric must be size or time" << std::endl;
+    return 1;
+  }
+  const int metric = name == "time" ? RL_PAIRWISE_TIME : RL_PAIRWISE_SIZE;
+  const int device = opt.count("device") ? atoi(opt["device"].c_str()) : 0;
+  std::vector<const char *> paths;
+  for (const std::string &f : files) paths.push_back(f.c_str());
+  int N = 0;
+  long long W = 0;
+  if (rl_pairwise_anc(paths.data(), (int)paths.size(), metric, device, nullptr, nullptr, &N) != 0) {
+    std::cerr << "Error: " << rl_last_error() << std::endl;
+    return 1;
+  }
+  std::vector<uint64_t> S((size_t)N * N);  // (the bits of doubles for --metric time)
+  if (rl_pairwise_anc(paths.data(), (int)paths.size(), metric, device, S.data(), &W, &N) != 0) {
+    std::cerr << "Error: " << rl_last_error() << std::endl;
+    return 1;
+  }
+  long long trees = 0;
+  for (const std::string &f : files) {  // header of a .anc file: bool ages, uint32 N, [N doubles], uint32 trees
+    FILE *fp = fopen(f.c_str(), "rb");
+    unsigned char ages = 0;
+    unsigned n = 0, t = 0;
+    const bool ok = fp && fread(&ages, 1, 1, fp) == 1 && fread(&n, 4, 1, fp) == 1 &&
+                    (!ages || fseek(fp, (long)n * 8, SEEK_CUR) == 0) && fread(&t, 4, 1, fp) == 1;
+    if (fp) fclose(fp);
+    if (!ok) {
+      std::cerr << "Error: cannot read the header of " << f << std::endl;
+      return 1;
+    }
+    trees += t;
+  }
+  const std::string out = opt["output"] + ".pwc";
+  {
+    FILE *fp = fopen(out.c_str(), "wb");
+    const int32_t head[2] = {N, metric};
+    const int64_t w = W;
+    const bool ok = fp && fwrite(head, 4, 2, fp) == 2 && fwrite(&w, 8, 1, fp) == 1 && fwrite(S.data(), 8, S.size(), fp) == S.size();
+    if ((fp && fclose(fp) != 0) || !ok) {
+      std::cerr << "Error: writing " << out << " failed" << std::endl;
+      return 1;
+    }
+  }
+  // the mean matrix S / W: its off-diagonal mean (row order, double) and its extreme pairs (the first in row order)
+  auto mean_of = [&](size_t k) {
+    double s;
+    if (metric == RL_PAIRWISE_TIME) memcpy(&s, &S[k], 8);
+    else s = (double)S[k];
+    return s / (double)W;
+  };
+  double sum = 0.0, lo = 0.0, hi = 0.0;
+  int lo_i = -1, lo_j = -1, hi_i = -1, hi_j = -1;
+  for (int i = 0; i < N; i++)
+    for (int j = 0; j < N; j++) {
+      if (i == j) continue;
+      const double v = mean_of((size_t)i * N + j);
+      sum += v;
+      if (j < i) continue;
+      if (lo_i < 0 || v < lo) lo = v, lo_i = i, lo_j = j;
+      if (hi_i < 0 || v > hi) hi = v, hi_i = i, hi_j = j;
+    }
+  char line[768];
+  snprintf(line, sizeof line,
+           "haplotypes %d\nfiles %d\ntrees %lld\nsnps %lld\nmetric %s\nmean %.17g\nmin_pair %d %d %.17g\nmax_pair %d %d %.17g\n",
+           N, (int)files.size(), trees, W, name.c_str(), sum / ((double)N * (double)(N - 1)), lo_i, lo_j, lo, hi_i, hi_j, hi);
+  std::cout << line;
+  return 0;
+}
+
 int main(int argc, char **argv) {
   // BuildTopology keeps several tree-builder launches and window kernels in flight from its section threads: more
   // hardware queues than HIP's default four (read when the runtime starts; an explicit setting wins) -- but not more
@@ -208,6 +297,7 @@ int main(int argc, char **argv) {
       {"find_equivalent_branches", false},  // (PaintBuildTopology / BuildTopology of a whole chunk: the next stage fused in)
       {"paint_all_windows", false},  // (PaintBuildTopology of a section range: Paint keeps every window, not the range's)
       {"input", true},  // (OptimizeParameters: the grid, Relate.cpp:43)
+      {"metric", true},  // (PairwiseCoalescence: size | time)
       // accepted and ignored by these two modes in the reference as well
       {"haps", true}, {"sample", true}, {"map", true}, {"mutation_rate", true}, {"effectiveN", true},
       {"memory", true}, {"dist", true}, {"annot", true}, {"coal", true}, {"transversion", false}};
@@ -242,10 +332,12 @@ int main(int argc, char **argv) {
   if ((opt.count("help") && !(opt.count("mode") && opt["mode"] == "OptimizeParameters")) || !opt.count("mode")) {
     std::cerr << "Usage: Relate --mode " << kModes << " [--chunk_index c] -o out [options]" << std::endl;
     std::cerr << "  CompareTopology: -i,--input a.anc,b.anc [-o out] [--device d]" << std::endl;
+    std::cerr << "  PairwiseCoalescence: -i,--input a.anc[,b.anc,...] -o out [--metric size|time] [--device d]" << std::endl;
     return opt.count("help") ? 0 : 1;
   }
   const std::string mode = opt["mode"];
   if (mode == "CompareTopology") return compare_topology(opt);
+  if (mode == "PairwiseCoalescence") return pairwise_coalescence(opt);
   if (mode == "OptimizeParameters" && opt.count("output") && opt["output"].find('/') != std::string::npos) {
     std::cerr << "Output needs to be in working directory." << std::endl;  // Relate.cpp:50-58
     return 1;

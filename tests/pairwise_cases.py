@@ -1,0 +1,128 @@
+"""The oracle of the PairwiseCoalescence tests (test_pairwise_cpu.py, test_pairwise_gpu.py).  Nothing here calls the
+library: the definition of include/relate_amd.h is restated with Python sets, ints and floats -- the ancestors of
+every leaf, the MRCA of two leaves as the smallest label among their common ancestors (labels rise towards the root),
+sizes by counting leaves, heights by the first-child recursion, sums in tree order."""
+import numpy as np
+
+from compare_cases import ANC_NODE, balanced, caterpillar, random_tree  # noqa: F401  (the tests' tree shapes)
+
+
+def tree_values(parent, branch_length, metric):
+    """-> (mrca [N][N] of labels, None on the diagonal; value per node label: leaves below it or its height)"""
+    parent = [int(p) for p in parent]
+    nodes = len(parent)
+    N = (nodes + 1) // 2
+    above = []
+    for leaf in range(N):
+        s, v = set(), parent[leaf]
+        while v != -1:
+            s.add(v)
+            v = parent[v]
+        above.append(s)
+    mrca = [[None if i == j else min(above[i] & above[j]) for j in range(N)] for i in range(N)]
+    if metric == "size":
+        value = {m: sum(1 for leaf in range(N) if m in above[leaf]) for m in range(N, nodes)}
+    else:
+        bl = [float(x) for x in branch_length]
+        first = {}
+        for v, p in enumerate(parent):  # the first child in node order
+            if p != -1 and p not in first:
+                first[p] = v
+        value = {v: 0.0 for v in range(N)}
+        for m in range(N, nodes):  # children have smaller labels
+            value[m] = value[first[m]] + bl[first[m]]
+    return mrca, value
+
+
+def oracle_sum(trees, metric):
+    """trees: [(parent, branch_length or None, weight)] in order -> (S as a list of lists of Python ints (size) or
+    floats (time), W)"""
+    N = (len(trees[0][0]) + 1) // 2
+    S = [[0 if metric == "size" else 0.0 for _ in range(N)] for _ in range(N)]
+    W = 0
+    for parent, bl, w in trees:
+        mrca, value = tree_values(parent, bl, metric)
+        W += int(w)
+        for i in range(N):
+            for j in range(N):
+                if i != j:
+                    if metric == "size":
+                        S[i][j] += int(w) * value[mrca[i][j]]
+                    else:
+                        S[i][j] = S[i][j] + float(int(w)) * value[mrca[i][j]]  # product rounded, then the sum
+    return S, W
+
+
+def oracle_summary(S, W, metric, files, trees):
+    """the stdout of `Relate --mode PairwiseCoalescence`: the off-diagonal mean of S / W summed in row order, the
+    extreme pairs i < j (the first in row order)"""
+    N = len(S)
+    total, lo, hi = 0.0, None, None
+    for i in range(N):
+        for j in range(N):
+            if i == j:
+                continue
+            v = float(S[i][j]) / float(W)
+            total += v
+            if j > i:
+                if lo is None or v < lo[2]:
+                    lo = (i, j, v)
+                if hi is None or v > hi[2]:
+                    hi = (i, j, v)
+    return ["haplotypes %d" % N, "files %d" % files, "trees %d" % trees, "snps %d" % W, "metric %s" % metric,
+            "mean %.17g" % (total / (float(N) * float(N - 1))), "min_pair %d %d %.17g" % lo, "max_pair %d %d %.17g" % hi]
+
+
+def pwc_bytes(S, W, metric):
+    """out.pwc: int32 N, int32 metric, int64 W, N x N sums row-major, little-endian"""
+    a = np.array(S, dtype="<u8" if metric == "size" else "<f8")
+    return (np.array([len(S), 0 if metric == "size" else 1], "<i4").tobytes() + np.array([W], "<i8").tobytes() +
+            a.tobytes())
+
+
+def branch_lengths(N, rng):
+    """positive, not dyadic: a fused multiply-add in the sum would show"""
+    return rng.random(2 * N - 1) * 1000.0 + 0.1
+
+
+def write_anc(path, N, trees, end, ages=None):
+    """trees: [(pos, parent, branch_length or None)]; SNP_begin / SNP_end as BuildTopology leaves them (the tree's
+    position, the next tree's; the last tree's SNP_end = end); ages: sample ages, written if given"""
+    with open(path, "wb") as f:
+        f.write(np.uint8(ages is not None).tobytes() + np.uint32(N).tobytes())
+        if ages is not None:
+            f.write(np.asarray(ages, "<f8").tobytes())
+        f.write(np.uint32(len(trees)).tobytes())
+        for t, (pos, parent, bl) in enumerate(trees):
+            rec = np.zeros(2 * N - 1, ANC_NODE)
+            rec["parent"] = parent
+            if bl is not None:
+                rec["branch_length"] = bl
+            rec["snp_begin"] = pos
+            rec["snp_end"] = trees[t + 1][0] if t + 1 < len(trees) else end
+            f.write(np.int32(pos).tobytes() + rec.tobytes())
+
+
+def read_anc(buf):
+    """bytes of a .anc file without sample ages -> (N, [(pos, parent, branch_length, largest SNP_end)])"""
+    assert buf[0] == 0
+    N, T = [int(x) for x in np.frombuffer(buf, "<u4", 2, 1)]
+    at, out = 9, []
+    for _ in range(T):
+        pos = int(np.frombuffer(buf, "<i4", 1, at)[0])
+        rec = np.frombuffer(buf, ANC_NODE, 2 * N - 1, at + 4)
+        out.append((pos, rec["parent"].astype(np.int32), rec["branch_length"].astype(np.float64), int(rec["snp_end"].max())))
+        at += 4 + 24 * (2 * N - 1)
+    assert at == len(buf)
+    return N, out
+
+
+def file_weights(trees, end):
+    """SNPs each tree of a file covers: to the next tree's position, the last one up to and including `end`"""
+    pos = [t[0] for t in trees]
+    return [(pos[t + 1] if t + 1 < len(pos) else end + 1) - pos[t] for t in range(len(pos))]
+
+
+def shapes(N, rng, randoms=3):
+    """a caterpillar, the caterpillar on the leaves in reverse order, a balanced tree, random trees"""
+    return [caterpillar(N), caterpillar(N, range(N - 1, -1, -1)), balanced(N)] + [random_tree(N, rng) for _ in range(randoms)]

@@ -1,0 +1,184 @@
+"""PairwiseCoalescence on the device (relate_amd/csrc/pairwise_kernels.hip) against the host implementation, bit for
+bit, for both metrics, and end to end on the trees of a PaintBuildTopology run against the oracle of
+pairwise_cases.py.  Every step that uses the GPU is a child process under a time limit of its own; after one that
+was killed, aborted or timed out no further step is started."""
+import os
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+
+import bigtile
+import pairwise_cases as pc
+from golden_util import Fixture
+from relate_amd import api
+
+pytestmark = pytest.mark.gpu
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CLI = os.path.join(ROOT, "relate_amd", "Relate")
+STOP = []  # why no further GPU step may start
+SMALL_N = 1024  # kPairwiseSmallN: above it the kernels run with larger workgroups (256 / 1024 threads, not 64 / 256)
+
+CHILD = """
+import sys, time
+import numpy as np
+sys.path.insert(0, sys.argv[1])
+from relate_amd import api
+z = np.load(sys.argv[2])
+out = {}
+for key, metric in (("size", "size"), ("time", "time"), ("time_again", "time")):
+    t0 = time.perf_counter()
+    out[key], out["W_" + key] = api.pairwise_trees(z["parents"], z["weights"], z["bl"], metric, device=0)
+    out["seconds_" + key] = time.perf_counter() - t0
+np.savez(sys.argv[3], **out)
+"""
+
+CHILD_BAD = """
+import sys
+import numpy as np
+sys.path.insert(0, sys.argv[1])
+from relate_amd import api
+z = np.load(sys.argv[2])
+for metric in ("size", "time"):
+    try:
+        api.pairwise_trees(z["parents"], z["weights"], z["bl"], metric, device=0)
+        print("accepted")
+    except api.RelateError as e:
+        print(metric, e)
+good = np.delete(z["parents"], int(z["bad"]), 0)
+S, W = api.pairwise_trees(good, np.delete(z["weights"], int(z["bad"])), None, "size", device=0)  # the process is healthy
+np.savez(sys.argv[3], S=S, W=W)
+"""
+
+
+def gpu_step(cmd, seconds, **kw):
+    """one GPU step under its own time limit; a step that dies by a signal or runs out of time ends the GPU work of
+    this module"""
+    if STOP:
+        pytest.fail("not started: an earlier GPU step " + STOP[0])
+    try:
+        p = subprocess.run(["timeout", "-k", "10", str(seconds)] + cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE,
+                           **kw)
+    except Exception as e:  # pragma: no cover
+        STOP.append("could not be run: %r" % (e,))
+        raise
+    if p.returncode < 0 or p.returncode in (124, 134, 137, 139):
+        STOP.append("ended with status %d: %s" % (p.returncode, " ".join(cmd[:4])))
+    return p
+
+
+def on_device(tmp_path, parents, weights, bl, seconds=120):
+    src, dst = str(tmp_path / "in.npz"), str(tmp_path / "out.npz")
+    np.savez(src, parents=parents, weights=np.asarray(weights, np.int64), bl=bl)
+    p = gpu_step([sys.executable, "-c", CHILD, ROOT, src, dst], seconds)
+    assert p.returncode == 0, p.stderr.decode()[-3000:]
+    return np.load(dst)
+
+
+def check_against_host(tmp_path, N, parents, weights, bl, key):
+    host_size, W = api.pairwise_trees(parents, weights, None, "size")
+    host_time, _ = api.pairwise_trees(parents, weights, bl, "time")
+    z = on_device(tmp_path, parents, weights, bl)
+    assert z["size"].dtype == np.uint64 and z["time"].dtype == np.float64
+    assert int(z["W_size"]) == int(z["W_time"]) == W
+    assert np.array_equal(z["size"], host_size)
+    assert np.array_equal(z["time"].view(np.uint64), host_time.view(np.uint64))  # equal bits
+    assert np.array_equal(z["time_again"].view(np.uint64), z["time"].view(np.uint64))
+    assert host_time[np.triu_indices(N, 1)].min() > 0
+    bigtile.record("pairwise_coalescence/" + key,
+                   dict(N=N, trees=len(parents), device_call_seconds_size=float(z["seconds_size"]),
+                        device_call_seconds_time=float(z["seconds_time_again"])))
+    return z
+
+
+@pytest.mark.parametrize("N", [2, 3, 63, 64, 65, 257, SMALL_N, SMALL_N + 1])
+def test_device_equals_host(tmp_path, N):
+    """wave-width and workgroup-width edges of the scans, both sides of the switch of workgroup sizes; a caterpillar,
+    its reverse, a balanced tree and random ones, unequal weights with a zero among them"""
+    rng = np.random.default_rng(N)
+    parents = np.stack(pc.shapes(N, rng))
+    bl = np.stack([pc.branch_lengths(N, rng) for _ in parents])
+    check_against_host(tmp_path, N, parents, [7, 1, 0, 1000003, 12, 5], bl, "N%d" % N)
+
+
+def test_many_row_blocks_and_batches_and_the_same_bits_twice(tmp_path):
+    """N = 1500, 40 trees: 500 workgroups of three rows; for `time` a tree takes 54 KB of the 2 MB a batch may, so the
+    trees go up in two batches (38 + 2) and S waits on the device between them; `time` run twice gives the same bits
+    (asserted in check_against_host for every shape, here for the one with the most workgroups)"""
+    N = 1500
+    rng = np.random.default_rng(N)
+    parents = np.stack(pc.shapes(N, rng, randoms=37))
+    assert len(parents) == 40
+    bl = np.stack([pc.branch_lengths(N, rng) for _ in parents])
+    z = check_against_host(tmp_path, N, parents, rng.integers(0, 5000, 40), bl, "N1500_40_trees")
+    assert np.array_equal(z["time_again"].view(np.uint64), z["time"].view(np.uint64))
+
+
+def test_weights_beyond_32_bits(tmp_path):
+    rng = np.random.default_rng(31)
+    parents = np.stack([pc.random_tree(8, rng) for _ in range(3)])
+    bl = np.stack([pc.branch_lengths(8, rng) for _ in range(3)])
+    weights = [2 ** 31, 2 ** 31, 5]
+    want, W = pc.oracle_sum([(p, None, w) for p, w in zip(parents, weights)], "size")
+    assert sum(v > 2 ** 32 for row in want for v in row) > 8
+    z = check_against_host(tmp_path, 8, parents, weights, bl, "weights_64_bit")
+    assert int(z["W_size"]) == W == 2 ** 32 + 5 and [[int(v) for v in row] for row in z["size"]] == want
+
+
+def test_one_bad_tree_among_good_ones(tmp_path):
+    N = 65
+    rng = np.random.default_rng(9)
+    parents = np.stack([pc.random_tree(N, rng) for _ in range(12)])
+    parents[7] = pc.caterpillar(N)
+    bad = parents[7]  # (a view: the batch's tree 7)
+    a, b = 2 * N - 4, 2 * N - 3  # the two internal nodes below the root, a the child of b, trade labels
+    bad[[a, b]] = bad[[b, a]]
+    bad[bad == a], bad[bad == b] = -9, a
+    bad[bad == -9] = b
+    assert bad[b] == a  # parent a of node b: not above its child
+    src, dst = str(tmp_path / "in.npz"), str(tmp_path / "out.npz")
+    np.savez(src, parents=parents, weights=np.arange(1, 13), bl=np.stack([pc.branch_lengths(N, rng) for _ in parents]), bad=7)
+    p = gpu_step([sys.executable, "-c", CHILD_BAD, ROOT, src, dst], 120)
+    assert p.returncode == 0, p.stderr.decode()[-3000:]
+    lines = p.stdout.decode().splitlines()
+    assert len(lines) == 2
+    for metric, line in zip(("size", "time"), lines):
+        assert line.startswith(metric) and "error -1" in line and "tree 7" in line and "node %d" % b in line and "label above" in line
+    z = np.load(dst)
+    host, W = api.pairwise_trees(np.delete(parents, 7, 0), np.delete(np.arange(1, 13), 7))
+    assert int(z["W"]) == W and np.array_equal(z["S"], host)
+
+
+def test_end_to_end_on_built_trees(tmp_path):
+    """PaintBuildTopology of synth24, then PairwiseCoalescence over all its section files on the device and on the
+    host: the same bytes, for `size` the oracle's on the files read back in Python"""
+    work = tmp_path / "run"
+    (work / "out").mkdir(parents=True)
+    fx = Fixture("synth24", work / "out")
+    p = gpu_step([CLI, "--mode", "PaintBuildTopology", "--chunk_index", "0", "-o", "out", "--sum_mode", "exact"], 600,
+                 cwd=str(work))
+    assert p.returncode == 0, p.stderr.decode()[-3000:]
+    files = [str(work / "out" / "chunk_0" / ("out_%d.anc" % w)) for w in range(fx.W)]
+    seq = []
+    for f in files:
+        N, trees = pc.read_anc(open(f, "rb").read())
+        assert N == fx.N
+        seq += [(t[1], t[2], w) for t, w in zip(trees, pc.file_weights(trees, trees[-1][3]))]
+    for metric in ("size", "time"):
+        said = {}
+        for tag, device in (("dev", "0"), ("host", "-1")):
+            p = gpu_step([CLI, "--mode", "PairwiseCoalescence", "-i", ",".join(files), "-o", "%s_%s" % (metric, tag),
+                          "--metric", metric, "--device", device], 120, cwd=str(tmp_path))
+            assert p.returncode == 0, p.stderr.decode()[-3000:]
+            said[tag] = p.stdout.decode()
+        dev = open(str(tmp_path / ("%s_dev.pwc" % metric)), "rb").read()
+        assert dev == open(str(tmp_path / ("%s_host.pwc" % metric)), "rb").read()
+        assert said["dev"] == said["host"]
+        if metric == "size":
+            want, W = pc.oracle_sum(seq, "size")
+            assert dev == pc.pwc_bytes(want, W, "size")
+            assert said["dev"].splitlines() == pc.oracle_summary(want, W, "size", len(files), len(seq))
+            bigtile.record("pairwise_coalescence/synth24_size", dict(N=fx.N, files=len(files), trees=len(seq), snps=W,
+                                                                     mean=said["dev"].splitlines()[5].split()[1]))
