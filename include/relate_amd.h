@@ -583,6 +583,46 @@ int rl_pairwise_trees(const int *parents, const double *branch_length_or_null, c
 int rl_pairwise_anc(const char *const *anc_paths, int npaths, int metric, int device, void *sum_out_or_null,
                     long long *total_weight, int *N_out);
 
+/* --------------------------------------------------------- CopyingMatrix */
+/* The Li-Stephens coancestry ("chunk length") matrix of a painted chunk: C[n][j] = the number of SNPs recipient n is
+ * expected to copy from donor j, from the posterior rows RePaintSection leaves (rl_window_get_topology).  No reference
+ * counterpart in the pipeline (it is the chunk-length matrix of ChromoPainter / fineSTRUCTURE); the definition is the
+ * contract, and the host and the device return equal bits.
+ *   Window w owns the SNPs wb[w] <= s < wb[w+1].  Target n has D rows top[p][0..N-1] there (floats, top[p][n] == 0) at
+ *   the sites site[0] = boundarySNP_begin, the SNPs in between at which n is derived, site[D-1] = boundarySNP_end.
+ *   1. Row weights, doubles, s rising: p = the largest index with site[p] <= s.  s == site[p]: Wt[p] += 1.  Else with
+ *      a = rpos[site[p]], b = rpos[site[p+1]]: a == b: wl = wr = 0.5 (src/anc_builder.cpp:146-153), else
+ *      wl = (b - rpos[s]) / (b - a), wr = (rpos[s] - a) / (b - a); Wt[p] += wl, Wt[p+1] += wr: GetMatrix's
+ *      interpolation between a target's neighbouring rows (src/anc_builder.cpp:130-168), on normalised rows.
+ *   2. Z_p = the sum of (double)top[p][j]: 256 partial sums, partial t over j = t, t + 256, ... rising, then halved,
+ *      x[t] += x[t + h] for t < h, h = 128, 64, .. 1.  A row with Wt[p] != 0 whose Z_p is not finite and positive is
+ *      RL_ESTATE with a message naming window, target and row.
+ *   3. c_p = Wt[p] / Z_p; C[n][j] = C[n][j] + c_p * (double)top[p][j], the product rounded, then the sum (no fused
+ *      multiply-add); p rising within a window, the windows rising; rows with Wt[p] == 0 are skipped.
+ *   C: doubles, row = recipient, column = donor, zero diagonal; W = the SNPs covered; every row of C sums to W up to
+ *   rounding, C / W are the copying shares.
+ *   rl_window_copying: adds one window into a DEVICE buffer of (targets of the context) * N doubles
+ *     (relate_amd/csrc/copying_kernels.hip).  A bounded window (rl_window_open_bounded) is reduced part by part,
+ *     RePaintSection run again as for its matrices, every row once: the bits of the unbounded window.  Afterwards its
+ *     resident rows are the window's last part; its cursors are as before.  kernel_ms (optional): the reduce kernels.
+ *   rl_window_copying_host: the same into a host buffer (copied to the device, added to, copied back).
+ *   rl_copying_matrix: windows w_first .. w_last of a painted context (rl_paint; rl_set_window_range must cover them),
+ *     opened, reduced and closed one after another, each with the posterior rows the free HBM has room for.  C_host:
+ *     (targets of the context) * N doubles, overwritten; *W = wb[w_last+1] - wb[w_first].
+ *   rl_copying_weights_host / rl_copying_rows_host (no GPU): step 1 for one target and window (site[D] rising, the
+ *     window's SNPs [s_begin, s_end)), and steps 2 and 3 on the host for rows [D][N], added to c_row[N]: the twin the
+ *     device is held to.
+ *   rl_stage_copying_matrix: loads the chunk, paints the windows of [first_section, min(last_section, W-1)]
+ *     (rl_set_window_range), reduces them and writes out_path: int32 N, int32 chunk, int32 first_snp, int32 end_snp,
+ *     int64 W, then N*N doubles. */
+int rl_window_copying(rl_window *win, void *d_C, float *kernel_ms);
+int rl_window_copying_host(rl_window *win, double *C_host, float *kernel_ms);
+int rl_copying_matrix(rl_ctx *ctx, int w_first, int w_last, int sum_mode, double *C_host, long long *W);
+int rl_copying_weights_host(const int *site, int D, const double *rpos, int s_begin, int s_end, double *weights);
+int rl_copying_rows_host(const float *rows, const double *weights, int D, int N, double *c_row);
+int rl_stage_copying_matrix(const char *out_dir, int chunk_index, int first_section, int last_section,
+                            const rl_stage_opts *opts, const char *out_path);
+
 /* ------------------------------------------------------------------ tools */
 /* Synthetic block-coalescent panel (stand-in for MakeChunks input,
  * SURVEY.md 8d).  seq_chars (L*N) and/or bits (L*row_words) may be NULL. */

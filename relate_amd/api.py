@@ -73,6 +73,12 @@ def lib():
         L.rl_pairwise_anc.restype = C.c_int
         L.rl_pairwise_anc.argtypes = [C.POINTER(C.c_char_p), C.c_int, C.c_int, C.c_int, C.c_void_p,
                                       C.POINTER(C.c_longlong), C.POINTER(C.c_int)]
+        L.rl_window_copying.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        L.rl_window_copying_host.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        L.rl_copying_matrix.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.POINTER(C.c_longlong)]
+        L.rl_copying_weights_host.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p]
+        L.rl_copying_rows_host.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]
+        L.rl_stage_copying_matrix.argtypes = [C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_char_p]
         _lib = L
     return _lib
 
@@ -255,6 +261,16 @@ class Context:
                                          C.byref(n)))
         return n.value
 
+    def copying_matrix(self, w_first=0, w_last=None, sum_mode=RL_SUM_EXACT):
+        """rl_copying_matrix: the coancestry matrix of windows w_first .. w_last (default: the last) of the painted
+        context -> (C [targets of the context][N] float64, W = SNPs covered)"""
+        k0, k1 = self.target_range()
+        Cm = np.zeros((k1 - k0, self.N), np.float64)
+        W = C.c_longlong(0)
+        _check(lib().rl_copying_matrix(C.c_void_p(self._h), int(w_first), self.W - 1 if w_last is None else int(w_last),
+                                       sum_mode, _p(Cm), C.byref(W)))
+        return Cm, W.value
+
     def open_window(self, w, paint_file=None, first_snp=None, sum_mode=RL_SUM_EXACT, max_rows=0):
         """max_rows > 0: keep at most that many posterior rows resident (rl_window_open_bounded)"""
         return Window(self, w, paint_file, first_snp, sum_mode, max_rows)
@@ -311,6 +327,23 @@ class Window:
         _check(lib().rl_window_matrix(C.c_void_p(self._h), snp, _p(d), C.byref(ms)))
         self.matrix_ms = ms.value
         return d
+
+    def copying(self, Cm=None, device_ptr=None):
+        """rl_window_copying: this window's share of the coancestry matrix, ADDED to Cm ([targets of the context][N]
+        float64, zeros by default) and returned; with device_ptr (a device buffer of that shape, e.g. a torch tensor's
+        data_ptr()) it is added there and nothing crosses PCIe.  copying_ms: the reduce kernels."""
+        ms = C.c_float(0)
+        if device_ptr is not None:
+            _check(lib().rl_window_copying(C.c_void_p(self._h), C.c_void_p(device_ptr), C.byref(ms)))
+            self.copying_ms = ms.value
+            return None
+        k0, k1 = self.ctx.target_range()
+        if Cm is None:
+            Cm = np.zeros((k1 - k0, self.ctx.N), np.float64)
+        assert Cm.dtype == np.float64 and Cm.shape == (k1 - k0, self.ctx.N) and Cm.flags.c_contiguous
+        _check(lib().rl_window_copying_host(C.c_void_p(self._h), _p(Cm), C.byref(ms)))
+        self.copying_ms = ms.value
+        return Cm
 
     def matrix_rows_into(self, snp, device_ptr):
         """the same rows written to a device buffer ((k_end-k_begin)*N floats), e.g. a torch tensor's
@@ -371,6 +404,38 @@ class Builder:
 
     def __del__(self):
         self.close()
+
+
+def copying_weights_host(site, rpos, s_begin, s_end):
+    """rl_copying_weights_host: the row weights of one target in the window that owns the SNPs [s_begin, s_end)"""
+    site = np.ascontiguousarray(site, dtype=np.int32)
+    rpos = np.ascontiguousarray(rpos, dtype=np.float64)
+    wt = np.zeros(len(site), np.float64)
+    _check(lib().rl_copying_weights_host(_p(site), len(site), _p(rpos), int(s_begin), int(s_end), _p(wt)))
+    return wt
+
+
+def copying_rows_host(rows, weights, c_row=None):
+    """rl_copying_rows_host: the host twin of the device's reduction; rows [D][N] float32 -> c_row [N] (added to)"""
+    rows = np.ascontiguousarray(rows, dtype=np.float32)
+    D, N = rows.shape
+    weights = np.ascontiguousarray(weights, dtype=np.float64)
+    assert len(weights) == D
+    c_row = np.zeros(N, np.float64) if c_row is None else c_row
+    _check(lib().rl_copying_rows_host(_p(rows), _p(weights), D, N, _p(c_row)))
+    return c_row
+
+
+def read_cpy(path):
+    """a .cpy file of `Relate --mode CopyingMatrix` -> dict(N, chunk, first_snp, end_snp, W, C [N][N] float64)"""
+    with open(path, "rb") as f:
+        N, chunk, first_snp, end_snp = np.frombuffer(f.read(16), "<i4")
+        W = int(np.frombuffer(f.read(8), "<i8")[0])
+        Cm = np.frombuffer(f.read(), "<f8")
+    if Cm.size != int(N) * int(N):
+        raise RelateError("%s: %d doubles behind the header, %d x %d expected" % (path, Cm.size, N, N))
+    return dict(N=int(N), chunk=int(chunk), first_snp=int(first_snp), end_snp=int(end_snp), W=W,
+                C=Cm.reshape(int(N), int(N)).copy())
 
 
 MATRIX_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.c_void_p)  # rl_matrix_fn / rl_matrix_dev_fn

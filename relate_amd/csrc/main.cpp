@@ -11,6 +11,8 @@
 //           stdout as `key value` lines; with -o, out.cmp: `snp_begin snp_end treeA treeB d` per interval; --device -1:
 //           on the host)
 //   Relate --mode PairwiseCoalescence -i a.anc[,b.anc,...] -o out [--metric size|time] [--device d]
+//   Relate --mode CopyingMatrix --chunk_index c -o out [--first_section a --last_section b] [--painting t,r]
+//          [--sum_mode m] [--device d]
 //          (no reference counterpart: for every pair of haplotypes the size (leaves below) or the time (height) of
 //           their most recent common ancestor, SNP-weighted over the files' trees; out.pwc: int32 N, int32 metric
 //           (0 size, 1 time), int64 W (SNPs), then the N x N sums (uint64 / double) row-major; the summary on stdout
@@ -25,6 +27,8 @@
 #include <sys/resource.h>
 #include <unistd.h>
 
+#include <algorithm>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -46,7 +50,7 @@ static void usage_line() {
   std::cerr << "---------------------------------------------------------" << std::endl << std::endl;
 }
 
-static const char *kModes = "MakeChunks|Paint|BuildTopology|PaintBuildTopology|FindEquivalentBranches|OptimizeParameters|CompareTopology|PairwiseCoalescence";
+static const char *kModes = "MakeChunks|Paint|BuildTopology|PaintBuildTopology|FindEquivalentBranches|OptimizeParameters|CompareTopology|PairwiseCoalescence|CopyingMatrix";
 
 // `Relate --mode OptimizeParameters` (pipeline/OptimizeParameters.cpp:22-206): MakeChunks, then for every chunk the
 // grid of (theta, recombination factor) through rl_stage_optimize_parameters, the temporary files removed as the
@@ -279,6 +283,64 @@ static int pairwise_coalescence(std::map<std::string, std::string> &opt) {
   return 0;
 }
 
+// `Relate --mode CopyingMatrix --chunk_index c -o out [--first_section a --last_section b] [--painting t,r]
+// [--sum_mode m] [--device d]` (rl_stage_copying_matrix): out.cpy and a summary of the copying shares C / W
+static int copying_matrix(const std::string &out, int chunk, int first_section, int last_section, const rl_stage_opts &so) {
+  const std::string path = out + ".cpy";
+  if (rl_stage_copying_matrix(out.c_str(), chunk, first_section, last_section, &so, path.c_str()) != 0) {
+    std::cerr << "Error: " << rl_last_error() << std::endl;
+    return 1;
+  }
+  int32_t head[4] = {0, 0, 0, 0};
+  int64_t W = 0;
+  std::vector<double> C;
+  {
+    FILE *fp = fopen(path.c_str(), "rb");
+    bool ok = fp && fread(head, 4, 4, fp) == 4 && fread(&W, 8, 1, fp) == 1 && head[0] > 0;
+    if (ok) {
+      C.resize((size_t)head[0] * head[0]);
+      ok = fread(C.data(), 8, C.size(), fp) == C.size();
+    }
+    if (fp) fclose(fp);
+    if (!ok) {
+      std::cerr << "Error: cannot read back " << path << std::endl;
+      return 1;
+    }
+  }
+  const int N = head[0];
+  int windows = 0;
+  {  // parameters_c<c>.bin: int32 N, L, W + 1, then the window boundaries
+    FILE *fp = fopen((out + "/parameters_c" + std::to_string(chunk) + ".bin").c_str(), "rb");
+    int32_t h3[3] = {0, 0, 0};
+    if (fp && fread(h3, 4, 3, fp) == 3 && h3[2] > 0) {
+      std::vector<int32_t> wb((size_t)h3[2]);
+      if (fread(wb.data(), 4, wb.size(), fp) == wb.size())
+        for (size_t w = 0; w + 1 < wb.size(); w++) windows += wb[w] >= head[2] && wb[w + 1] <= head[3];
+    }
+    if (fp) fclose(fp);
+  }
+  // shares in row order, sums in double in column order
+  double top = -1.0, worst = 0.0, donors = 0.0;
+  int top_i = -1, top_j = -1;
+  for (int i = 0; i < N; i++) {
+    double rowsum = 0.0, sq = 0.0;
+    for (int j = 0; j < N; j++) {
+      const double c = C[(size_t)i * N + j], share = c / (double)W;
+      rowsum += c;
+      sq += share * share;
+      if (i != j && share > top) top = share, top_i = i, top_j = j;
+    }
+    worst = std::max(worst, std::fabs(rowsum / (double)W - 1.0));
+    donors += 1.0 / sq;
+  }
+  char line[768];
+  snprintf(line, sizeof line,
+           "haplotypes %d\nwindows %d\nsnps %lld\nmax_share %d %d %.17g\nmax_rowsum_error %.17g\nmean_effective_donors %.17g\n",
+           N, windows, (long long)W, top_i, top_j, top, worst, donors / (double)N);
+  std::cout << line;
+  return 0;
+}
+
 int main(int argc, char **argv) {
   // BuildTopology keeps several tree-builder launches and window kernels in flight from its section threads: more
   // hardware queues than HIP's default four (read when the runtime starts; an explicit setting wins) -- but not more
@@ -333,6 +395,7 @@ int main(int argc, char **argv) {
     std::cerr << "Usage: Relate --mode " << kModes << " [--chunk_index c] -o out [options]" << std::endl;
     std::cerr << "  CompareTopology: -i,--input a.anc,b.anc [-o out] [--device d]" << std::endl;
     std::cerr << "  PairwiseCoalescence: -i,--input a.anc[,b.anc,...] -o out [--metric size|time] [--device d]" << std::endl;
+    std::cerr << "  CopyingMatrix: --chunk_index c -o out [--first_section a --last_section b] [--painting theta,rho] [--sum_mode m] [--device d]" << std::endl;
     return opt.count("help") ? 0 : 1;
   }
   const std::string mode = opt["mode"];
@@ -433,6 +496,9 @@ int main(int argc, char **argv) {
   if (opt.count("paint_all_windows")) so.paint_windows = 0;  // (read by PaintBuildTopology alone)
   if (mode == "OptimizeParameters") {
     return optimize_parameters(opt, so);
+  } else if (mode == "CopyingMatrix") {
+    return copying_matrix(out, chunk, opt.count("first_section") ? atoi(opt["first_section"].c_str()) : 0,
+                          opt.count("last_section") ? atoi(opt["last_section"].c_str()) : 1 << 30, so);
   } else if (mode == "Paint") {
     std::cerr << "---------------------------------------------------------" << std::endl;
     std::cerr << "Painting sequences..." << std::endl;

@@ -12,6 +12,7 @@
 #include <numeric>
 
 #include "common.h"
+#include "copying.h"
 
 using namespace rl;
 
@@ -45,6 +46,8 @@ struct rl_window {
   size_t h_place_bytes = 0;
   std::vector<int32_t> b_row, start_row, save_row;  // [nloc]
   int anchor_snp = -1;  // the SNP the kept backward states stand above (the same for all targets), -1: none
+  int part_last = -1;   // the last SNP whose trees the resident rows serve (place_rows)
+  DevBuf d_cw, d_clohi, d_cbad;  // rl_window_copying: the rows' weights, the rows of one launch, the rows it refused
   // RELATE_AMD_TIMING: where the window's wall-clock goes (seconds): choosing rows + uploads, waiting for the context's
   // RePaint turn, the launch until it is through, the matrices' own part (arguments, kernel, wait)
   double t_place = 0, t_turn = 0, t_launch = 0, t_matrix = 0;
@@ -247,6 +250,7 @@ static int place_rows(rl_window *win, int snp, float *kernel_ms) {
       win->row_hi[t] = (int32_t)std::min<int64_t>(D, (int64_t)win->row_lo[t] + extra[t] + 2);
     }
   }
+  win->part_last = part_last;
   int64_t at = 0;
   for (int t = 0; t < nloc; t++) {
     win->slab_off[t] = at;
@@ -796,6 +800,149 @@ int rl_window_matrix_rows_device_ex(rl_window *win, int snp, void *d_rows, const
     return RL_EINVAL;
   }
   return window_matrix(win, snp, nullptr, d_rows, kernel_ms, carriers, val, static_cast<float *>(d_rowmin));
+}
+
+// CopyingMatrix (relate_amd.h): the window's posterior rows, weighted, into the rows of its targets in d_C.
+int rl_window_copying(rl_window *win, void *d_C, float *kernel_ms) {
+  if (!win || !d_C) {
+    set_error("rl_window_copying: bad arguments (null window or device pointer)");
+    return RL_EINVAL;
+  }
+  rl_ctx *ctx = win->ctx;
+  RL_HIP(hipSetDevice(ctx->device));
+  const int N = ctx->N, L = ctx->L, W = ctx->W, w = win->w, nloc = win->nloc, k0 = win->k0;
+  const Plan &pl = ctx->plan;
+  const int s_begin = ctx->wb[w], s_end = ctx->wb[w + 1];
+  const int64_t all_rows = win->top_off[nloc];
+  // ---- step 1 on the host: the weights of every row of the window, and where each target's rows begin to count
+  std::vector<double> wt((size_t)all_rows, 0.0);
+  std::vector<const int32_t *> site(nloc);
+  std::vector<int32_t> plain;  // the visited sites of the targets' slices without the plan's flag bit
+  {
+    plain.resize((size_t)all_rows);
+    for (int t = 0; t < nloc; t++) {
+      const int n = k0 + t;
+      const int32_t *sv = &pl.sites[pl.off[n] + pl.ia[(size_t)n * W + w]];
+      const int D = (int)(win->top_off[t + 1] - win->top_off[t]);
+      int32_t *o = &plain[win->top_off[t]];
+      for (int d = 0; d < D; d++) o[d] = sv[d] & 0x7fffffff;
+      site[t] = o;
+      const int rc = copying_weights(o, D, ctx->rpos.data(), s_begin, s_end, &wt[win->top_off[t]]);
+      if (rc) {
+        set_error("rl_window_copying: window %d, target %d: %s", w, n, std::string(rl_last_error()).c_str());
+        return rc;
+      }
+    }
+  }
+  int rc = win->d_cw.upload(wt);
+  rc = rc ? rc : win->d_clohi.alloc((size_t)nloc * 8);
+  std::vector<int32_t> bad(nloc, 0), lohi((size_t)2 * nloc);
+  rc = rc ? rc : win->d_cbad.upload(bad);
+  if (rc) return rc;
+  hipEvent_t e0 = nullptr, e1 = nullptr;
+  if (hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess) {
+    if (e0) (void)hipEventDestroy(e0);
+    set_error("rl_window_copying: event creation failed");
+    return RL_EHIP;
+  }
+  float ms_total = 0.f;
+  // the rows [lo, hi) of every target that are resident now and have not been reduced: one launch
+  std::vector<int32_t> done(nloc, 0);
+  auto reduce_resident = [&]() -> int {
+    for (int t = 0; t < nloc; t++) {
+      lohi[t] = std::max(win->row_lo[t], done[t]);
+      lohi[(size_t)nloc + t] = win->row_hi[t];
+      done[t] = std::max(done[t], win->row_hi[t]);
+    }
+    CopyingParams p;
+    p.lay = ctx->lay;
+    p.N = N;
+    p.S = ctx->S;
+    p.waves = ctx->waves;
+    p.nloc = nloc;
+    p.topology = win->d_top.as<float>();
+    p.top_off = win->d_top_off.as<int64_t>();
+    p.slab_base = reinterpret_cast<const int64_t *>(win->d_place.as<unsigned char>() + (size_t)nloc * 8);
+    p.row_lo = win->d_clohi.as<int32_t>();
+    p.row_hi = p.row_lo + nloc;
+    p.weights = win->d_cw.as<double>();
+    p.C = static_cast<double *>(d_C);
+    p.bad_row = win->d_cbad.as<int32_t>();
+    std::lock_guard<std::mutex> s0_is_mine(ctx->repaint_mutex);
+    RL_HIP(hipMemcpyAsync(win->d_clohi.p, lohi.data(), (size_t)nloc * 8, hipMemcpyHostToDevice, ctx->s0));
+    RL_HIP(hipEventRecord(e0, ctx->s0));
+    RL_HIP(launch_copying(p, ctx->s0));
+    RL_HIP(hipEventRecord(e1, ctx->s0));
+    RL_HIP(hipEventSynchronize(e1));  // (lohi is rewritten by the next part)
+    float ms = 0.f;
+    (void)hipEventElapsedTime(&ms, e0, e1);
+    ms_total += ms;
+    return RL_OK;
+  };
+  std::vector<int32_t> first_lo(nloc, 0);
+  if (win->cap_rows >= all_rows) {
+    rc = reduce_resident();
+  } else {
+    // A bounded window, part by part as the tree builder would move through it: the rows from the cursors at `snp`
+    // (the row of the largest site <= snp) up to two past the derived sites of the part are resident (place_rows);
+    // what an earlier part reduced is left out, so every row is reduced once, rows and windows in rising order --
+    // the bits of the whole window.  The cursors of the caller are put back; the resident part is the window's last.
+    const std::vector<int32_t> cursors = win->v_snp_prev;
+    bool first = true;
+    for (int snp = s_begin; snp < s_end && !rc; snp = win->part_last + 1) {
+      for (int t = 0; t < nloc; t++) {
+        const int D = (int)(win->top_off[t + 1] - win->top_off[t]);
+        int c = 0;
+        while (c + 1 < D && site[t][c + 1] <= snp) c++;
+        win->v_snp_prev[t] = c;
+      }
+      rc = place_rows(win, snp, nullptr);
+      if (first)
+        for (int t = 0; t < nloc; t++) first_lo[t] = win->row_lo[t];
+      first = false;
+      rc = rc ? rc : reduce_resident();
+    }
+    win->v_snp_prev = cursors;
+    for (int t = 0; t < nloc && !rc; t++) {
+      const int D = (int)(win->top_off[t + 1] - win->top_off[t]);
+      for (int d = 0; d < D; d++)
+        if (wt[win->top_off[t] + d] != 0.0 && (d < first_lo[t] || d >= done[t])) {
+          set_error("rl_window_copying: window %d, target %d: row %d has a weight and was in no part of the window", w,
+                    k0 + t, d);
+          rc = RL_ESTATE;
+          break;
+        }
+    }
+  }
+  (void)hipEventDestroy(e0);
+  (void)hipEventDestroy(e1);
+  if (rc) return rc;
+  RL_HIP(hipMemcpy(bad.data(), win->d_cbad.p, (size_t)nloc * 4, hipMemcpyDeviceToHost));
+  for (int t = 0; t < nloc; t++)
+    if (bad[t]) {
+      set_error("CopyingMatrix: window %d, target %d, row %d: the posterior row has a weight and its sum is not finite "
+                "and positive", w, k0 + t, bad[t] - 1);
+      return RL_ESTATE;
+    }
+  (void)L;
+  if (kernel_ms) *kernel_ms = ms_total;
+  return RL_OK;
+}
+
+int rl_window_copying_host(rl_window *win, double *C_host, float *kernel_ms) {
+  if (!win || !C_host) {
+    set_error("rl_window_copying_host: bad arguments (null window or matrix)");
+    return RL_EINVAL;
+  }
+  RL_HIP(hipSetDevice(win->ctx->device));
+  const size_t bytes = (size_t)win->nloc * win->ctx->N * sizeof(double);
+  DevBuf d_C;
+  int rc = d_C.alloc(bytes);
+  if (rc) return rc;
+  RL_HIP(hipMemcpy(d_C.p, C_host, bytes, hipMemcpyHostToDevice));
+  if ((rc = rl_window_copying(win, d_C.p, kernel_ms))) return rc;
+  RL_HIP(hipMemcpy(C_host, d_C.p, bytes, hipMemcpyDeviceToHost));
+  return RL_OK;
 }
 
 }  // extern "C"
