@@ -1,7 +1,9 @@
 """The oracle of the PairwiseCoalescence tests (test_pairwise_cpu.py, test_pairwise_gpu.py).  Nothing here calls the
 library: the definition of include/relate_amd.h is restated with Python sets, ints and floats -- the ancestors of
 every leaf, the MRCA of two leaves as the smallest label among their common ancestors (labels rise towards the root),
-sizes by counting leaves, heights by the first-child recursion, sums in tree order."""
+sizes by counting leaves, heights by the first-child recursion, sums in tree order.  That oracle is O(N^3);
+reference_sum is the same definition in numpy for the sizes the device promises (N <= 10,240), held to the oracle at
+small N in test_pairwise_cpu.py."""
 import numpy as np
 
 from compare_cases import ANC_NODE, balanced, caterpillar, random_tree  # noqa: F401  (the tests' tree shapes)
@@ -51,6 +53,55 @@ def oracle_sum(trees, metric):
                     else:
                         S[i][j] = S[i][j] + float(int(w)) * value[mrca[i][j]]  # product rounded, then the sum
     return S, W
+
+
+def reference_sum(trees, metric, N):
+    """the same sums in numpy, affordable at N = 10,240 (a few seconds per tree), and not by the library's algorithm
+    (depth-first ranks and running maxima): the internal nodes in label order, children first; every live node keeps
+    the indices of the leaves below it; node m with the children a < b (node order) is the MRCA of exactly the pairs
+    A x B, so w * value(m) is added to S[A, B] and S[B, A] -- the product formed first, then one addition per element
+    and tree, in tree order: the floats carry the bits of oracle_sum.
+    trees: [(parent, branch_length or None, weight)] -> (S [N][N] uint64 (size) or float64 (time), W)"""
+    assert metric in ("size", "time")
+    S = np.zeros((N, N), np.uint64 if metric == "size" else np.float64)
+    W = 0
+    for parent, bl, w in trees:
+        parent = np.asarray(parent, np.int64)
+        assert parent.shape == (2 * N - 1,) and parent[-1] == -1 and (parent[:-1] > np.arange(2 * N - 2)).all()
+        # sorted by parent, ties in node order: behind the root, the two children of N, of N + 1, ...
+        kids = np.argsort(parent, kind="stable")[1:].reshape(N - 1, 2)
+        assert np.array_equal(parent[kids], np.repeat(np.arange(N, 2 * N - 1), 2).reshape(N - 1, 2))
+        W += int(w)
+        below = {}  # live node -> the leaves below it
+        h = [0.0] * (2 * N - 1)
+        for m in range(N, 2 * N - 1):
+            a, b = int(kids[m - N, 0]), int(kids[m - N, 1])
+            A = below.pop(a) if a >= N else np.array([a])
+            B = below.pop(b) if b >= N else np.array([b])
+            if metric == "size":
+                add = np.uint64(int(w) * (len(A) + len(B)))
+            else:
+                h[m] = h[a] + float(bl[a])  # the first child in node order
+                add = np.float64(float(int(w))) * np.float64(h[m])
+            S[np.ix_(A, B)] += add
+            S[np.ix_(B, A)] += add
+            below[m] = np.concatenate((A, B))
+        assert list(below) == [2 * N - 2] and len(below[2 * N - 2]) == N
+    return S, W
+
+
+LARGE_WEIGHTS = [3, 2 ** 32 + 7, 0, 11]  # of large_case: one above 2^32, a zero
+
+
+def large_case(N, balanced_too=True):
+    """the input of the tests at the sizes only reference_sum affords: a caterpillar, its reverse, a balanced tree
+    (weight 0) and one random tree -> (parents [T][2N-1], weights [T], branch lengths [T][2N-1]); without the
+    balanced tree the zero weight goes with it"""
+    rng = np.random.default_rng(N)
+    keep = [0, 1, 2, 3] if balanced_too else [0, 1, 3]
+    parents = np.stack(shapes(N, rng, randoms=1))[keep]
+    bl = np.stack([branch_lengths(N, rng) for _ in range(4)])[keep]
+    return parents, [LARGE_WEIGHTS[k] for k in keep], bl
 
 
 def oracle_summary(S, W, metric, files, trees):

@@ -70,6 +70,92 @@ def test_two_wavefronts_per_target(tmp_path):
     ctx.close()
 
 
+INSTANTIATIONS = (1, 2, 4, 8, 12, 16, 20, 24, 32, 40)  # launch_copying: copying_reduce_kernel<K> takes N <= 256 K
+# the largest N of every instantiation (a full tile: each thread owns a real column in every slot) and the smallest of
+# the next; 5120 / 5121 is also the switch from one wavefront per target to two in the painting layout
+EDGES = [256 * K + d for K in INSTANTIATIONS for d in (0, 1) if 256 * K + d <= 10240]
+# N = 256 K has rem == 0 and 256 K + 1 has rem == 1 in the painting layout (q = N / lanes, rem = N % lanes, 64 or 128
+# lanes): the largest remainders, one and two wavefronts, and q + 1 = 80 = the largest register tile
+LARGEST_REM = [4095, 8191, 10239]
+ENDS = 16  # recipients painted at either end of the panel
+
+
+def edge_chunk(N):
+    from test_edge_gpu import random_chunk
+    return random_chunk(N, 70, 0.15, seed=5, wb=[0, 30, 70])
+
+
+def reduce_of_the_windows_own_rows(ch, k0, k1):
+    """The reduce kernel alone: the recipients k0 .. k1-1 painted on the device, and per window the device's
+    win.copying() against cc.reduce_rows (numpy) of the posterior rows the SAME window hands out through
+    win.topology(n) -- host code that undoes the [wave][register][lane] layout, held to the oracle in
+    test_window_gpu.py -- with the weights of cc.row_weights on the oracle's boundary SNPs.  Both windows go into
+    one matrix, so the second launch starts from the C the first one left.  Window.topology and Window.rows take
+    the GLOBAL index of the recipient under a target range; win.copying() returns the context's rows.
+    -> (C [k1-k0][N], layout (tile, waves))"""
+    o = rlutil.oracle()
+    ctx = api.Context()
+    ctx.set_chunk(ch.seq, ch.r, ch.rpos, ch.wb)
+    ctx.set_target_range(k0, k1)
+    ctx.paint(api.RL_SUM_EXACT)
+    layout = (ctx.tile, ctx.waves)
+    want = np.zeros((k1 - k0, ch.N), np.float64)
+    got = None
+    for w in range(ch.W):
+        win = ctx.open_window(w, None, None, api.RL_SUM_EXACT)
+        for i, n in enumerate(range(k0, k1)):
+            top, _ = win.topology(n)
+            bb, be = cc.plan_bounds(o, ch, n)
+            site = cc.row_sites(ch, n, bb[w], be[w])
+            assert top.shape == (len(site), ch.N) and not top[:, n].any(), (w, n)  # the own-donor slot is pinned to 0
+            cc.reduce_rows(top, cc.row_weights(site, ch.rpos, ch.wb[w], ch.wb[w + 1]), want[i])
+        got = win.copying(got)
+        win.close()
+        assert got.shape == want.shape and np.array_equal(cc.bits(got), cc.bits(want)), (w, np.abs(got - want).max())
+    ctx.close()
+    return got, layout
+
+
+@pytest.mark.parametrize("N", EDGES + LARGEST_REM)
+def test_every_instantiation_at_both_of_its_edges(tmp_path, N):
+    """Every K of launch_copying at its largest and its smallest N (N = 256 K: rem == 0 in the layout, every thread
+    owns a real column in every slot; 256 K + 1: one column in the last slot, rem == 1), either side of the one-wave /
+    two-wave switch of the layout, N = 10,240, and three sizes with the largest remainder.  The first and the last 16
+    recipients: the pinned own-donor entry falls in the first lane of the first wavefront and in the last lane of
+    the last.  The yardstick is
+    reduce_of_the_windows_own_rows; at N = 257, 2049 and 5121 (one wavefront with a short and a long tile, two
+    wavefronts) the result is also held to the full oracle route -- the oracle's own painting and RePaint of every
+    target -- restricted to these recipients."""
+    ch = edge_chunk(N)
+    ranges = [(0, ENDS), (N - ENDS, N)]
+    rows, layouts = zip(*[reduce_of_the_windows_own_rows(ch, k0, k1) for k0, k1 in ranges])
+    assert layouts[0] == layouts[1] and layouts[0][1] == (1 if N <= 5120 else 2), layouts
+    got = np.concatenate(rows)
+    targets = [n for k0, k1 in ranges for n in range(k0, k1)]
+    for i, n in enumerate(targets):
+        assert cc.bits(got[i, n:n + 1])[0] == 0, (n, got[i, n])  # +0.0 on the diagonal
+    rel = np.abs(np.array([sum(float(v) for v in got[i]) for i in range(len(targets))]) / ch.L - 1.0)
+    assert rel.max() <= 1e-10, rel.max()
+    assert got.min() >= 0.0 and (got > 0.0).sum(axis=1).min() >= 1
+    if N in (257, 2049, 5121):
+        oracle_paint(ch, str(tmp_path))
+        want = np.zeros((len(targets), N), np.float64)
+        for w in range(ch.W):
+            ow = cc.OracleWindow(ch, os.path.join(str(tmp_path), "relate_%d.bin" % w), w)
+            cc.add_window(ow, want, targets)
+            ow.close()
+        assert np.array_equal(cc.bits(got), cc.bits(want)), np.abs(got - want).max()
+
+
+def test_one_haplotype_too_many_has_no_layout():
+    """N = 10,241: refused when the chunk is set, before any CopyingMatrix kernel could be asked for it"""
+    ch = edge_chunk(10241)
+    ctx = api.Context()
+    with pytest.raises(api.RelateError, match="exceeds the largest"):
+        ctx.set_chunk(ch.seq, ch.r, ch.rpos, ch.wb)
+    ctx.close()
+
+
 def test_bounded_window_has_the_bits_of_the_whole_one(tmp_path):
     ch = rlutil.synth_chunk(96, 1400, seed=9, budget=60000)
     ctx = api.Context()

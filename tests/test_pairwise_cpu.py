@@ -48,6 +48,34 @@ def test_sums_against_the_oracle(N, metric):
     assert w0 == 0 and not none.any()
 
 
+@pytest.mark.parametrize("metric", METRICS)
+@pytest.mark.parametrize("N", [2, 3, 9, 40])
+def test_reference_equals_the_oracle(N, metric):
+    """the numpy reference of the large device tests against the Python-set oracle, element by element"""
+    trees = case(N, N)
+    want, W = pc.oracle_sum(trees, metric)
+    S, gotW = pc.reference_sum(trees, metric, N)
+    assert S.dtype == (np.uint64 if metric == "size" else np.float64) and S.shape == (N, N)
+    assert gotW == W and S.tolist() == want  # equal, not close
+    big = [(t[0], t[1], w) for t, w in zip(trees, (2 ** 31, 2 ** 33 + 1, 5))]  # sums beyond 32 bits
+    S, gotW = pc.reference_sum(big, metric, N)
+    want, W = pc.oracle_sum(big, metric)
+    assert gotW == W and S.tolist() == want
+
+
+@pytest.mark.parametrize("metric", METRICS)
+@pytest.mark.parametrize("N", [1537, 3511])
+def test_host_equals_the_reference(N, metric):
+    """the host implementation above toy size against something that does not share its design: four and seven rows
+    per row block, a caterpillar, its reverse, a balanced tree and a random one, a zero weight and one above 2^32"""
+    trees = list(zip(*[pc.large_case(N)[k] for k in (0, 2, 1)]))  # (parent, branch_length, weight)
+    want, W = pc.reference_sum(trees, metric, N)
+    S, gotW = call(trees, metric)
+    assert gotW == W == sum(pc.LARGE_WEIGHTS) > 2 ** 32
+    assert S.dtype == want.dtype and np.array_equal(S.view(np.uint64), want.view(np.uint64))  # equal bits
+    assert np.array_equal(S, S.T) and not S.diagonal().any()
+
+
 def test_weights_beyond_32_bits():
     """w * N summed over trees passes 2^32: 32-bit accumulators are wrong"""
     rng = np.random.default_rng(31)

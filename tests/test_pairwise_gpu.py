@@ -53,6 +53,36 @@ np.savez(sys.argv[3], S=S, W=W)
 """
 
 
+CHILD_ONE = """
+import sys, time
+import numpy as np
+sys.path.insert(0, sys.argv[1])
+from relate_amd import api
+z = np.load(sys.argv[2])
+t0 = time.perf_counter()
+S, W = api.pairwise_trees(z["parents"], z["weights"], z["bl"], sys.argv[4], device=0)
+seconds = time.perf_counter() - t0
+np.save(sys.argv[3], S)
+print(W, seconds)
+"""
+
+CHILD_TOO_LARGE = """
+import sys
+import numpy as np
+sys.path.insert(0, sys.argv[1])
+from relate_amd import api
+z = np.load(sys.argv[2])
+for metric in ("size", "time"):
+    try:
+        api.pairwise_trees(z["parents"], z["weights"], z["bl"], metric, device=0)
+        print("accepted")
+    except api.RelateError as e:
+        print(metric, e)
+S, W = api.pairwise_trees(z["small"], z["weights"], z["small_bl"], "time", device=0)  # the process is healthy
+np.savez(sys.argv[3], S=S, W=W)
+"""
+
+
 def gpu_step(cmd, seconds, **kw):
     """one GPU step under its own time limit; a step that dies by a signal or runs out of time ends the GPU work of
     this module"""
@@ -74,7 +104,8 @@ def on_device(tmp_path, parents, weights, bl, seconds=120):
     np.savez(src, parents=parents, weights=np.asarray(weights, np.int64), bl=bl)
     p = gpu_step([sys.executable, "-c", CHILD, ROOT, src, dst], seconds)
     assert p.returncode == 0, p.stderr.decode()[-3000:]
-    return np.load(dst)
+    z = np.load(dst)
+    return {k: z[k] for k in z.files}  # (read once: a matrix is 300 MB at N = 6146)
 
 
 def check_against_host(tmp_path, N, parents, weights, bl, key):
@@ -114,6 +145,81 @@ def test_many_row_blocks_and_batches_and_the_same_bits_twice(tmp_path):
     bl = np.stack([pc.branch_lengths(N, rng) for _ in parents])
     z = check_against_host(tmp_path, N, parents, rng.integers(0, 5000, 40), bl, "N1500_40_trees")
     assert np.array_equal(z["time_again"].view(np.uint64), z["time"].view(np.uint64))
+
+
+@pytest.mark.parametrize("N", [1537, 3510, 3511, 4098, 6146])
+def test_device_equals_the_reference_across_the_lds_switches(tmp_path, N):
+    """The sizes at which the launchers change route, against pairwise_cases.reference_sum (numpy, no ranks and no
+    running maxima) over the whole matrix, bit for bit, and against the host implementation.  Dynamic LDS above 48 KB
+    is asked for with hipFuncSetAttribute: `time` accumulate (14 N bytes) from N = 3511, `time` prepare (12 (N-1))
+    from 4098, `size` accumulate (8 N) from 6145 and `size` prepare (8 (N-1)) from 6146.  1537: the smallest N with
+    four rows per workgroup, the last workgroup a partial one (1 row); 3510 / 3511: either side of the first switch;
+    6146: all four kernels above it, 13 rows per workgroup.  Below: test_device_equals_host.  A caterpillar, its
+    reverse, a balanced tree with weight 0 and a random tree; one weight above 2^32."""
+    parents, weights, bl = pc.large_case(N)
+    rows = (N + 511) // 512
+    assert (N + rows - 1) // rows * rows != N  # a partial last workgroup
+    z = check_against_host(tmp_path, N, parents, weights, bl, "N%d" % N)
+    trees = list(zip(parents, bl, weights))
+    for metric in ("size", "time"):
+        want, W = pc.reference_sum(trees, metric, N)
+        assert int(z["W_" + metric]) == W == sum(weights)
+        assert z[metric].dtype == want.dtype and np.array_equal(z[metric].view(np.uint64), want.view(np.uint64))
+        del want
+
+
+def test_device_equals_the_reference_at_the_documented_maximum(tmp_path):
+    """N = 10,240, the largest the device takes: 20 rows per workgroup, 140 KB of LDS in a workgroup of 1024 threads
+    (`time`), the root's size N = 10,240 and internal labels up to 10,238 in 16 bits.  Both caterpillars (the deepest
+    trees: every boundary of the rank scans has another owner) and a random tree, one weight above 2^32, against
+    reference_sum over the whole matrix, bit for bit.  A matrix is 839 MB: one metric at a time, each in a device
+    process of its own, freed before the next; no host-twin comparison and no second `time` run here (the sizes
+    below have them, and the zero weight).  The test is dominated by the reference on the CPU, about 3 s per tree
+    and metric, 15 to 20 s in all; the device calls are recorded, not asserted on."""
+    N = 10240
+    parents, weights, bl = pc.large_case(N, balanced_too=False)
+    assert len(parents) == 3 and max(weights) > 2 ** 32
+    trees = list(zip(parents, bl, weights))
+    src = str(tmp_path / "in.npz")
+    np.savez(src, parents=parents, weights=np.asarray(weights, np.int64), bl=bl)
+    seconds = {}
+    for metric in ("size", "time"):
+        dst = str(tmp_path / (metric + ".npy"))
+        p = gpu_step([sys.executable, "-c", CHILD_ONE, ROOT, src, dst, metric], 180)
+        assert p.returncode == 0, p.stderr.decode()[-3000:]
+        gotW, seconds[metric] = p.stdout.decode().split()
+        got = np.load(dst)
+        os.remove(dst)
+        want, W = pc.reference_sum(trees, metric, N)
+        assert int(gotW) == W == sum(weights)
+        assert got.dtype == want.dtype and got.shape == (N, N)
+        assert np.array_equal(got.view(np.uint64), want.view(np.uint64))
+        if metric == "size":
+            # leaves 0 and N-1 meet at the root of both caterpillars: the size 10,240 is among the values added
+            assert N * (weights[0] + weights[1]) + 2 * weights[2] <= int(got[0, N - 1]) <= int(got.max()) <= N * W
+        del got, want
+    bigtile.record("pairwise_coalescence/N10240", dict(N=N, trees=len(parents), device_call_seconds_size=float(seconds["size"]),
+                                                       device_call_seconds_time=float(seconds["time"])))
+
+
+def test_one_leaf_too_many_is_refused(tmp_path):
+    """N = 10,241: the device route returns RL_EINVAL (labels, ranks and sizes are 16-bit and the LDS is full) and
+    says what it takes; the process computes a small case correctly afterwards"""
+    N, n = 10241, 65
+    rng = np.random.default_rng(N)
+    small, small_bl = pc.random_tree(n, rng), pc.branch_lengths(n, rng)
+    src, dst = str(tmp_path / "in.npz"), str(tmp_path / "out.npz")
+    np.savez(src, parents=pc.caterpillar(N)[None], weights=np.array([5], np.int64), bl=pc.branch_lengths(N, rng)[None],
+             small=small[None], small_bl=small_bl[None])
+    p = gpu_step([sys.executable, "-c", CHILD_TOO_LARGE, ROOT, src, dst], 120)
+    assert p.returncode == 0, p.stderr.decode()[-3000:]
+    lines = p.stdout.decode().splitlines()
+    assert len(lines) == 2
+    for metric, line in zip(("size", "time"), lines):
+        assert line.startswith(metric) and "error -1" in line and "2 <= N <= 10240" in line and "N=10241" in line, line
+    z = np.load(dst)
+    want, W = pc.reference_sum([(small, small_bl, 5)], "time", n)
+    assert int(z["W"]) == W == 5 and np.array_equal(z["S"].view(np.uint64), want.view(np.uint64))
 
 
 def test_weights_beyond_32_bits(tmp_path):

@@ -16,6 +16,11 @@ input (profiles/pairwise_coalescence.json).
         rewritten after every (N, metric).
     python tools/pairwise_measure.py timing N metric OUT.json [trees reps]
     python tools/pairwise_measure.py kernels N metric [trees]
+
+The device == host assert of `timing` is a guard of the measurement (random trees, the host twin shares the device's
+design).  What decides whether the device is right at these sizes is tests/test_pairwise_gpu.py:
+test_device_equals_the_reference_across_the_lds_switches and ..._at_the_documented_maximum (N = 10,240, caterpillars
+too, against the independent numpy reference of tests/pairwise_cases.py).
 """
 import glob
 import json
