@@ -35,6 +35,34 @@ inline int timing_level() {
     }                                                                             \
   } while (0)
 
+// makes `device` the calling thread's device.  RL_OK, or the message set: RL_ENODEVICE (none usable; `who` asked for
+// one that is not there) or RL_EHIP
+inline int select_device(const char *who, int device) {
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) {
+    (void)hipGetLastError();
+    set_error("no usable HIP device");
+    return RL_ENODEVICE;
+  }
+  if (device >= ndev) {
+    set_error("%s: device %d of %d", who, device, ndev);
+    return RL_ENODEVICE;
+  }
+  RL_HIP(hipSetDevice(device));
+  return RL_OK;
+}
+
+// launches kernel<<<grid, block, dyn, stream>>>(args...); dynamic LDS above 48 KB has to be asked for first
+template <class... P, class... A>
+inline hipError_t launch_with_lds(void (*kernel)(P...), int grid, int block, size_t dyn, hipStream_t stream, A... args) {
+  if (dyn > 48 * 1024) {
+    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn);
+    if (e != hipSuccess) return e;
+  }
+  hipLaunchKernelGGL(kernel, dim3(grid), dim3(block), dyn, stream, args...);
+  return hipGetLastError();
+}
+
 // Streams of the stage, three priorities.  LOWEST: the tree builder's resident workers -- the runtime maps the
 // priorities to hardware queues of their own, so nothing queues up behind a launch that lasts for seconds.  HIGHEST:
 // the streams of the sections (a window's distance matrices; a builder's penalty, prior, weave and pair scan) -- a

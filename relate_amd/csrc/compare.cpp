@@ -26,61 +26,30 @@
 
 #include "anc_file.h"
 #include "common.h"
+#include "tree_host.h"
 
 namespace rl {
 
 int compare_trees_device(const int *parentsA, int treesA, const int *parentsB, int treesB, int N, int npairs,
                          const int *pairs, int device, int *out);  // compare_kernels.hip
 
-// the shape every tree of this library has (MinMatch numbers a merged cluster after its parts): binary, leaves
-// 0..N-1, parent[v] > v, root 2N-2.  0, or the first node that breaks the rule + 1.  (pairwise.cpp uses it as well.)
-int first_bad_node(const int *parent, int N, std::vector<unsigned char> &kids) {
-  const int nodes = 2 * N - 1;
-  kids.assign((size_t)nodes, 0);
-  for (int v = 0; v < nodes - 1; v++) {
-    const int p = parent[v];
-    if (!(p > v && p >= N && p < nodes) || ++kids[p] > 2) return v + 1;
-  }
-  if (parent[nodes - 1] != -1) return nodes;
-  for (int v = N; v < nodes; v++)
-    if (kids[v] != 2) return v + 1;
-  return 0;
-}
-
-static int refuse_tree(const char *which, int index, const int *parent, int N) {
-  std::vector<unsigned char> kids;
-  const int bad = first_bad_node(parent, N, kids);
-  const int v = bad - 1;
-  if (bad == 0) set_error("rl_compare_trees: tree %d of %s was refused by the device and not by the host", index, which);
-  else if (v == 2 * N - 2) set_error("rl_compare_trees: tree %d of %s: node %d is not the root (parent %d, expected -1) or has not two children", index, which, v, parent[v]);
-  else if (parent[v] <= v) set_error("rl_compare_trees: tree %d of %s: parent %d of node %d does not have a label above its child's", index, which, parent[v], v);
-  else set_error("rl_compare_trees: tree %d of %s: node %d (parent %d) does not fit a binary tree on %d leaves", index, which, v, parent[v], N);
-  return RL_EINVAL;
+static int refuse_side(const char *which, int index, const int *parent, int N) {
+  char tree[64];
+  snprintf(tree, sizeof tree, "rl_compare_trees: tree %d of %s", index, which);
+  return refuse_tree(tree, parent, N);
 }
 
 // Day's algorithm for one tree A against any number of trees B
-struct HostComparer {
-  int N, nodes;
-  std::vector<int> size, lo, first, second, table, sz, mn, mx;
-  std::vector<unsigned char> kids;
-  explicit HostComparer(int n) : N(n), nodes(2 * n - 1), size(nodes), lo(nodes), first(nodes), second(nodes), table(n), sz(nodes), mn(nodes), mx(nodes) {}
+struct HostComparer : TreeTables {
+  std::vector<int> table, sz, mn, mx;
+  explicit HostComparer(int n) : TreeTables(n), table(n), sz(nodes), mn(nodes), mx(nodes) {}
 
   // ranks and the interval table of A; parent must have passed first_bad_node
   void set_reference(const int *parent) {
-    std::fill(first.begin(), first.end(), -1);
-    for (int v = 0; v < nodes; v++) size[v] = v < N ? 1 : 0;
-    for (int v = 0; v < nodes - 1; v++) {  // label order: a node is complete before its parent reads it
-      const int p = parent[v];
-      size[p] += size[v];
-      if (first[p] == -1) first[p] = v;
-      else second[p] = v;
-    }
+    fill(parent);
     std::fill(table.begin(), table.end(), -1);
-    lo[nodes - 1] = 0;
-    for (int p = nodes - 1; p >= N; p--) {  // falling order: a parent hands the left ends down
+    for (int p = N; p < nodes; p++) {
       const int a = first[p], b = second[p];
-      lo[a] = lo[p];
-      lo[b] = lo[p] + size[a];
       if (a >= N) table[lo[a] + size[a] - 1] = lo[a];       // first child, stored at r: holds l
       if (b >= N) table[lo[b]] = lo[b] + size[b] - 1;       // second child, stored at l: holds r
     }
@@ -115,11 +84,11 @@ static int compare_trees_host(const int *parentsA, const int *parentsB, int N, i
     const int a = pairs[2 * k], b = pairs[2 * k + 1];
     const int *pa = parentsA + (size_t)a * nodes, *pb = parentsB + (size_t)b * nodes;
     if (a != held) {
-      if (first_bad_node(pa, N, hc.kids)) return refuse_tree("A", a, pa, N);
+      if (first_bad_node(pa, N, hc.kids)) return refuse_side("A", a, pa, N);
       hc.set_reference(pa);
       held = a;
     }
-    if (first_bad_node(pb, N, hc.kids)) return refuse_tree("B", b, pb, N);
+    if (first_bad_node(pb, N, hc.kids)) return refuse_side("B", b, pb, N);
     out[k] = hc.distance(pb);
   }
   return RL_OK;
@@ -152,7 +121,7 @@ extern "C" int rl_compare_trees(const int *parentsA, const int *parentsB, int N,
     if (out[k] < 0) {
       const bool isA = out[k] == -1;
       const int t = pairs[2 * k + (isA ? 0 : 1)];
-      return refuse_tree(isA ? "A" : "B", t, (isA ? parentsA : parentsB) + (size_t)t * ((size_t)2 * N - 1), N);
+      return refuse_side(isA ? "A" : "B", t, (isA ? parentsA : parentsB) + (size_t)t * ((size_t)2 * N - 1), N);
     }
   return RL_OK;
 }
@@ -204,10 +173,9 @@ extern "C" int rl_compare_anc(const char *ancA, const char *ancB, int device, rl
       at = next;
     }
   }
-  const size_t nodes = (size_t)2 * N - 1;
-  std::vector<int> pa(A.trees.size() * nodes), pb(B.trees.size() * nodes), pairs(iv.size() * 2), d(iv.size());
-  for (size_t t = 0; t < A.trees.size(); t++) memcpy(&pa[t * nodes], A.trees[t].parent.data(), nodes * sizeof(int));
-  for (size_t t = 0; t < B.trees.size(); t++) memcpy(&pb[t * nodes], B.trees[t].parent.data(), nodes * sizeof(int));
+  std::vector<int> pa, pb, pairs(iv.size() * 2), d(iv.size());
+  flatten_anc(A, pa);
+  flatten_anc(B, pb);
   for (size_t k = 0; k < iv.size(); k++) {
     pairs[2 * k] = iv[k].ta;
     pairs[2 * k + 1] = iv[k].tb;

@@ -17,53 +17,30 @@
 #include "anc_file.h"
 #include "common.h"
 #include "pairwise.h"
+#include "tree_host.h"
 
 namespace rl {
 
-int first_bad_node(const int *parent, int N, std::vector<unsigned char> &kids);  // compare.cpp
-
 namespace {
 
-int refuse_tree(const char *where, long long index, const int *parent, int N) {
-  std::vector<unsigned char> kids;
-  const int bad = first_bad_node(parent, N, kids);
-  const int v = bad - 1;
-  if (bad == 0) set_error("%s: tree %lld was refused by the device and not by the host", where, index);
-  else if (v == 2 * N - 2) set_error("%s: tree %lld: node %d is not the root (parent %d, expected -1) or has not two children", where, index, v, parent[v]);
-  else if (parent[v] <= v) set_error("%s: tree %lld: parent %d of node %d does not have a label above its child's", where, index, parent[v], v);
-  else set_error("%s: tree %lld: node %d (parent %d) does not fit a binary tree on %d leaves", where, index, v, parent[v], N);
-  return RL_EINVAL;
+int refuse_at(const char *where, long long index, const int *parent, int N) {
+  return refuse_tree((std::string(where) + ": tree " + std::to_string(index)).c_str(), parent, N);
 }
 
 // one tree's tables and its contribution to S
-struct HostPairwise {
-  int N, nodes;
-  std::vector<int> first, second, size, lo, order, g;
+struct HostPairwise : TreeTables {
+  std::vector<int> order, g;
   std::vector<double> height;
-  std::vector<unsigned char> kids;
-  explicit HostPairwise(int n) : N(n), nodes(2 * n - 1), first(nodes), second(nodes), size(nodes), lo(nodes), order(n), g(n), height(nodes) {}
+  explicit HostPairwise(int n) : TreeTables(n), order(n), g(n), height(nodes) {}
 
   // parent must have passed first_bad_node
   void prepare(const int *parent, const double *bl) {
-    std::fill(first.begin(), first.end(), -1);
-    for (int v = 0; v < nodes; v++) size[v] = v < N ? 1 : 0;
-    for (int v = 0; v < nodes - 1; v++) {  // label order: a node is complete before its parent reads it
-      const int p = parent[v];
-      size[p] += size[v];
-      if (first[p] == -1) first[p] = v;
-      else second[p] = v;
-    }
+    fill(parent);
     if (bl) {
       for (int v = 0; v < N; v++) height[v] = 0.0;
       for (int n = N; n < nodes; n++) height[n] = height[first[n]] + bl[first[n]];  // one addition per node
     }
-    lo[nodes - 1] = 0;
-    for (int p = nodes - 1; p >= N; p--) {  // falling order: a parent hands the left ends down
-      const int a = first[p], b = second[p];
-      lo[a] = lo[p];
-      lo[b] = lo[p] + size[a];
-      g[lo[b] - 1] = p;
-    }
+    for (int p = N; p < nodes; p++) g[lo[second[p]] - 1] = p;
     for (int v = 0; v < N; v++) order[lo[v]] = v;
   }
 
@@ -125,11 +102,11 @@ struct Pairwise {
     if (dev) {
       int bad = -1;
       const int rc = pairwise_device_add(dev, parents, bl, weights, ntrees, &bad);
-      return bad >= 0 ? refuse_tree(where, bad, parents + (size_t)bad * nodes, N) : rc;
+      return bad >= 0 ? refuse_at(where, bad, parents + (size_t)bad * nodes, N) : rc;
     }
     for (int t = 0; t < ntrees; t++) {
       const int *parent = parents + t * nodes;
-      if (first_bad_node(parent, N, host->kids)) return refuse_tree(where, t, parent, N);
+      if (first_bad_node(parent, N, host->kids)) return refuse_at(where, t, parent, N);
       host->prepare(parent, time ? bl + t * nodes : nullptr);
       const HostPairwise &h = *host;
       for (int i = 0; i < N; i++) {
@@ -199,7 +176,6 @@ extern "C" int rl_pairwise_anc(const char *const *anc_paths, int npaths, int met
   const bool time = metric == RL_PAIRWISE_TIME;
   Pairwise pw;
   if ((rc = pw.begin(N, time, device, sum_out))) return rc;
-  const size_t nodes = (size_t)2 * N - 1;
   std::vector<int> parents;
   std::vector<double> bl;
   std::vector<long long> weights;
@@ -217,14 +193,9 @@ extern "C" int rl_pairwise_anc(const char *const *anc_paths, int npaths, int met
     int first_snp, last_snp;
     if ((rc = anc_coverage(A, anc_paths[f], &first_snp, &last_snp))) return rc;
     const size_t T = A.trees.size();
-    parents.resize(T * nodes);
+    flatten_anc(A, parents, time ? &bl : nullptr);
     weights.resize(T);
-    if (time) bl.resize(T * nodes);
-    for (size_t t = 0; t < T; t++) {
-      memcpy(&parents[t * nodes], A.trees[t].parent.data(), nodes * sizeof(int));
-      if (time) memcpy(&bl[t * nodes], A.trees[t].branch_length.data(), nodes * sizeof(double));
-      weights[t] = (t + 1 < T ? A.trees[t + 1].pos : last_snp + 1) - (long long)A.trees[t].pos;
-    }
+    for (size_t t = 0; t < T; t++) weights[t] = (t + 1 < T ? A.trees[t + 1].pos : last_snp + 1) - (long long)A.trees[t].pos;
     if ((rc = pw.add(parents.data(), time ? bl.data() : nullptr, weights.data(), (int)T, anc_paths[f]))) return rc;
   }
   return pw.finish(total_weight);

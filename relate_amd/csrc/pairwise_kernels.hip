@@ -74,29 +74,19 @@ __global__ void __launch_bounds__(T) pairwise_prepare_kernel(const int *__restri
     if (wave0) {
       const double *bl = BL + (size_t)t * nodes;
       double *val = reinterpret_cast<double *>(VAL) + (size_t)t * N;
+      const auto leaf = [](int) { return 0.0; };
+      const auto table = [&](int j) { return H[j]; };
       for (int b = 0; b < ni; b += 64) {
         const int i = b + lane;
         const bool act = i < ni;
         int dep = -1;
         double base = 0.0, len = 0.0;
         if (act) {
-          const int c1 = (int)(K[i] >> 16) - 1;
+          const int c1 = first_child(K, i);
           len = bl[c1];
-          if (c1 < N) base = 0.0;
-          else if (c1 - N < b) base = H[c1 - N];
-          else dep = c1 - N - b;
+          dep = child_source(c1, N, b, &base, leaf, table);
         }
-        double h = 0.0;
-        bool done = !act;
-        for (;;) {
-          const unsigned long long dm = __ballot(done);
-          if (dm == ~0ull) break;
-          const double up = __shfl(h, dep < 0 ? 0 : dep, 64);
-          if (!done && (dep < 0 || ((dm >> dep) & 1))) {
-            h = (dep < 0 ? base : up) + len;
-            done = true;
-          }
-        }
+        const double h = wave_pull(act, dep, base, [len](double below) { return below + len; });
         if (act) {
           H[i] = h;
           val[i] = h;
@@ -114,12 +104,10 @@ __global__ void __launch_bounds__(T) pairwise_prepare_kernel(const int *__restri
   __syncthreads();
   for (int v = threadIdx.x; v < N; v += T) {
     const int pi = par[v] - N;
-    const int c1 = (int)(K[pi] >> 16) - 1;
-    rank[v] = (u16)(U[pi] + (c1 != v ? (c1 < N ? 1u : (unsigned)SZ[c1 - N]) : 0u));
+    rank[v] = (u16)leaf_rank(K, SZ, N, v, pi, U[pi]);
   }
   for (int i = threadIdx.x; i < ni; i += T) {
-    const int c1 = (int)(K[i] >> 16) - 1;
-    g[U[i] + (c1 < N ? 1u : (unsigned)SZ[c1 - N]) - 1u] = (u16)i;
+    g[U[i] + first_child_leaves(K, SZ, N, i) - 1u] = (u16)i;
     if (!TIME) reinterpret_cast<u16 *>(VAL)[(size_t)t * N + i] = SZ[i];
   }
 }
@@ -217,35 +205,6 @@ __global__ void __launch_bounds__(T) pairwise_accumulate_kernel(const u16 *__res
 
 static size_t round16(size_t b) { return (b + 15) & ~(size_t)15; }
 
-template <int T, bool TIME>
-static hipError_t launch_prepare(const int *par, const double *bl, int N, int ntrees, u16 *rank, u16 *g, void *val,
-                                 int *bad, hipStream_t stream) {
-  const size_t dyn = round16((size_t)(TIME ? 12 : 8) * (N - 1));
-  const void *fn = reinterpret_cast<const void *>(&pairwise_prepare_kernel<T, TIME>);
-  if (dyn > 48 * 1024) {
-    const hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn);
-    if (e != hipSuccess) return e;
-  }
-  hipLaunchKernelGGL((pairwise_prepare_kernel<T, TIME>), dim3(ntrees), dim3(T), dyn, stream, par, bl, N, ntrees, rank, g,
-                     val, bad);
-  return hipGetLastError();
-}
-
-template <int T, bool TIME>
-static hipError_t launch_accumulate(const u16 *rank, const u16 *g, const void *val, const long long *w, int N,
-                                    int ntrees, void *S, hipStream_t stream) {
-  const size_t dyn = round16((size_t)(TIME ? 14 : 8) * N);
-  const void *fn = reinterpret_cast<const void *>(&pairwise_accumulate_kernel<T, TIME>);
-  if (dyn > 48 * 1024) {
-    const hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn);
-    if (e != hipSuccess) return e;
-  }
-  const int rows = (N + 511) / 512, blocks = (N + rows - 1) / rows;
-  hipLaunchKernelGGL((pairwise_accumulate_kernel<T, TIME>), dim3(blocks), dim3(T), dyn, stream, rank, g, val, w, N,
-                     ntrees, rows, S);
-  return hipGetLastError();
-}
-
 struct PairwiseDevice {
   int N = 0, device = 0, batch = 0;
   bool time = false;
@@ -261,17 +220,7 @@ int pairwise_device_begin(PairwiseDevice **out, int N, bool time, int device) {
     set_error("rl_pairwise_trees: the device takes trees of 2 <= N <= %d leaves (N=%d); device < 0 selects the host", kPairwiseMaxN, N);
     return RL_EINVAL;
   }
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) {
-    (void)hipGetLastError();
-    set_error("no usable HIP device");
-    return RL_ENODEVICE;
-  }
-  if (device >= ndev) {
-    set_error("rl_pairwise_trees: device %d of %d", device, ndev);
-    return RL_ENODEVICE;
-  }
-  RL_HIP(hipSetDevice(device));
+  if (const int rc = select_device("rl_pairwise_trees", device)) return rc;
   PairwiseDevice *d = new PairwiseDevice;
   d->N = N;
   d->device = device;
@@ -311,29 +260,23 @@ int pairwise_device_begin(PairwiseDevice **out, int N, bool time, int device) {
   return RL_OK;
 }
 
-// the trees in order, batch by batch; *bad_tree: -1, or the first tree the device refused (RL_EINVAL; the caller
-// words the message)
-int pairwise_device_add(PairwiseDevice *d, const int *parents, const double *branch_length, const long long *weights,
-                        int ntrees, int *bad_tree) {
-  *bad_tree = -1;
-  RL_HIP(hipSetDevice(d->device));
+// the trees in order, batch by batch; SMALL: N <= kPairwiseSmallN
+template <bool TIME, bool SMALL>
+static int pairwise_add_batches(PairwiseDevice *d, const int *parents, const double *branch_length,
+                                const long long *weights, int ntrees, int *bad_tree) {
   const int N = d->N;
   const size_t nodes = (size_t)2 * N - 1;
+  const size_t dyn_prepare = round16((size_t)(TIME ? 12 : 8) * (N - 1)), dyn_accumulate = round16((size_t)(TIME ? 14 : 8) * N);
+  const int rows = (N + 511) / 512, blocks = (N + rows - 1) / rows;
+  u16 *rank = d->rank.as<u16>(), *g = d->g.as<u16>();
   for (int t0 = 0; t0 < ntrees; t0 += d->batch) {
     const int n = std::min(d->batch, ntrees - t0);
     RL_HIP(hipMemcpy(d->par.p, parents + (size_t)t0 * nodes, (size_t)n * nodes * 4, hipMemcpyHostToDevice));
-    if (d->time) RL_HIP(hipMemcpy(d->bl.p, branch_length + (size_t)t0 * nodes, (size_t)n * nodes * 8, hipMemcpyHostToDevice));
+    if (TIME) RL_HIP(hipMemcpy(d->bl.p, branch_length + (size_t)t0 * nodes, (size_t)n * nodes * 8, hipMemcpyHostToDevice));
     RL_HIP(hipMemcpy(d->w.p, weights + t0, (size_t)n * 8, hipMemcpyHostToDevice));
     RL_HIP(hipMemset(d->bad.p, 0, (size_t)n * 4));
-    u16 *rank = d->rank.as<u16>(), *g = d->g.as<u16>();
-    const bool small = N <= kPairwiseSmallN;
-    if (d->time) {
-      if (small) RL_HIP((launch_prepare<64, true>(d->par.as<int>(), d->bl.as<double>(), N, n, rank, g, d->val.p, d->bad.as<int>(), nullptr)));
-      else RL_HIP((launch_prepare<256, true>(d->par.as<int>(), d->bl.as<double>(), N, n, rank, g, d->val.p, d->bad.as<int>(), nullptr)));
-    } else {
-      if (small) RL_HIP((launch_prepare<64, false>(d->par.as<int>(), nullptr, N, n, rank, g, d->val.p, d->bad.as<int>(), nullptr)));
-      else RL_HIP((launch_prepare<256, false>(d->par.as<int>(), nullptr, N, n, rank, g, d->val.p, d->bad.as<int>(), nullptr)));
-    }
+    RL_HIP(launch_with_lds(pairwise_prepare_kernel<SMALL ? 64 : 256, TIME>, n, SMALL ? 64 : 256, dyn_prepare, nullptr, d->par.as<int>(),
+                           TIME ? d->bl.as<double>() : nullptr, N, n, rank, g, d->val.p, d->bad.as<int>()));
     // (the copy waits for the kernel.)  Nothing of a batch is added unless all of its trees passed: the accumulation
     // uses rank and g as indices
     RL_HIP(hipMemcpy(d->flags.data(), d->bad.p, (size_t)n * 4, hipMemcpyDeviceToHost));
@@ -342,17 +285,23 @@ int pairwise_device_add(PairwiseDevice *d, const int *parents, const double *bra
         *bad_tree = t0 + k;
         return RL_EINVAL;
       }
-    const long long *w = d->w.as<long long>();
-    if (d->time) {
-      if (small) RL_HIP((launch_accumulate<256, true>(rank, g, d->val.p, w, N, n, d->S.p, nullptr)));
-      else RL_HIP((launch_accumulate<1024, true>(rank, g, d->val.p, w, N, n, d->S.p, nullptr)));
-    } else {
-      if (small) RL_HIP((launch_accumulate<256, false>(rank, g, d->val.p, w, N, n, d->S.p, nullptr)));
-      else RL_HIP((launch_accumulate<1024, false>(rank, g, d->val.p, w, N, n, d->S.p, nullptr)));
-    }
+    RL_HIP(launch_with_lds(pairwise_accumulate_kernel<SMALL ? 256 : 1024, TIME>, blocks, SMALL ? 256 : 1024, dyn_accumulate, nullptr, rank,
+                           g, d->val.p, d->w.as<long long>(), N, n, rows, d->S.p));
     RL_HIP(hipDeviceSynchronize());  // the next batch overwrites the arrays this one reads
   }
   return RL_OK;
+}
+
+// *bad_tree: -1, or the first tree the device refused (RL_EINVAL; the caller words the message)
+int pairwise_device_add(PairwiseDevice *d, const int *parents, const double *branch_length, const long long *weights,
+                        int ntrees, int *bad_tree) {
+  *bad_tree = -1;
+  RL_HIP(hipSetDevice(d->device));
+  const bool small = d->N <= kPairwiseSmallN;
+  if (d->time) return small ? pairwise_add_batches<true, true>(d, parents, branch_length, weights, ntrees, bad_tree)
+                            : pairwise_add_batches<true, false>(d, parents, branch_length, weights, ntrees, bad_tree);
+  return small ? pairwise_add_batches<false, true>(d, parents, branch_length, weights, ntrees, bad_tree)
+               : pairwise_add_batches<false, false>(d, parents, branch_length, weights, ntrees, bad_tree);
 }
 
 int pairwise_device_finish(PairwiseDevice *d, void *sum_out) {

@@ -3,13 +3,13 @@
 // LDS, internal node v at index v - N (ni = N - 1 of them).
 //   build_kids      all threads: kids of every internal node, with the validity checks that must precede any use of a
 //                   label as an index;
+//   wave_pull       one wavefront: the scan every pass below and in the kernels is an instance of;
 //   wave_clade_sizes   one wavefront: leaves below every internal node, label order;
 //   wave_left_ends     one wavefront: left end of every internal node's interval of depth-first ranks, falling order.
-// The two wave passes take the internal nodes 64 at a time; a lane PULLS what it depends on -- from LDS for a node of
-// another 64, by lane shuffle for a node of its own 64 once that lane is done (a ballot of the done lanes per round;
-// the lane whose dependencies lie outside the 64 never waits).  A round costs a ballot and one or two shuffles, no
-// LDS traffic: a caterpillar, whose every node waits for the one before it, takes N-1 such rounds per pass, O(N) in
-// all -- there is no walk from a leaf to the root anywhere.
+// The wave passes take the internal nodes 64 at a time; a lane PULLS what it depends on -- from LDS for a node of
+// another 64, by lane shuffle for a node of its own 64 once that lane is done.  A round costs a ballot and a shuffle
+// per dependency and value word, no LDS traffic: a caterpillar, whose every node waits for the one before it, takes
+// N-1 such rounds per pass, O(N) in all -- there is no walk from a leaf to the root anywhere.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -54,35 +54,83 @@ __device__ bool build_kids(const int *__restrict__ par, int N, unsigned *K, u16 
   return *bad == 0;
 }
 
+inline __device__ int first_child(const unsigned *K, int pi) { return (int)(K[pi] >> 16) - 1; }
+inline __device__ int second_child(const unsigned *K, int pi) { return (int)(K[pi] & 0xffffu) - 1; }
+// leaves below the first child of internal node pi
+inline __device__ unsigned first_child_leaves(const unsigned *K, const u16 *SZ, int N, int pi) {
+  const int c1 = first_child(K, pi);
+  return c1 < N ? 1u : (unsigned)SZ[c1 - N];
+}
+// depth-first rank of leaf v, a child of internal node pi whose left end is lo: the first child starts where its
+// parent does, the second after the first child's leaves
+inline __device__ unsigned leaf_rank(const unsigned *K, const u16 *SZ, int N, int v, int pi, unsigned lo) {
+  return lo + (first_child(K, pi) != v ? first_child_leaves(K, SZ, N, pi) : 0u);
+}
+
+// (size, min rank << 16 | max rank) of a clade: the value CompareTopology pulls, shuffled member by member
+struct SizeSpan {
+  unsigned sz, mm;
+};
+template <class V>
+inline __device__ V wave_shfl(V v, int lane) { return __shfl(v, lane, 64); }
+inline __device__ SizeSpan wave_shfl(SizeSpan v, int lane) { return SizeSpan{__shfl(v.sz, lane, 64), __shfl(v.mm, lane, 64)}; }
+
+// The pull scan over 64 consecutive items, one per lane of the calling wavefront (all 64 lanes call it).  A lane with
+// `pending` set has DEPS (1 or 2) dependencies: d < 0 -- the value is known already and given; d >= 0 -- it is the
+// value of lane d of this 64.  Returns combine(value of dependency 1[, of dependency 2]) to a pending lane, V() to
+// any other.  Per round: a ballot of the done lanes, a shuffle of every dependency's value, and the lanes whose
+// dependencies are all done finish.
+// Termination: in a rising pass (children before parents) every dependency is a LOWER lane, in a falling pass
+// (parents before children) a HIGHER one -- the callers' labels rise from child to parent, which build_kids has
+// checked.  So the lowest (highest) lane not done has no dependency that is not done: every round retires at least
+// one lane, 64 rounds at the most, and no lane reads a value before the ballot has shown it final.
+template <int DEPS, class V, class F>
+inline __device__ V wave_pull(bool pending, int d1, V known1, int d2, V known2, F combine) {
+  static_assert(DEPS == 1 || DEPS == 2, "one or two dependencies");
+  V val = V();
+  bool done = !pending;
+  for (;;) {
+    const unsigned long long dm = __ballot(done);
+    if (dm == ~0ull) break;
+    const V t1 = wave_shfl(val, d1 < 0 ? 0 : d1);
+    const V t2 = DEPS == 2 ? wave_shfl(val, d2 < 0 ? 0 : d2) : known2;
+    if (!done && (d1 < 0 || ((dm >> d1) & 1)) && (DEPS == 1 || d2 < 0 || ((dm >> d2) & 1))) {
+      val = combine(d1 < 0 ? known1 : t1, DEPS == 1 || d2 < 0 ? known2 : t2);
+      done = true;
+    }
+  }
+  return val;
+}
+template <class V, class F>
+inline __device__ V wave_pull(bool pending, int d, V known, F combine) {
+  return wave_pull<1>(pending, d, known, -1, V(), [&](V a, V) { return combine(a); });
+}
+
+// Where a rising pass over the 64 items from b finds child c: -1 with *known = leaf(c) or table(c - N) (a leaf; a
+// node of an earlier 64, in LDS by now), or the lane of this 64 that will have it.
+template <class V, class L, class T>
+inline __device__ int child_source(int c, int N, int b, V *known, L leaf, T table) {
+  if (c < N) *known = leaf(c);
+  else if (c - N < b) *known = table(c - N);
+  else return c - N - b;
+  return -1;
+}
+
 // SZ[i] = leaves below internal node i.  One wavefront calls it (lane = its lane index).
 __device__ inline void wave_clade_sizes(const unsigned *K, int N, u16 *SZ, int lane) {
   const int ni = N - 1;
+  const auto leaf = [](int) { return 1u; };
+  const auto table = [&](int j) { return (unsigned)SZ[j]; };
   for (int b = 0; b < ni; b += 64) {
     const int i = b + lane;
     const bool act = i < ni;
     int d1 = -1, d2 = -1;  // lanes this one waits for
     unsigned s1 = 0, s2 = 0;
     if (act) {
-      const unsigned k = K[i];
-      const int c1 = (int)(k >> 16) - 1, c2 = (int)(k & 0xffffu) - 1;
-      if (c1 < N) s1 = 1;
-      else if (c1 - N < b) s1 = SZ[c1 - N];
-      else d1 = c1 - N - b;
-      if (c2 < N) s2 = 1;
-      else if (c2 - N < b) s2 = SZ[c2 - N];
-      else d2 = c2 - N - b;
+      d1 = child_source(first_child(K, i), N, b, &s1, leaf, table);
+      d2 = child_source(second_child(K, i), N, b, &s2, leaf, table);
     }
-    unsigned sz = 0;
-    bool done = !act;
-    for (;;) {
-      const unsigned long long dm = __ballot(done);
-      if (dm == ~0ull) break;
-      const unsigned t1 = __shfl(sz, d1 < 0 ? 0 : d1, 64), t2 = __shfl(sz, d2 < 0 ? 0 : d2, 64);
-      if (!done && (d1 < 0 || ((dm >> d1) & 1)) && (d2 < 0 || ((dm >> d2) & 1))) {
-        sz = (d1 < 0 ? s1 : t1) + (d2 < 0 ? s2 : t2);
-        done = true;
-      }
-    }
+    const unsigned sz = wave_pull<2>(act, d1, s1, d2, s2, [](unsigned a, unsigned c) { return a + c; });
     if (act) SZ[i] = (u16)sz;
   }
 }
@@ -101,23 +149,12 @@ __device__ inline void wave_left_ends(const unsigned *K, const u16 *SZ, u16 *U, 
     bool second = false;
     if (act && !root) {
       const int pi = U[i];
-      const int c1 = (int)(K[pi] >> 16) - 1;  // the parent's first child
-      second = c1 != i + N;
-      if (second) off = c1 < N ? 1u : (unsigned)SZ[c1 - N];
+      second = first_child(K, pi) != i + N;
+      if (second) off = first_child_leaves(K, SZ, N, pi);
       if (pi >= b + 64) base = U[pi];  // (its left end by now: written 64 or more labels ago)
       else dep = pi - b;
     }
-    unsigned lo = 0;
-    bool done = !act || root;
-    for (;;) {
-      const unsigned long long dm = __ballot(done);
-      if (dm == ~0ull) break;
-      const unsigned t = __shfl(lo, dep < 0 ? 0 : dep, 64);
-      if (!done && (dep < 0 || ((dm >> dep) & 1))) {
-        lo = (dep < 0 ? base : t) + off;
-        done = true;
-      }
-    }
+    const unsigned lo = wave_pull(act && !root, dep, base, [off](unsigned a) { return a + off; });  // the root: 0
     if (act) {
       U[i] = (u16)lo;
       visit(i, lo, second, root);

@@ -6,7 +6,7 @@ reference_sum is the same definition in numpy for the sizes the device promises 
 small N in test_pairwise_cpu.py."""
 import numpy as np
 
-from compare_cases import ANC_NODE, balanced, caterpillar, random_tree  # noqa: F401  (the tests' tree shapes)
+from tree_cases import balanced, caterpillar, random_tree, read_anc, shapes, write_anc  # noqa: F401  (the tests' trees and files)
 
 
 def tree_values(parent, branch_length, metric):
@@ -136,44 +136,7 @@ def branch_lengths(N, rng):
     return rng.random(2 * N - 1) * 1000.0 + 0.1
 
 
-def write_anc(path, N, trees, end, ages=None):
-    """trees: [(pos, parent, branch_length or None)]; SNP_begin / SNP_end as BuildTopology leaves them (the tree's
-    position, the next tree's; the last tree's SNP_end = end); ages: sample ages, written if given"""
-    with open(path, "wb") as f:
-        f.write(np.uint8(ages is not None).tobytes() + np.uint32(N).tobytes())
-        if ages is not None:
-            f.write(np.asarray(ages, "<f8").tobytes())
-        f.write(np.uint32(len(trees)).tobytes())
-        for t, (pos, parent, bl) in enumerate(trees):
-            rec = np.zeros(2 * N - 1, ANC_NODE)
-            rec["parent"] = parent
-            if bl is not None:
-                rec["branch_length"] = bl
-            rec["snp_begin"] = pos
-            rec["snp_end"] = trees[t + 1][0] if t + 1 < len(trees) else end
-            f.write(np.int32(pos).tobytes() + rec.tobytes())
-
-
-def read_anc(buf):
-    """bytes of a .anc file without sample ages -> (N, [(pos, parent, branch_length, largest SNP_end)])"""
-    assert buf[0] == 0
-    N, T = [int(x) for x in np.frombuffer(buf, "<u4", 2, 1)]
-    at, out = 9, []
-    for _ in range(T):
-        pos = int(np.frombuffer(buf, "<i4", 1, at)[0])
-        rec = np.frombuffer(buf, ANC_NODE, 2 * N - 1, at + 4)
-        out.append((pos, rec["parent"].astype(np.int32), rec["branch_length"].astype(np.float64), int(rec["snp_end"].max())))
-        at += 4 + 24 * (2 * N - 1)
-    assert at == len(buf)
-    return N, out
-
-
 def file_weights(trees, end):
     """SNPs each tree of a file covers: to the next tree's position, the last one up to and including `end`"""
     pos = [t[0] for t in trees]
     return [(pos[t + 1] if t + 1 < len(pos) else end + 1) - pos[t] for t in range(len(pos))]
-
-
-def shapes(N, rng, randoms=3):
-    """a caterpillar, the caterpillar on the leaves in reverse order, a balanced tree, random trees"""
-    return [caterpillar(N), caterpillar(N, range(N - 1, -1, -1)), balanced(N)] + [random_tree(N, rng) for _ in range(randoms)]

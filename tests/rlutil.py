@@ -140,6 +140,27 @@ def synth_chunk(N, L, seed=1, block=100, jitter=True, budget=None, theta=0.001):
     return Chunk(seq, r, rpos, wb, bp, theta)
 
 
+# ------------------------------------------------------------ GPU steps
+STOP = []  # why no further GPU step may start: one list for every test module that uses gpu_step
+
+
+def gpu_step(cmd, seconds, **kw):
+    """one GPU step of a test, a child process under its own time limit; a step that dies by a signal or runs out of
+    time ends the GPU work of every module that starts its steps here"""
+    import pytest
+    if STOP:
+        pytest.fail("not started: an earlier GPU step " + STOP[0])
+    try:
+        p = subprocess.run(["timeout", "-k", "10", str(seconds)] + cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE,
+                           **kw)
+    except Exception as e:  # pragma: no cover
+        STOP.append("could not be run: %r" % (e,))
+        raise
+    if p.returncode < 0 or p.returncode in (124, 134, 137, 139):
+        STOP.append("ended with status %d: %s" % (p.returncode, " ".join(cmd[:4])))
+    return p
+
+
 # ---------------------------------------------------------------- parsers
 def parse_paint_file(path, N):
     """-> list over targets of dict(start,end,bb,la,alpha,be,lb,beta)"""

@@ -70,8 +70,8 @@ def fixture_sequences(tmp_path):
     N, seq_a = None, []
     for w in range(W):
         N, trees = cc.read_anc(z["anc/%d" % w].tobytes())
-        seq_a += [(pos, parent) for pos, parent, _ in trees]
-        end = trees[-1][2]
+        seq_a += [(pos, parent) for pos, parent, _, _ in trees]
+        end = trees[-1][3]
     assert N == 24 and len(seq_a) > W and all(seq_a[t][0] < seq_a[t + 1][0] for t in range(len(seq_a) - 1))
     rng = np.random.default_rng(24)
     seq_b = []

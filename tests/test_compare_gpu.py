@@ -3,7 +3,6 @@ implementation, integer for integer, and end to end on the trees of the exact an
 the brute-force oracle of compare_cases.py.  Every step that uses the GPU is a child process under a time limit of
 its own; after one that was killed, aborted or timed out no further step is started."""
 import os
-import subprocess
 import sys
 
 import numpy as np
@@ -13,12 +12,12 @@ import bigtile
 import compare_cases as cc
 from golden_util import Fixture
 from relate_amd import api
+from rlutil import gpu_step
 
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CLI = os.path.join(ROOT, "relate_amd", "Relate")
-STOP = []  # why no further GPU step may start
 
 CHILD = """
 import sys, time
@@ -30,22 +29,6 @@ t0 = time.perf_counter()
 out = api.compare_trees(z["A"], z["B"], z["pairs"], device=0)
 np.savez(sys.argv[3], out=out, seconds=time.perf_counter() - t0)
 """
-
-
-def gpu_step(cmd, seconds, **kw):
-    """one GPU step under its own time limit; a step that dies by a signal or runs out of time ends the GPU work of
-    this module"""
-    if STOP:
-        pytest.fail("not started: an earlier GPU step " + STOP[0])
-    try:
-        p = subprocess.run(["timeout", "-k", "10", str(seconds)] + cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE,
-                           **kw)
-    except Exception as e:  # pragma: no cover
-        STOP.append("could not be run: %r" % (e,))
-        raise
-    if p.returncode < 0 or p.returncode in (124, 134, 137, 139):
-        STOP.append("ended with status %d: %s" % (p.returncode, " ".join(cmd[:4])))
-    return p
 
 
 def on_device(tmp_path, A, B, pairs, seconds=120):
@@ -150,7 +133,7 @@ def test_end_to_end_exact_and_fast_modes(tmp_path):
             assert int(said["max_distance"]) == host["max_distance"]
             na, ta = cc.read_anc(open(a, "rb").read())
             nb, tb = cc.read_anc(open(b, "rb").read())
-            rows, want = cc.oracle_compare(N, [t[:2] for t in ta], ta[-1][2], [t[:2] for t in tb], tb[-1][2])
+            rows, want = cc.oracle_compare(N, [t[:2] for t in ta], ta[-1][3], [t[:2] for t in tb], tb[-1][3])
             cc.check_summary(host, rows, want)
             if tag == "exact2":
                 assert all(r[4] == 0 for r in cli_rows) and host["share_identical"] == 1.0

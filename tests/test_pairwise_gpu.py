@@ -3,7 +3,6 @@ bit, for both metrics, and end to end on the trees of a PaintBuildTopology run a
 pairwise_cases.py.  Every step that uses the GPU is a child process under a time limit of its own; after one that
 was killed, aborted or timed out no further step is started."""
 import os
-import subprocess
 import sys
 
 import numpy as np
@@ -13,12 +12,12 @@ import bigtile
 import pairwise_cases as pc
 from golden_util import Fixture
 from relate_amd import api
+from rlutil import gpu_step
 
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CLI = os.path.join(ROOT, "relate_amd", "Relate")
-STOP = []  # why no further GPU step may start
 SMALL_N = 1024  # kPairwiseSmallN: above it the kernels run with larger workgroups (256 / 1024 threads, not 64 / 256)
 
 CHILD = """
@@ -83,22 +82,6 @@ np.savez(sys.argv[3], S=S, W=W)
 """
 
 
-def gpu_step(cmd, seconds, **kw):
-    """one GPU step under its own time limit; a step that dies by a signal or runs out of time ends the GPU work of
-    this module"""
-    if STOP:
-        pytest.fail("not started: an earlier GPU step " + STOP[0])
-    try:
-        p = subprocess.run(["timeout", "-k", "10", str(seconds)] + cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE,
-                           **kw)
-    except Exception as e:  # pragma: no cover
-        STOP.append("could not be run: %r" % (e,))
-        raise
-    if p.returncode < 0 or p.returncode in (124, 134, 137, 139):
-        STOP.append("ended with status %d: %s" % (p.returncode, " ".join(cmd[:4])))
-    return p
-
-
 def on_device(tmp_path, parents, weights, bl, seconds=120):
     src, dst = str(tmp_path / "in.npz"), str(tmp_path / "out.npz")
     np.savez(src, parents=parents, weights=np.asarray(weights, np.int64), bl=bl)
@@ -132,6 +115,39 @@ def test_device_equals_host(tmp_path, N):
     parents = np.stack(pc.shapes(N, rng))
     bl = np.stack([pc.branch_lengths(N, rng) for _ in parents])
     check_against_host(tmp_path, N, parents, [7, 1, 0, 1000003, 12, 5], bl, "N%d" % N)
+
+
+def cherry_comb(N):
+    """(((l0, l1), (l2, l3)), (l4, l5)), ...: cherries joined in a chain, each label given as it is needed.  The first
+    child (smaller label) of a chain node is the chain node two labels below it: the deepest chain of FIRST children a
+    tree with rising labels has (a caterpillar's first child is always the leaf).  An odd N ends with (last leaf, chain)"""
+    parent = np.full(2 * N - 1, -1, np.int32)
+    parent[0] = parent[1] = chain = N
+    label = N + 1
+    for leaf in range(2, N - 1, 2):
+        parent[leaf] = parent[leaf + 1] = label
+        parent[chain] = parent[label] = chain = label + 1
+        label += 2
+    if N % 2:
+        parent[N - 1] = parent[chain] = label
+    return parent
+
+
+def test_two_full_blocks_of_64(tmp_path):
+    """N = 129: the 128 internal nodes are exactly two full blocks of 64 of the wave passes, no partial block, every
+    lane of both blocks at work.  A caterpillar and its reverse: in the sizes and the left ends every lane waits for
+    its neighbour, the first lane of a block for what the block before left in LDS.  Their heights do not chain (the
+    first child of every node is a leaf), so a comb of cherries goes with them: there the heights pass, the pull scan
+    on a double, has lane k wait for lane k - 2 through both blocks.  Both metrics against the host's bits.  (N = 65
+    and 257 of test_device_equals_host end in a partial block.)"""
+    N = 129
+    rng = np.random.default_rng(N)
+    parents = np.stack(pc.shapes(N, rng, randoms=0)[:2] + [cherry_comb(N)])
+    assert (parents[:2, N:-1] == np.arange(N + 1, 2 * N - 1)).all()  # caterpillars: a chain of all internal nodes
+    first = np.array([np.flatnonzero(parents[2] == m)[0] for m in range(N, 2 * N - 1)])
+    assert (first[2:-1:2] == np.arange(N, 2 * N - 4, 2)).all()  # comb: the first child of N + 2k is N + 2k - 2
+    bl = np.stack([pc.branch_lengths(N, rng) for _ in parents])
+    check_against_host(tmp_path, N, parents, [3, 5, 7], bl, "N129_two_full_blocks")
 
 
 def test_many_row_blocks_and_batches_and_the_same_bits_twice(tmp_path):
