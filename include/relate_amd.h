@@ -175,7 +175,7 @@ int rl_debug_wave_sum_ex(const double *x, int n, int batch, int rows_per_group, 
                          unsigned long long *stats8);
 
 /* Experiment builds only (kernels compiled with -DRL_STATS and
- * RELATE_AMD_STATS set): 16 event counters of the last rl_paint. */
+ * RELATE_AMD_TEST_STATS set): 16 event counters of the last rl_paint. */
 int rl_debug_stats(rl_ctx *ctx, unsigned long long *out16);
 /* ... and all 32 (16..24: cycles of the forward / backward step by segment, paint_kernels.hip) */
 int rl_debug_stats32(rl_ctx *ctx, unsigned long long *out32);

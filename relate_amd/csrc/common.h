@@ -3,6 +3,7 @@
 #include <cstdlib>
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <atomic>
 #include <cstdarg>
 #include <cstdint>
@@ -22,7 +23,7 @@ void set_error(const char *fmt, ...);
 // RELATE_AMD_TIMING: 0 / unset -- quiet; 1 -- where the wall-clock goes, on stderr; 2 -- also the tree builder's
 // progress marks (which worker holds which tree, the merge and phase a waiting build has reached)
 inline int timing_level() {
-  static const int level = getenv("RELATE_AMD_TIMING") ? (atoi(getenv("RELATE_AMD_TIMING")) >= 2 ? 2 : 1) : 0;
+  static const int level = getenv("RELATE_AMD_TIMING") ? std::max(0, std::min(2, atoi(getenv("RELATE_AMD_TIMING")))) : 0;
   return level;
 }
 

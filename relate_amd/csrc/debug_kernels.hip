@@ -32,9 +32,7 @@ __global__ void __launch_bounds__(64 * WAVES) sum_kernel(const double *__restric
                                                          unsigned long long *__restrict__ stats) {
   __shared__ WaveLinkStorage link;
   __shared__ unsigned long long lstats[SUM_STATS];
-  WaveLink<WAVES> lk;
-  lk.s = &link;
-  lk.w = WAVES > 1 ? __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)) : 0;
+  WaveLink<WAVES> lk = make_wave_link<WAVES>(&link);
   if (threadIdx.x < SUM_STATS) lstats[threadIdx.x] = 0;
   __syncthreads();
   // the kernels' layout over n terms (make_layout(n, WAVES), PaintLane::init)
@@ -76,26 +74,9 @@ template <int MODE>
 static hipError_t launch_sum(int S, int waves, const double *x, int n, int groups, int rows_per_group,
                              const unsigned long long *masks, double th, double nth, double *out,
                              unsigned long long *stats) {
-  if (waves == 1) {
-    switch (S) {
-#define RL_CASE(s, t) \
-  case s:             \
-    return launch_sum_t<s, MODE, 1>(x, n, groups, rows_per_group, masks, th, nth, out, stats);
-      RL_FOR_EACH_S(RL_CASE)
-#undef RL_CASE
-    }
-  } else {
-#ifndef RL_ONLY_S
-    switch (S) {
-#define RL_CASE(s, t) \
-  case s:             \
-    return launch_sum_t<s, MODE, 2>(x, n, groups, rows_per_group, masks, th, nth, out, stats);
-      RL_FOR_EACH_S_2WAVES(RL_CASE)
-#undef RL_CASE
-    }
-#endif
-  }
-  return hipErrorInvalidValue;
+  return dispatch_tile(S, waves, [&](auto s, auto, auto w) {
+    return launch_sum_t<s(), MODE, w()>(x, n, groups, rows_per_group, masks, th, nth, out, stats);
+  });
 }
 
 }  // namespace rl
@@ -119,7 +100,7 @@ extern "C" int rl_debug_wave_sum_ex(const double *x, int n, int batch, int rows_
   }
   const int waves = target_waves(n);
   const Layout lay = make_layout(n, waves);
-  const int S = choose_S(lay);  // (two waves: 48, 64 or 80, the RL_FOR_EACH_S_2WAVES set)
+  const int S = choose_S(lay);  // (two waves: 48, 64 or 80, launch.h tile_has_two_waves)
   if (!S) {
     set_error("rl_debug_wave_sum_ex: no register tile for n=%d", n);
     return RL_EINVAL;

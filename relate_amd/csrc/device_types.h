@@ -45,7 +45,9 @@ struct PaintParams {
   float *alpha, *beta;      // [Wr][nloc][N] stepping stones, donor order
   float *ls_alpha, *ls_beta;  // [Wr][nloc]
   int sum_mode;             // RL_SUM_EXACT / RL_SUM_LANES / RL_SUM_EXACT_SERIAL
-  int merge_order;          // one launch for both directions: 0 = backward blocks first, then forward; 1 = interleaved
+  int merge_order;          // always 0: in the one launch for both directions the backward blocks come first, then the
+                            // forward ones.  (1 = interleaved is dead; the field and its branch in paint_kernel stay
+                            // because that kernel gets 68 B of scratch without them, DESIGN_NOTES.md 13)
   unsigned long long *stats;  // 16 event counters (experiment builds with -DRL_STATS), else null
 };
 

@@ -134,6 +134,28 @@ struct WaveLink {
     if constexpr (WAVES > 1) __syncthreads();
   }
 };
+// the link of this wave of a workgroup of WAVES waves (the prologue of every kernel that sums)
+template <int WAVES>
+RL_DEV WaveLink<WAVES> make_wave_link(WaveLinkStorage *storage) {
+  WaveLink<WAVES> lk;
+  lk.s = storage;
+  lk.w = WAVES > 1 ? __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)) : 0;
+  return lk;
+}
+// The `lanes` order: the wave's (workgroup's) total of one value per lane as a balanced tree, in double.
+template <int WAVES>
+RL_DEV double lanes_total(double lane_sum, WaveLink<WAVES> &lk) {
+  lk.phase++;
+  const double t = wave_sum_butterfly(lane_sum);
+  if constexpr (WAVES == 1) {
+    return t;
+  } else {  // the top level of the balanced tree over 128 lane sums
+    const unsigned ph = lk.phase & 1u;
+    if ((threadIdx.x & 63) == 0) lk.s->tot[ph][lk.w] = t;
+    lk.barrier();
+    return lk.s->tot[ph][0] + lk.s->tot[ph][1];
+  }
+}
 
 // The literal serial sum as the rare-path fallback of sum_exact_fast: same
 // result as sum_exact, but the terms are recomputed in every round (the empty
@@ -456,21 +478,14 @@ RL_DEV double sum_exact_fast(const T &term, double L, WaveLink<WAVES> &lk) {
 // L = the lane's local serial sum of its terms (see sum_exact_fast)
 template <int MODE, int S, int WAVES, typename T>
 RL_DEV double wave_sum(const T &term, double L, WaveLink<WAVES> &lk) {
-  lk.phase++;
-  if constexpr (MODE == 1) {
-    return sum_exact_fast<S, WAVES>(term, L, lk);
-  } else if constexpr (MODE == 2) {
-    return sum_exact_fallback_linked<S, WAVES>(term, lk);
+  if constexpr (MODE == 0) {
+    return lanes_total(L, lk);
   } else {
-    const double t = wave_sum_butterfly(L);
-    if constexpr (WAVES == 1) {
-      return t;
-    } else {  // the top level of the balanced tree over 128 lane sums
-      const unsigned ph = lk.phase & 1u;
-      if ((threadIdx.x & 63) == 0) lk.s->tot[ph][lk.w] = t;
-      lk.barrier();
-      return lk.s->tot[ph][0] + lk.s->tot[ph][1];
-    }
+    lk.phase++;
+    if constexpr (MODE == 1)
+      return sum_exact_fast<S, WAVES>(term, L, lk);
+    else
+      return sum_exact_fallback_linked<S, WAVES>(term, lk);
   }
 }
 // one wave per target (K2, the test hook)

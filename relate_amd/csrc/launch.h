@@ -2,6 +2,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <type_traits>
+
 #include "device_types.h"
 
 namespace rl {
@@ -18,9 +20,10 @@ namespace rl {
 // smallest instantiated S with S >= q + (rem > 0); 0 if N is too large
 inline int choose_S(const Layout &lay) {
   const int need = lay.q + (lay.rem > 0 ? 1 : 0);
-  static const int sizes[] = {8, 16, 32, 48, 64, 80};
-  for (int s : sizes)
-    if (s >= need) return s;
+#define RL_FITS(s, t) \
+  if (s >= need) return s;
+  RL_FOR_EACH_S(RL_FITS)
+#undef RL_FITS
   return 0;
 }
 
@@ -37,7 +40,49 @@ inline Layout make_layout(int N, int waves = 1) {
 // K1 and K2 give a target to a workgroup of two waves once one wave would need more than 80
 // registers per lane (two waves per SIMD need the kernels to stay within 256 VGPRs)
 inline int target_waves(int N) { return N > 80 * 64 ? 2 : 1; }
-#define RL_FOR_EACH_S_2WAVES(X) X(48, 16) X(64, 16) X(80, 16)
+// ... which leaves 41 .. 80 registers per lane (q = N / 128 >= 40 and choose_S rounds q + 1 up to a tile of
+// RL_FOR_EACH_S): the two-wave kernels exist for the tiles from 48 on.
+// (RL_ONLY_S is an experiment switch of the kernel files alone, tools/build_paint_variant.sh: there the tile list is
+//  the one tile and no two-wave kernel is built.  The host files are compiled without it, so choose_S keeps the full
+//  list in a variant library and a tile the variant lacks comes back as hipErrorInvalidValue.)
+constexpr bool tile_has_two_waves(int S) {
+#ifdef RL_ONLY_S
+  return false;
+#else
+  return S >= 48;
+#endif
+}
+// The run-time (S, waves) as compile-time (S, TAIL, WAVES): f(integral_constant S, TAIL, WAVES) of the instantiated
+// tile, hipErrorInvalidValue for any other.  The one switch over the tiles.
+template <typename F>
+hipError_t dispatch_tile(int S, int waves, F &&f) {
+  switch (S) {
+#define RL_CASE(s, t)                                                                                    \
+  case s:                                                                                                \
+    if (waves == 1) return f(std::integral_constant<int, s>{}, std::integral_constant<int, t>{},         \
+                             std::integral_constant<int, 1>{});                                          \
+    if constexpr (tile_has_two_waves(s))                                                                 \
+      if (waves == 2) return f(std::integral_constant<int, s>{}, std::integral_constant<int, t>{},       \
+                               std::integral_constant<int, 2>{});                                        \
+    break;
+    RL_FOR_EACH_S(RL_CASE)
+#undef RL_CASE
+  }
+  return hipErrorInvalidValue;
+}
+// K1's launch of one direction (dir = 0 forward, 1 backward: nloc workgroups) or of both (2: 2 * nloc workgroups);
+// kernel_of(integral_constant DIR) is the kernel
+template <typename K>
+hipError_t launch_paint_dir(K kernel_of, const PaintParams &p, int waves, int dir, hipStream_t stream) {
+  const dim3 grid(dir == 2 ? 2 * p.nloc : p.nloc), block(64 * waves);
+  if (dir == 2)
+    hipLaunchKernelGGL(kernel_of(std::integral_constant<int, 2>{}), grid, block, 0, stream, p);
+  else if (dir == 1)
+    hipLaunchKernelGGL(kernel_of(std::integral_constant<int, 1>{}), grid, block, 0, stream, p);
+  else
+    hipLaunchKernelGGL(kernel_of(std::integral_constant<int, 0>{}), grid, block, 0, stream, p);
+  return hipGetLastError();
+}
 hipError_t launch_lane_masks(const uint32_t *bits, int row_words, int L, const Layout &lay, int S, int waves,
                              unsigned long long *masks, hipStream_t stream);
 

@@ -17,9 +17,10 @@
 // (the weighted sum as ntheta * sum_all + (theta - ntheta) * sum_mis'), against 3 + 6 in the `lanes` order on doubles.
 // The lanes' sums are FP32 partials (two chains per half), widened and reduced over the wave in double as in `lanes`;
 // the step's factor, logscale and rescaling tests stay double.  80 state registers instead of 160: four waves a SIMD.
+// The stones, the `lanes` total and the dispatch are the FP64 kernels' (paint_pass.h, exact_sum.h, launch.h); the step
+// bodies are this file's own, and so are the passes' preamble and the backward row pipeline (DESIGN_NOTES.md 13).
 #include <cstdlib>
-#include "paint_device.h"
-#include "exact_sum.h"
+#include "paint_pass.h"
 #include "launch.h"
 
 // experiment knobs (tools/build_paint_variant.sh): waves per SIMD the kernel is held to, mask words per chunk
@@ -34,9 +35,6 @@
 #endif
 
 namespace rl {
-
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef const __attribute__((address_space(4))) PaintParams *ColdParams32;
 
 RL_DEV f32x2 splat(float v) { return f32x2{v, v}; }
 // (clang selects v_pk_add_f32 / v_pk_mul_f32 for <2 x float> arithmetic on gfx950; -ffp-contract=off keeps them apart.
@@ -166,44 +164,6 @@ RL_DEV void set_slot32(f32x2 (&a)[S / 2], int j, u64 bit, float v) {
   pin_registers32<S>(a);
 }
 
-// one stepping stone, donor order (paint_kernels.hip emit_stone, the state being floats already)
-template <int S>
-RL_DEV void emit_stone32(const PaintLane<S> &pl, const f32x2 (&v)[S / 2], float *__restrict__ out, float self_value,
-                         float *stage) {
-  constexpr int R = S % 16 == 0 ? 16 : 8;
-#pragma unroll
-  for (int c = 0; c < S / R; c++) {
-#pragma unroll
-    for (int ii = 0; ii < R; ii += 2) {
-      f32x2 x = v[(c * R + ii) / 2];
-      asm volatile("" : "+v"(x) : : "memory");
-      stage[ii * 64 + pl.lane] = x.x;
-      stage[(ii + 1) * 64 + pl.lane] = x.y;
-    }
-#pragma clang loop unroll(disable)
-    for (int ii = 0; ii < R; ii++) {
-      const int i = c * R + ii;
-      const int n = pl.start + i;
-      if (i < pl.len) out[n] = (n == pl.k) ? self_value : stage[ii * 64 + pl.lane];
-    }
-  }
-}
-
-// the wave's (workgroup's) sum of per-lane FP32 partials, in double: the `lanes` reduction (exact_sum.h wave_sum<0>)
-template <int S, int WAVES>
-RL_DEV double lanes_total(double lane_sum, WaveLink<WAVES> &lk) {
-  lk.phase++;
-  const double t = wave_sum_butterfly(lane_sum);
-  if constexpr (WAVES == 1) {
-    return t;
-  } else {
-    const unsigned ph = lk.phase & 1u;
-    if ((threadIdx.x & 63) == 0) lk.s->tot[ph][lk.w] = t;
-    lk.barrier();
-    return lk.s->tot[ph][0] + lk.s->tot[ph][1];
-  }
-}
-
 template <int S, int TAIL, int WAVES>
 RL_DEV void paint32_forward(const PaintParams &p, int k, float *stage, WaveLink<WAVES> &lk) {
   static_assert(TAIL % 2 == 0 && S % 8 == 0, "pairs");
@@ -244,42 +204,25 @@ RL_DEV void paint32_forward(const PaintParams &p, int k, float *stage, WaveLink<
     s0 += s1;
     return (double)s0.x + (double)s0.y;
   };
-  double ssum = lanes_total<S, WAVES>(lane_sum(), lk);
+  double ssum = lanes_total(lane_sum(), lk);
   double ls = 0.0;
-  int wa = 0;
-  auto stone_index = [&](int w) {
-    const ColdParams32 cp = cold_params<PaintParams>();
-    return w <= cp->w_last ? cp->stone_ia[(size_t)k * cp->W + w] : -1;
-  };
-  auto write_stone = [&]() {  // (the stones below the window range are walked past, not written)
-    const ColdParams32 cp = cold_params<PaintParams>();
-    if (wa >= cp->w_first) {
-      const size_t N = cp->lay.N, row = (size_t)(wa - cp->w_first) * cp->nloc + (k - cp->k0);
-      emit_stone32<S>(pl, a, cp->alpha + row * N, 0.0f, stage);
-      if (pl.lane == 0 && wv == 0) cp->ls_alpha[row] = (float)ls;
-    }
-    wa++;
-  };
-  int next_stone = stone_index(0);
+  int wa = 0, next_stone = forward_stone_index(k, 0);
   while (next_stone == 0) {
-    write_stone();
-    next_stone = stone_index(wa);
+    write_forward_stone<S>(wa, pl, wv, a, ls, stage);
+    next_stone = forward_stone_index(k, wa);
   }
   double cfac = cfp[0] * ssum;  // :260
 
-  int s1 = D > 1 ? st[1] : 0, s2 = D > 2 ? st[2] : 0;
-  uint32_t touched = 0;
+  ForwardRows<S, WAVES> pipe(st, D, 1);
   float K1 = (float)c.K1;
   asm volatile("" : "+v"(K1));
   constexpr int CH = (S % 16 == 0 && RL32_FWD_CH == 16) ? 16 : 8;  // mask words (= donors per lane) per chunk
   typedef typename MaskChunk<CH>::type Chunk;
-  MaskRow row = site_row(p.masks, S, p.L, s1, WAVES, wv);
+  MaskRow row = pipe.row(p, wv);
   Chunk first = load_masks<CH>(row, 0);
   for (int i = 1; i < D; i++) {
-    retire_touch(touched);
-    if (i + 1 < D) touched = touch_row(p.masks, S, s2, pl.lane, WAVES, wv);
-    s1 = s2;
-    if (i + 2 < D) s2 = st[i + 2];
+    pipe.retire();
+    pipe.advance(p, i, pl.lane, wv);
     const double nx_i = nx[i - 1], cf_i = cfp[i];
     const float cf32 = (float)cfac;
     set_slot32<S>(a, pl.jk, pl.kbit, -cf32);  // donor k: (-c) + c = +0.0
@@ -308,10 +251,10 @@ RL_DEV void paint32_forward(const PaintParams &p, int k, float *stage, WaveLink<
         sb += v[q + 1];
       }
     });
-    row = site_row(p.masks, S, p.L, s1, WAVES, wv);
+    row = pipe.row(p, wv);
     first = load_masks<CH>(row, 0);
     sa += sb;
-    ssum = lanes_total<S, WAVES>((double)sa.x + (double)sa.y, lk);
+    ssum = lanes_total((double)sa.x + (double)sa.y, lk);
     ls += nx_i;  // :281-282
     cfac = ssum;
     if (cfac < c.lower || cfac > c.upper) {  // :334-347
@@ -323,11 +266,11 @@ RL_DEV void paint32_forward(const PaintParams &p, int k, float *stage, WaveLink<
     }
     cfac *= cf_i;  // :349-352
     while (next_stone == i) {  // :354-374
-      write_stone();
-      next_stone = stone_index(wa);
+      write_forward_stone<S>(wa, pl, wv, a, ls, stage);
+      next_stone = forward_stone_index(k, wa);
     }
   }
-  retire_touch(touched);
+  pipe.retire();
 }
 
 template <int S, int TAIL, int WAVES>
@@ -357,24 +300,10 @@ RL_DEV void paint32_backward(const PaintParams &p, int k, float *stage, WaveLink
   }
   set_slot32<S>(b, pl.jk, pl.kbit, 0.0f);
   double bsum = p.binit[k];
-  int we = p.W - 1;
-  auto stone_index = [&](int w) {
-    const ColdParams32 cp = cold_params<PaintParams>();
-    return w >= cp->w_first ? cp->stone_ie[(size_t)k * cp->W + w] : -2;
-  };
-  auto write_stone = [&](float self_value) {  // (the stones above the window range are walked past, not written)
-    const ColdParams32 cp = cold_params<PaintParams>();
-    if (we <= cp->w_last) {
-      const size_t N = cp->lay.N, row = (size_t)(we - cp->w_first) * cp->nloc + (k - cp->k0);
-      emit_stone32<S>(pl, b, cp->beta + row * N, self_value, stage);
-      if (pl.lane == 0 && wv == 0) cp->ls_beta[row] = (float)ls;
-    }
-    we--;
-  };
-  int next_stone = stone_index(we);
+  int we = p.W - 1, next_stone = backward_stone_index(k, we);
   while (next_stone == D - 1) {
-    write_stone(1.0f);
-    next_stone = stone_index(we);
+    write_backward_stone<S>(we, pl, wv, b, ls, 1.0f, stage);  // beta[k] = 1 at the last SNP
+    next_stone = backward_stone_index(k, we);
   }
   double cfac = cfp[D - 1] * bsum;  // :454-455
 
@@ -432,7 +361,7 @@ RL_DEV void paint32_backward(const PaintParams &p, int k, float *stage, WaveLink
     firstn = load_masks<BCH>(rown, 0);
     firsth = load_masks<BCH>(rowh, 0);
     const double lane_all = (double)sall.x + (double)sall.y, lane_mis = (double)smis0 + (double)smis1;
-    bsum = lanes_total<S, WAVES>(ntheta * lane_all + (theta - ntheta) * lane_mis, lk);
+    bsum = lanes_total(ntheta * lane_all + (theta - ntheta) * lane_mis, lk);
     ls += nx_j;  // :471-472
     cfac = bsum;
     if (cfac < c.lower || cfac > c.upper) {  // :538-551
@@ -444,8 +373,8 @@ RL_DEV void paint32_backward(const PaintParams &p, int k, float *stage, WaveLink
     }
     cfac *= cf_j;  // :553-556
     while (next_stone == j) {  // :559-578
-      write_stone(0.0f);
-      next_stone = stone_index(we);
+      write_backward_stone<S>(we, pl, wv, b, ls, 0.0f, stage);
+      next_stone = backward_stone_index(k, we);
     }
   }
   retire_touch(touched);
@@ -456,9 +385,7 @@ template <int S, int TAIL, int WAVES, int DIR>
 __global__ void __launch_bounds__(64 * WAVES, WAVES == 1 ? RL32_WAVES_PER_SIMD : RL32_WAVES_PER_SIMD / 2) paint32_kernel(const PaintParams p) {
   __shared__ float stage[WAVES][16 * 64];
   __shared__ WaveLinkStorage link;
-  WaveLink<WAVES> lk;
-  lk.s = &link;
-  lk.w = WAVES > 1 ? __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)) : 0;
+  WaveLink<WAVES> lk = make_wave_link<WAVES>(&link);
   int b = blockIdx.x;
   bool backward = DIR == 1;
   if (DIR == 2) {
@@ -472,40 +399,13 @@ __global__ void __launch_bounds__(64 * WAVES, WAVES == 1 ? RL32_WAVES_PER_SIMD :
     paint32_forward<S, TAIL, WAVES>(p, k, stage[lk.w], lk);
 }
 
-template <int S, int TAIL, int WAVES>
-static hipError_t launch_paint32_t(const PaintParams &p, int dir, hipStream_t stream) {
-  const dim3 grid(dir == 2 ? 2 * p.nloc : p.nloc), block(64 * WAVES);
-  if (dir == 2)
-    hipLaunchKernelGGL((paint32_kernel<S, TAIL, WAVES, 2>), grid, block, 0, stream, p);
-  else if (dir == 1)
-    hipLaunchKernelGGL((paint32_kernel<S, TAIL, WAVES, 1>), grid, block, 0, stream, p);
-  else
-    hipLaunchKernelGGL((paint32_kernel<S, TAIL, WAVES, 0>), grid, block, 0, stream, p);
-  return hipGetLastError();
-}
-
 template <>
-hipError_t launch_paint_mode<3>(const PaintParams &p, int S, int waves, int dir, hipStream_t stream) {
-  if (waves == 1) {
-    switch (S) {
-#define RL_CASE(s, t) \
-  case s:             \
-    return launch_paint32_t<s, t, 1>(p, dir, stream);
-      RL_FOR_EACH_S(RL_CASE)
-#undef RL_CASE
-    }
-  } else if (waves == 2) {
-#ifndef RL_ONLY_S
-    switch (S) {
-#define RL_CASE(s, t) \
-  case s:             \
-    return launch_paint32_t<s, t, 2>(p, dir, stream);
-      RL_FOR_EACH_S_2WAVES(RL_CASE)
-#undef RL_CASE
-    }
-#endif
-  }
-  return hipErrorInvalidValue;
+hipError_t launch_paint_mode<3>(const PaintParams &p, int tile, int waves, int dir, hipStream_t stream) {
+  return dispatch_tile(tile, waves, [&](auto s, auto t, auto w) {
+    constexpr int S = s(), TAIL = t(), WAVES = w();
+    const auto kernel_of = [](auto d) { return &paint32_kernel<S, TAIL, WAVES, decltype(d)::value>; };
+    return launch_paint_dir(kernel_of, p, WAVES, dir, stream);
+  });
 }
 
 }  // namespace rl

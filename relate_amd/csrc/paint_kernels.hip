@@ -2,13 +2,15 @@
 //
 // Replaces FastPainting::PaintSteppingStones (fast_painting.cpp:18-618).
 // The two directions are independent in this stage: by default ONE launch of
-// 2N workgroups paints both (block 2i the backward pass of target order[i],
-// block 2i+1 its forward pass; longest target first), so that the last round
-// of workgroups of one direction does not leave the chip half empty while the
-// other direction waits.  DIR = 0 / 1 launch one direction alone (profiling).
+// 2N workgroups paints both (blocks 0 .. N-1 the backward passes, blocks
+// N .. 2N-1 the forward passes; longest target first in each), so that the last
+// round of workgroups of one direction does not leave the chip half empty while
+// the other direction waits.  DIR = 0 / 1 launch one direction alone (profiling).
+// The forward step body and row pipeline and the stones are paint_pass.h,
+// shared with paint32_kernels.hip and repaint_kernels.hip; the backward pass
+// keeps its own (DESIGN_NOTES.md 13).
 #include <cstdlib>
-#include "paint_device.h"
-#include "exact_sum.h"
+#include "paint_pass.h"
 #include "launch.h"
 
 #ifndef RL_MODE
@@ -16,35 +18,6 @@
 #endif
 
 namespace rl {
-
-// Write the lane's registers as one stepping stone in donor order.  Stones
-// are rare (W per target against D_k steps); to keep S per-register store
-// addresses out of the hot loop's register budget the registers are staged,
-// 16 at a time, through a 4 KiB LDS strip private to the wave and written by a
-// rolled loop (each lane reads back only what it wrote: no barrier needed).
-// The slot of donor k itself (held at +0.0) is written as self_value.
-template <int S>
-RL_DEV void emit_stone(const PaintLane<S> &pl, const double (&v)[S], float *__restrict__ out,
-                       float self_value, float *stage) {
-  static_assert(S % 8 == 0, "S must be a multiple of 8");
-  constexpr int R = S % 16 == 0 ? 16 : 8;
-#pragma unroll
-  for (int c = 0; c < S / R; c++) {
-#pragma unroll
-    for (int ii = 0; ii < R; ii++) {
-      // pin the conversion to its chunk: hoisted, all S floats would be live at once
-      double x = v[c * R + ii];
-      asm volatile("" : "+v"(x) : : "memory");
-      stage[ii * 64 + pl.lane] = (float)x;
-    }
-#pragma clang loop unroll(disable)
-    for (int ii = 0; ii < R; ii++) {
-      const int i = c * R + ii;
-      const int n = pl.start + i;
-      if (i < pl.len) out[n] = (n == pl.k) ? self_value : stage[ii * 64 + pl.lane];
-    }
-  }
-}
 
 // experiment builds (-DRL_STATS): per-segment cycle counters of the forward step, lanes mode
 #ifdef RL_STATS
@@ -55,20 +28,14 @@ RL_DEV void emit_stone(const PaintLane<S> &pl, const double (&v)[S], float *__re
 #define RL_TOCK(acc, a, b) do { } while (0)
 #endif
 
-typedef const __attribute__((address_space(4))) PaintParams *ColdParams;
-
 template <int S, int TAIL, int MODE, int WAVES>
 RL_DEV void paint_forward(const PaintParams &p, int k, float *stage, WaveLink<WAVES> &lk) {
   const int wv = lk.w;  // this wave of the target's workgroup (wave-uniform)
   PaintLane<S> pl;
   pl.init(p.lay, k, wv);
   const PaintConsts &c = p.c;
-  const int64_t off = p.plan_off[k];
-  const int D = forward_steps(k, (int)(p.plan_off[k + 1] - off));  // (paint_device.h: ends at the range's last stone)
-  // the plan arrays come in by vector loads (vmcnt), requested a step ahead
-  const int32_t *__restrict__ st = p.sites + off;
-  const double *__restrict__ cfp = p.cf + off;
-  const double *__restrict__ nx = p.nxt + off;
+  const auto [Dk, st, cfp, nx] = plan_slice(p, k);
+  const int D = forward_steps(k, Dk);  // (paint_device.h: ends at the range's last stone)
 
   double a[S];
 
@@ -85,72 +52,33 @@ RL_DEV void paint_forward(const PaintParams &p, int k, float *stage, WaveLink<WA
   set_slot<S>(a, pl.jk, pl.kbit, 0.0);
   double ssum = wave_sum<MODE, S, WAVES>(RegTerm<S>{a, 0.0, 0.0, p.stats}, local_sum<S>(RegTerm<S>{a}), lk);
   double ls = 0.0;
-  int wa = 0;
-  // stone wa of the target: written when the visited index reaches stone_ia[k][wa] (:354-374)
-  auto stone_index = [&](int w) {
-    const ColdParams cp = cold_params<PaintParams>();
-    return w <= cp->w_last ? cp->stone_ia[(size_t)k * cp->W + w] : -1;
-  };
-  auto write_stone = [&]() {  // (the stones below the window range are walked past, not written)
-    const ColdParams cp = cold_params<PaintParams>();
-    if (wa >= cp->w_first) {
-      const size_t N = cp->lay.N, row = (size_t)(wa - cp->w_first) * cp->nloc + (k - cp->k0);
-      emit_stone<S>(pl, a, cp->alpha + row * N, 0.0f, stage);
-      if (pl.lane == 0 && wv == 0) cp->ls_alpha[row] = (float)ls;
-    }
-    wa++;
-  };
-  int next_stone = stone_index(0);
+  int wa = 0, next_stone = forward_stone_index(k, 0);
   while (next_stone == 0) {
-    write_stone();
-    next_stone = stone_index(wa);
+    write_forward_stone<S>(wa, pl, wv, a, ls, stage);
+    next_stone = forward_stone_index(k, wa);
   }
   double cfac = cfp[0] * ssum;  // :260
 
-  // row pipeline: step i reads the row of s1 with scalar loads, its first
-  // chunk requested before the previous step's sum; the row of s2 (step i+1) is
-  // pulled into L2 by a vector load during step i
-  int s1 = D > 1 ? st[1] : 0, s2 = D > 2 ? st[2] : 0;
-  uint32_t touched = 0;
+  ForwardRows<S, WAVES> pipe(st, D, 1);
   const double K1 = in_vgpr(c.K1);
   constexpr int CH = S % 16 == 0 ? 16 : 8;  // registers per chunk of masks
   typedef typename MaskChunk<CH>::type Chunk;
-  MaskRow row = site_row(p.masks, S, p.L, s1, WAVES, wv);
+  MaskRow row = pipe.row(p, wv);
   Chunk first = load_masks<CH>(row, 0);
   unsigned long long seg1 = 0, seg2 = 0, seg3 = 0, seg4 = 0, seg5 = 0;
   (void)seg1; (void)seg2; (void)seg3; (void)seg4; (void)seg5;
   for (int i = 1; i < D; i++) {
     RL_TICK(0);
-    retire_touch(touched);
+    pipe.retire();
     RL_TICK(1);
-    if (i + 1 < D) touched = touch_row(p.masks, S, s2, pl.lane, WAVES, wv);
-    s1 = s2;
-    if (i + 2 < D) s2 = st[i + 2];
+    pipe.advance(p, i, pl.lane, wv);
     // requested here, used after the sum: the chunk loop's waits cover the latency
     const double nx_i = nx[i - 1], cf_i = cfp[i];
     set_slot<S>(a, pl.jk, pl.kbit, -cfac);  // donor k: (-c) + c = +0.0
-    double lsum = 0.0;
     RL_TICK(2);
-    for_each_chunk_from<S, CH>(row, first, [&](int j0, const Chunk &m) {  // :288-295
-      double v[CH];
-#pragma unroll
-      for (int jj = 0; jj < CH; jj++) {
-        v[jj] = a[j0 + jj];
-        if (j0 + jj < S - TAIL)
-          v[jj] = v[jj] + cfac;
-        else
-          tail_add(v[jj], pl.len, j0 + jj, cfac);  // slots past the lane's run stay +0.0
-      }
-      masked_mul8<0>(v, m, K1);  // v *= (mismatch ? K1 : 1.0)
-      if constexpr (CH == 16) masked_mul8<8>(v + 8, m, K1);
-#pragma unroll
-      for (int jj = 0; jj < CH; jj++) {
-        a[j0 + jj] = v[jj];
-        lsum += v[jj];  // the lane's share of the serial sum (:300-303)
-      }
-    });
+    const double lsum = forward_update<S, TAIL, CH>(a, row, first, pl.len, cfac, K1);  // :288-295
     RL_TICK(3);
-    row = site_row(p.masks, S, p.L, s1, WAVES, wv);
+    row = pipe.row(p, wv);
     first = load_masks<CH>(row, 0);
     ssum = wave_sum<MODE, S, WAVES>(RegTerm<S>{a, 0.0, 0.0, p.stats}, lsum, lk);
     RL_TICK(4);
@@ -166,11 +94,11 @@ RL_DEV void paint_forward(const PaintParams &p, int k, float *stage, WaveLink<WA
     RL_TICK(5);
     RL_TOCK(seg1, 0, 1); RL_TOCK(seg2, 1, 2); RL_TOCK(seg3, 2, 3); RL_TOCK(seg4, 3, 4); RL_TOCK(seg5, 4, 5);
     while (next_stone == i) {  // :354-374
-      write_stone();
-      next_stone = stone_index(wa);
+      write_forward_stone<S>(wa, pl, wv, a, ls, stage);
+      next_stone = forward_stone_index(k, wa);
     }
   }
-  retire_touch(touched);
+  pipe.retire();
 #ifdef RL_STATS
   if (MODE != 0 && p.stats && pl.lane == 0 && wv == 0) {  // whole step | chunk loop | sum | rescale test + factor
     atomicAdd(&p.stats[16], seg1 + seg2 + seg3 + seg4 + seg5);
@@ -190,11 +118,7 @@ RL_DEV void paint_backward(const PaintParams &p, int k, float *stage, WaveLink<W
   PaintLane<S> pl;
   pl.init(p.lay, k, wv);
   const PaintConsts &c = p.c;
-  const int64_t off = p.plan_off[k];
-  const int D = ((int)(p.plan_off[k + 1] - off));
-  const int32_t *__restrict__ st = p.sites + off;
-  const double *__restrict__ cfp = p.cf + off;
-  const double *__restrict__ nx = p.nxt + off;
+  const auto [D, st, cfp, nx] = plan_slice(p, k);
 
   double b[S];
 
@@ -208,24 +132,10 @@ RL_DEV void paint_backward(const PaintParams &p, int k, float *stage, WaveLink<W
   }
   set_slot<S>(b, pl.jk, pl.kbit, 0.0);  // written as beta[k] = 1 below, +0.0 from then on
   double bsum = p.binit[k];  // serial sum of theta/ntheta minus ntheta (:421-431)
-  int we = p.W - 1;
-  auto stone_index = [&](int w) {
-    const ColdParams cp = cold_params<PaintParams>();
-    return w >= cp->w_first ? cp->stone_ie[(size_t)k * cp->W + w] : -2;
-  };
-  auto write_stone = [&](float self_value) {  // (the stones above the window range are walked past, not written)
-    const ColdParams cp = cold_params<PaintParams>();
-    if (we <= cp->w_last) {
-      const size_t N = cp->lay.N, row = (size_t)(we - cp->w_first) * cp->nloc + (k - cp->k0);
-      emit_stone<S>(pl, b, cp->beta + row * N, self_value, stage);
-      if (pl.lane == 0 && wv == 0) cp->ls_beta[row] = (float)ls;
-    }
-    we--;
-  };
-  int next_stone = stone_index(we);
+  int we = p.W - 1, next_stone = backward_stone_index(k, we);
   while (next_stone == D - 1) {
-    write_stone(1.0f);  // beta[k] = 1 at the last SNP
-    next_stone = stone_index(we);
+    write_backward_stone<S>(we, pl, wv, b, ls, 1.0f, stage);  // beta[k] = 1 at the last SNP
+    next_stone = backward_stone_index(k, we);
   }
   double cfac = cfp[D - 1] * bsum;  // :454-455
 
@@ -296,8 +206,8 @@ RL_DEV void paint_backward(const PaintParams &p, int k, float *stage, WaveLink<W
     RL_TICK(4);
     RL_TOCK(bseg1, 0, 1); RL_TOCK(bseg2, 1, 2); RL_TOCK(bseg3, 2, 3); RL_TOCK(bseg4, 3, 4);
     while (next_stone == j) {  // :559-578
-      write_stone(0.0f);
-      next_stone = stone_index(we);
+      write_backward_stone<S>(we, pl, wv, b, ls, 0.0f, stage);
+      next_stone = backward_stone_index(k, we);
     }
   }
   retire_touch(touched);
@@ -316,12 +226,12 @@ template <int S, int TAIL, int MODE, int WAVES, int DIR>
 __global__ void __launch_bounds__(64 * WAVES, 2) paint_kernel(const PaintParams p) {
   __shared__ float stage[WAVES][16 * 64];
   __shared__ WaveLinkStorage link;
-  WaveLink<WAVES> lk;
-  lk.s = &link;
-  lk.w = WAVES > 1 ? __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)) : 0;
+  WaveLink<WAVES> lk = make_wave_link<WAVES>(&link);
   int b = blockIdx.x;
   bool backward = DIR == 1;
   if (DIR == 2) {
+    // (merge_order is always 0: backward blocks first.  The dead branch stays: without it the register allocator
+    //  gives this kernel 68 B of scratch at S >= 32, DESIGN_NOTES.md 13)
     if (p.merge_order == 1) {
       backward = !(b & 1);
       b >>= 1;
@@ -353,41 +263,13 @@ __global__ void __launch_bounds__(64 * WAVES, 2) paint_kernel(const PaintParams 
 #endif
 }
 
-template <int S, int TAIL, int WAVES>
-static hipError_t launch_paint_t(const PaintParams &p, int dir, hipStream_t stream) {
-  const dim3 grid(dir == 2 ? 2 * p.nloc : p.nloc), block(64 * WAVES);
-  const int lds = 0;
-  if (dir == 2)
-    hipLaunchKernelGGL((paint_kernel<S, TAIL, RL_MODE, WAVES, 2>), grid, block, lds, stream, p);
-  else if (dir == 1)
-    hipLaunchKernelGGL((paint_kernel<S, TAIL, RL_MODE, WAVES, 1>), grid, block, lds, stream, p);
-  else
-    hipLaunchKernelGGL((paint_kernel<S, TAIL, RL_MODE, WAVES, 0>), grid, block, lds, stream, p);
-  return hipGetLastError();
-}
-
 template <>
-hipError_t launch_paint_mode<RL_MODE>(const PaintParams &p, int S, int waves, int dir, hipStream_t stream) {
-  if (waves == 1) {
-    switch (S) {
-#define RL_CASE(s, t) \
-  case s:             \
-    return launch_paint_t<s, t, 1>(p, dir, stream);
-      RL_FOR_EACH_S(RL_CASE)
-#undef RL_CASE
-    }
-  } else if (waves == 2) {
-#ifndef RL_ONLY_S
-    switch (S) {
-#define RL_CASE(s, t) \
-  case s:             \
-    return launch_paint_t<s, t, 2>(p, dir, stream);
-      RL_FOR_EACH_S_2WAVES(RL_CASE)
-#undef RL_CASE
-    }
-#endif
-  }
-  return hipErrorInvalidValue;
+hipError_t launch_paint_mode<RL_MODE>(const PaintParams &p, int tile, int waves, int dir, hipStream_t stream) {
+  return dispatch_tile(tile, waves, [&](auto s, auto t, auto w) {
+    constexpr int S = s(), TAIL = t(), WAVES = w();
+    const auto kernel_of = [](auto d) { return &paint_kernel<S, TAIL, RL_MODE, WAVES, decltype(d)::value>; };
+    return launch_paint_dir(kernel_of, p, WAVES, dir, stream);
+  });
 }
 
 }  // namespace rl

@@ -10,11 +10,13 @@
 // pass reads it back, two chunks of registers ahead of their use, and writes the
 // posterior rows `topology = float(alpha*beta)` in the same register-major
 // layout (4 B per donor per visited site: the kernel is HBM-bound).
+// The forward step body and row pipeline are K1's (paint_pass.h); the backward
+// ones, the rescale blocks, side records, checkpoints, HeldRow and product_*
+// are this file's own.
 #include <algorithm>
 #include <atomic>
 
-#include "paint_device.h"
-#include "exact_sum.h"
+#include "paint_pass.h"
 #include "launch.h"
 
 #ifndef RL_MODE
@@ -83,11 +85,7 @@ RL_DEV void repaint_forward(const RepaintParams &p, int n, float *stage, WaveLin
   const PaintConsts &c = p.c;
   const int t = n - p.k0;  // index into the per-target arrays of this context
   const int ib = p.ib[t], ie = p.ie[t];
-  const int D = ie - ib + 1;
-  const int64_t off = p.plan_off[n] + ib;
-  const int32_t *__restrict__ st = p.sites + off;
-  const double *__restrict__ cfp = p.cf + off;
-  const double *__restrict__ nx = p.nxt + off;
+  const auto [D, st, cfp, nx] = plan_slice(p, n, ib, ie - ib + 1);
   const double cf_last = p.cf_last[t];
   constexpr int CK = REPAINT_CHECKPOINT;
   constexpr int ROW = S * 64 * WAVES;  // a checkpoint row: [wave][register][lane]
@@ -128,42 +126,21 @@ RL_DEV void repaint_forward(const RepaintParams &p, int n, float *stage, WaveLin
     side[(size_t)f0 * REPAINT_SIDE + 1] = 0.0;
     side[(size_t)f0 * REPAINT_SIDE + 2] = (double)lsf;
   }
-  int s1 = D > f0 + 1 ? st[f0 + 1] : 0, s2 = D > f0 + 2 ? st[f0 + 2] : 0;  // row pipeline as in paint_forward
-  uint32_t touched = 0;
-  MaskRow row = site_row(p.masks, S, p.L, s1, WAVES, wv);
+  ForwardRows<S, WAVES> pipe(st, D, f0 + 1);
+  MaskRow row = pipe.row(p, wv);
   Chunk first = load_masks<CH>(row, 0);
   // (a later launch of a bounded window: rows from row_hi on are of no use to the backward pass)
   const int Dfwd = p.partial ? min(D, max(1, (int)p.row_hi[t])) : D;
   const int ck_from = p.partial ? (int)p.row_lo[t] : 0;
   for (int i = f0 + 1; i < Dfwd; i++) {
-    retire_touch(touched);
-    if (i + 1 < D) touched = touch_row(p.masks, S, s2, pl.lane, WAVES, wv);
-    s1 = s2;
-    if (i + 2 < D) s2 = st[i + 2];
+    pipe.retire();
+    pipe.advance(p, i, pl.lane, wv);
     const double nx_i = nx[i - 1], cf_i = (i == D - 1 ? cf_last : cfp[i]);
     const double cfac_used = cfac;
     double divisor = 0.0;
     set_slot<S>(a, pl.jk, pl.kbit, -cfac);  // the target's own slot: (-c) + c = +0.0
-    double lsum = 0.0;
-    for_each_chunk_from<S, CH>(row, first, [&](int j0, const Chunk &m) {
-      double v[CH];
-#pragma unroll
-      for (int jj = 0; jj < CH; jj++) {
-        v[jj] = a[j0 + jj];
-        if (j0 + jj < S - TAIL)
-          v[jj] = v[jj] + cfac;
-        else
-          tail_add(v[jj], pl.len, j0 + jj, cfac);
-      }
-      masked_mul8<0>(v, m, K1);  // v *= (mismatch ? K1 : 1.0)
-      if constexpr (CH == 16) masked_mul8<8>(v + 8, m, K1);
-#pragma unroll
-      for (int jj = 0; jj < CH; jj++) {
-        a[j0 + jj] = v[jj];
-        lsum += v[jj];
-      }
-    });
-    row = site_row(p.masks, S, p.L, s1, WAVES, wv);
+    const double lsum = forward_update<S, TAIL, CH>(a, row, first, pl.len, cfac, K1);
+    row = pipe.row(p, wv);
     first = load_masks<CH>(row, 0);
     ssum = wave_sum<MODE, S, WAVES>(RegTerm<S>{a}, lsum, lk);
     prev_ls += nx_i;
@@ -195,7 +172,7 @@ RL_DEV void repaint_forward(const RepaintParams &p, int n, float *stage, WaveLin
       }
     }
   }
-  retire_touch(touched);
+  pipe.retire();
 }
 
 // ---------------- K2b: the backward pass of one target (:887-1073) and its posterior rows
@@ -317,11 +294,10 @@ RL_DEV void repaint_backward(const RepaintParams &p, int n, float *stage, double
   const PaintConsts &c = p.c;
   const int t = n - p.k0;
   const int ib = p.ib[t], ie = p.ie[t];
-  const int D = ie - ib + 1;
-  const int64_t off = p.plan_off[n] + ib;
-  const int32_t *__restrict__ st = p.sites + off;
-  const double *__restrict__ cfp = p.cf + off;
-  const double *__restrict__ nx = p.nxt + off;
+  const PlanSlice ps = plan_slice(p, n, ib, ie - ib + 1);
+  const int D = ps.D;
+  const int32_t *st = ps.st;  // (the lambdas below capture them)
+  const double *cfp = ps.cfp, *nx = ps.nx;
   const double cf_last = p.cf_last[t], nxt_last = p.nxt_last[t];
   constexpr int CK = REPAINT_CHECKPOINT;
   constexpr int ROW = S * 64 * WAVES;
@@ -524,9 +500,7 @@ template <int S, int TAIL, int MODE, int WAVES>
 __global__ void __launch_bounds__(64 * WAVES, 2) repaint_fwd_kernel(const RepaintParams p) {
   __shared__ float stage[WAVES][16 * 64];
   __shared__ WaveLinkStorage link;
-  WaveLink<WAVES> lk;
-  lk.s = &link;
-  lk.w = WAVES > 1 ? __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)) : 0;
+  WaveLink<WAVES> lk = make_wave_link<WAVES>(&link);
   repaint_forward<S, TAIL, MODE, WAVES>(p, p.order[blockIdx.x], stage[lk.w], lk);
 }
 // One wave per SIMD (the LDS strips decide that): beta in registers, the block's checkpoint row in LDS.  The strips
@@ -539,9 +513,7 @@ template <int S, int TAIL, int MODE, int WAVES>
 __global__ void __launch_bounds__(64 * WAVES, 2) repaint_bwd_kernel(const RepaintParams p) {
   extern __shared__ double strips[];  // [WAVES][strip]: stage (16 * 64 floats) first, then the held checkpoint row
   __shared__ WaveLinkStorage link;
-  WaveLink<WAVES> lk;
-  lk.s = &link;
-  lk.w = WAVES > 1 ? __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)) : 0;
+  WaveLink<WAVES> lk = make_wave_link<WAVES>(&link);
   double *strip = strips + lk.w * strip_doubles<S>();
   repaint_backward<S, TAIL, MODE, WAVES>(p, p.order[blockIdx.x], (float *)strip, strip, lk);
 }
@@ -551,9 +523,7 @@ template <int S, int TAIL, int MODE, int WAVES>
 __global__ void __launch_bounds__(64 * WAVES, 2) repaint_bwd_nostrip_kernel(const RepaintParams p) {
   __shared__ float stage[WAVES][16 * 64];
   __shared__ WaveLinkStorage link;
-  WaveLink<WAVES> lk;
-  lk.s = &link;
-  lk.w = WAVES > 1 ? __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)) : 0;
+  WaveLink<WAVES> lk = make_wave_link<WAVES>(&link);
   repaint_backward<S, TAIL, MODE, WAVES, true>(p, p.order[blockIdx.x], stage[lk.w], nullptr, lk);
 }
 template <int S, int TAIL, int WAVES>
@@ -584,26 +554,7 @@ static hipError_t launch_repaint_t(const RepaintParams &p, hipStream_t stream) {
 
 template <>
 hipError_t launch_repaint_mode<RL_MODE>(const RepaintParams &p, int S, int waves, hipStream_t stream) {
-  if (waves == 1) {
-    switch (S) {
-#define RL_CASE(s, t) \
-  case s:             \
-    return launch_repaint_t<s, t, 1>(p, stream);
-      RL_FOR_EACH_S(RL_CASE)
-#undef RL_CASE
-    }
-  } else if (waves == 2) {
-#ifndef RL_ONLY_S
-    switch (S) {
-#define RL_CASE(s, t) \
-  case s:             \
-    return launch_repaint_t<s, t, 2>(p, stream);
-      RL_FOR_EACH_S_2WAVES(RL_CASE)
-#undef RL_CASE
-    }
-#endif
-  }
-  return hipErrorInvalidValue;
+  return dispatch_tile(S, waves, [&](auto s, auto t, auto w) { return launch_repaint_t<s(), t(), w()>(p, stream); });
 }
 
 }  // namespace rl

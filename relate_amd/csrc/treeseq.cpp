@@ -469,7 +469,7 @@ int rl_treeseq_build(rl_treeseq *ts, int start, int end, rl_matrix_fn matrix, rl
   int num_tree = 1;
   const float val = -std::log(ts->theta / (1.0 - ts->theta));  // :555
   // RELATE_AMD_TIMING=1: where a section's wall-clock goes (stderr)
-  const bool timing = getenv("RELATE_AMD_TIMING") != nullptr;
+  const bool timing = timing_level() >= 1;
   auto now = [] { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
   double t_matrix = 0, t_prior = 0, t_build = 0, t_map = 0, t_mark = 0;
   int builds = 0;
@@ -1074,7 +1074,7 @@ static int build_sections(rl_ctx *ctx, const char *out_dir, int chunk_index, int
   std::atomic<int> open_sections(0);
   int most_open = 0;            // (under g_gpu_mutex)
   const auto stage_t0 = std::chrono::steady_clock::now();
-  if (getenv("RELATE_AMD_TIMING"))
+  if (timing_level() >= 1)
     fprintf(stderr, "[stage] set-up before the section threads (plan, reservations) %.3f s\n",
             std::chrono::duration<double>(stage_t0 - entry_t0).count());
   double reserved_bytes = 0.0;  // (under g_gpu_mutex) HBM promised to windows that are being opened
@@ -1230,7 +1230,7 @@ static int build_sections(rl_ctx *ctx, const char *out_dir, int chunk_index, int
       const double t_open = std::chrono::duration<double>(std::chrono::steady_clock::now() - stage_t0).count();
       if (!r && opt) r = optimize_section(ts, start, end, win, *opt);  // (--mode OptimizeParameters: counts, no files)
       else if (!r) r = rl_treeseq_build(ts, start, end, win_matrix, win_advance, win, flags, fb);
-      if (getenv("RELATE_AMD_TIMING"))  // (when the sections start and end: the stage's ramp and tail)
+      if (timing_level() >= 1)  // (when the sections start and end: the stage's ramp and tail)
         fprintf(stderr, "[section %d] turn %d, %d SNPs: window open %.1f s after the stage began, trees built at %.1f s\n",
                 section, turn, end - start + 1, t_open,
                 std::chrono::duration<double>(std::chrono::steady_clock::now() - stage_t0).count());
@@ -1273,7 +1273,7 @@ static int build_sections(rl_ctx *ctx, const char *out_dir, int chunk_index, int
     // (as rl_stage_find_equivalent_branches: the last stage that reads chunk_<c>.bits removes it)
     if (!rc) (void)remove((od + "/chunk_" + c + ".bits").c_str());
   }
-  if (getenv("RELATE_AMD_TIMING"))
+  if (timing_level() >= 1)
     fprintf(stderr, "[stage] sections %d..%d on %d threads, up to %d open at once, %lld of at most %.0f posterior rows "
             "resident per window, %lld RePaint launches (%.1f s on the device), %s tree builder (%d workers asked for), %.1f s\n",
             first_section, last_section, nthreads, most_open, cap_rows > 0 ? cap_rows : (long long)max_rows, max_rows,
@@ -1281,7 +1281,7 @@ static int build_sections(rl_ctx *ctx, const char *out_dir, int chunk_index, int
             std::chrono::duration<double>(std::chrono::steady_clock::now() - stage_t0).count());
   const auto destroy_t0 = std::chrono::steady_clock::now();
   if (!opt) rl_destroy(ctx);
-  if (getenv("RELATE_AMD_TIMING"))
+  if (timing_level() >= 1)
     fprintf(stderr, "[stage] context released in %.3f s\n",
             std::chrono::duration<double>(std::chrono::steady_clock::now() - destroy_t0).count());
   if (!rc && !opt) {
@@ -1378,7 +1378,7 @@ int rl_stage_paint_build_topology_ex(const char *out_dir, int chunk_index, int f
   const int device = o.device, sum_mode = o.sum_mode, use_painting = o.use_painting;
   const double theta = o.theta, rho = o.rho;
   // RELATE_AMD_TIMING=1: wall-clock of what precedes the sections on stderr
-  const bool timing = getenv("RELATE_AMD_TIMING") != nullptr;
+  const bool timing = timing_level() >= 1;
   auto now = [] { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
   double t0 = now();
   auto lap = [&](const char *what) {
@@ -1469,7 +1469,7 @@ int rl_optimize_section(rl_ctx *ctx, int section, float theta, float rec_factor,
   if (win) rl_window_close(win);
   rl_treeseq_destroy(ts);
   if (!rc) *count = (int)run.count.load();
-  if (!rc && getenv("RELATE_AMD_TIMING"))
+  if (!rc && timing_level() >= 1)
     fprintf(stderr, "[optimize] section %d: %lld trees (%lld on the GPU, %lld on the host)\n", section, run.trees.load(),
             run.gpu_trees.load(), run.host_trees.load());
   return rc;
@@ -1527,7 +1527,7 @@ int rl_stage_optimize_parameters(const char *out_dir, int chunk_index, const flo
       gpu_trees += run.gpu_trees.load();
       host_trees += run.host_trees.load();
     }
-  if (getenv("RELATE_AMD_TIMING")) {
+  if (timing_level() >= 1) {
     const double sec = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     fprintf(stderr, "[optimize] chunk %d: %d grid points, %lld trees (%lld on the GPU, %lld on the host) in %.2f s: %.0f "
             "trees per second; chunk files + Paint %.2f s, plan per grid point %.3f s\n", chunk_index, n_theta * n_factor,

@@ -17,7 +17,7 @@ import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-os.environ["RELATE_AMD_STATS"] = "1"
+os.environ["RELATE_AMD_TEST_STATS"] = "1"
 import bench  # noqa: E402
 from relate_amd import api  # noqa: E402
 
