@@ -167,8 +167,12 @@ int rl_register_tile(const rl_ctx *ctx, int *S, int *waves);
  * (mismatch ? th : nth) * x, read through a lane-mask panel as in the
  * backward passes.  stats8 (may be NULL) receives the path counters of
  * RL_SUM_EXACT, counted per wave: sums, serial fallbacks, walked lanes,
- * multi-binade reruns, then four cycle counts.  Bad arguments: RL_EINVAL
- * before any device work. */
+ * multi-binade reruns, then four cycle counts.  sum_mode may carry
+ * RL_DEBUG_SUM_STASH (with RL_SUM_EXACT and a mismatch array only): the
+ * terms are computed once into the wave's LDS stash and every pass of the sum
+ * reads them back, as the exact backward pass of rl_paint does; geometry and
+ * counters as without it.  Bad arguments: RL_EINVAL before any device work. */
+#define RL_DEBUG_SUM_STASH 0x100
 int rl_debug_wave_sum(const double *x, int n, int batch, int sum_mode, double *out);
 int rl_debug_wave_sum_ex(const double *x, int n, int batch, int rows_per_group, int sum_mode,
                          const uint8_t *mismatch, double th, double nth, double *out,

@@ -16,6 +16,7 @@ RL_SUM_EXACT = 0
 RL_SUM_LANES = 1
 RL_SUM_EXACT_SERIAL = 2
 RL_SUM_LANES32 = 3
+RL_DEBUG_SUM_STASH = 0x100  # rl_debug_wave_sum_ex: or-ed into RL_SUM_EXACT, the terms go through the LDS stash
 
 _lib = None
 
@@ -96,9 +97,12 @@ def device_count():
     return lib().rl_device_count()
 
 
-def debug_wave_sum(x, sum_mode, rows_per_group=1, mismatch=None, th=0.001, nth=0.999):
+def debug_wave_sum(x, sum_mode, rows_per_group=1, mismatch=None, th=0.001, nth=0.999, stash=False):
     """rl_debug_wave_sum_ex: the kernels' sum of each row of x [batch][n] (terms (mismatch ? th : nth) * x if
-    mismatch is given) -> (sums [batch], stats), stats = the RL_SUM_EXACT path counters, counted per wave"""
+    mismatch is given; stash: computed once into the LDS stash of K1's exact backward pass and read back from it)
+    -> (sums [batch], stats), stats = the RL_SUM_EXACT path counters, counted per wave"""
+    if stash:
+        sum_mode |= RL_DEBUG_SUM_STASH
     x = np.ascontiguousarray(x, dtype=np.float64)
     batch, n = x.shape
     if mismatch is not None:

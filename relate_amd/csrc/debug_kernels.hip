@@ -8,7 +8,9 @@
 // WaveLink), and a workgroup sums several arrays back to back on that WaveLink,
 // as a step loop of K1 does.  The terms are the registers themselves (RegTerm,
 // the forward passes) or (mismatch ? th : nth) * x under the EXEC masks of a
-// lane-mask panel (MaskTerm, the backward passes).
+// lane-mask panel (MaskTerm, the backward passes), or those terms computed once
+// into the wave's LDS stash and read back from it by every pass of the sum
+// (StashTerm, K1's exact backward pass).
 //
 // This translation unit alone is compiled with the path counters of exact_sum.h
 // (RL_STATS); the Makefile has no -fgpu-rdc, so the paint and repaint objects
@@ -25,13 +27,18 @@ namespace rl {
 
 constexpr int SUM_STATS = 8;  // exact_sum.h RL_STAT: sums, fallbacks, walked lanes, reruns, then 4 cycle counts
 
-template <int S, int MODE, int WAVES, bool MASK>
+enum { TERM_REG = 0, TERM_MASK = 1, TERM_STASH = 2 };
+
+template <int S, int MODE, int WAVES, int KIND>
 __global__ void __launch_bounds__(64 * WAVES) sum_kernel(const double *__restrict__ x, int n, int rows_per_group,
                                                          const unsigned long long *__restrict__ masks, double th,
                                                          double nth, double *__restrict__ out,
                                                          unsigned long long *__restrict__ stats) {
   __shared__ WaveLinkStorage link;
   __shared__ unsigned long long lstats[SUM_STATS];
+  // the stash of each wave, as in paint_kernel (only the stashing kind has one)
+  constexpr int STASH = KIND == TERM_STASH ? stash_bytes(S) : 16;
+  __shared__ __attribute__((aligned(16))) char stash[WAVES][STASH];
   WaveLink<WAVES> lk = make_wave_link<WAVES>(&link);
   if (threadIdx.x < SUM_STATS) lstats[threadIdx.x] = 0;
   __syncthreads();
@@ -45,7 +52,21 @@ __global__ void __launch_bounds__(64 * WAVES) sum_kernel(const double *__restric
 #pragma unroll
     for (int i = 0; i < S; i++) a[i] = (i < len) ? xb[start + i] : 0.0;
     double sum;
-    if constexpr (MASK) {
+    if constexpr (KIND == TERM_STASH) {
+      // as K1's update loop: every weighted term once, its first KS into the stash, the lane's local sum alongside
+      const MaskRow mrow = (MaskRow)(masks + (row * WAVES + lk.w) * S);
+      const StashPtr sp = stash_of(stash[lk.w]);
+      double L = 0.0;
+      for_each_chunk<S, 4>(mrow, [&](int j0, const u64x4 &m) {
+        double w[4];
+        weighted4(w, a[j0], a[j0 + 1], a[j0 + 2], a[j0 + 3], m, th, nth);
+        if (j0 < stash_terms(S)) stash_put4(sp, j0 / 4, w);
+#pragma unroll
+        for (int jj = 0; jj < 4; jj++) L += w[jj];
+      });
+      const StashTerm<S> t{mrow, a, th, nth, lstats, sp};
+      sum = wave_sum<MODE, S, WAVES>(t, L, lk);
+    } else if constexpr (KIND == TERM_MASK) {
       const MaskTerm<S> t{(MaskRow)(masks + (row * WAVES + lk.w) * S), a, th, nth, lstats};
       sum = wave_sum<MODE, S, WAVES>(t, local_sum<S>(t), lk);
     } else {
@@ -60,12 +81,19 @@ __global__ void __launch_bounds__(64 * WAVES) sum_kernel(const double *__restric
 
 template <int S, int MODE, int WAVES>
 static hipError_t launch_sum_t(const double *x, int n, int groups, int rows_per_group, const unsigned long long *masks,
-                               double th, double nth, double *out, unsigned long long *stats) {
+                               double th, double nth, double *out, unsigned long long *stats, bool stash) {
+  if constexpr (MODE == 1) {  // (the stash exists for the exact order alone)
+    if (stash) {
+      hipLaunchKernelGGL((sum_kernel<S, MODE, WAVES, TERM_STASH>), dim3(groups), dim3(64 * WAVES), 0, nullptr, x, n,
+                         rows_per_group, masks, th, nth, out, stats);
+      return hipGetLastError();
+    }
+  }
   if (masks)
-    hipLaunchKernelGGL((sum_kernel<S, MODE, WAVES, true>), dim3(groups), dim3(64 * WAVES), 0, nullptr, x, n,
+    hipLaunchKernelGGL((sum_kernel<S, MODE, WAVES, TERM_MASK>), dim3(groups), dim3(64 * WAVES), 0, nullptr, x, n,
                        rows_per_group, masks, th, nth, out, stats);
   else
-    hipLaunchKernelGGL((sum_kernel<S, MODE, WAVES, false>), dim3(groups), dim3(64 * WAVES), 0, nullptr, x, n,
+    hipLaunchKernelGGL((sum_kernel<S, MODE, WAVES, TERM_REG>), dim3(groups), dim3(64 * WAVES), 0, nullptr, x, n,
                        rows_per_group, masks, th, nth, out, stats);
   return hipGetLastError();
 }
@@ -73,9 +101,9 @@ static hipError_t launch_sum_t(const double *x, int n, int groups, int rows_per_
 template <int MODE>
 static hipError_t launch_sum(int S, int waves, const double *x, int n, int groups, int rows_per_group,
                              const unsigned long long *masks, double th, double nth, double *out,
-                             unsigned long long *stats) {
+                             unsigned long long *stats, bool stash) {
   return dispatch_tile(S, waves, [&](auto s, auto, auto w) {
-    return launch_sum_t<s(), MODE, w()>(x, n, groups, rows_per_group, masks, th, nth, out, stats);
+    return launch_sum_t<s(), MODE, w()>(x, n, groups, rows_per_group, masks, th, nth, out, stats, stash);
   });
 }
 
@@ -87,6 +115,12 @@ extern "C" int rl_debug_wave_sum_ex(const double *x, int n, int batch, int rows_
   using namespace rl;
   if (!x || !out) {
     set_error("rl_debug_wave_sum_ex: null x or out");
+    return RL_EINVAL;
+  }
+  const bool stash = (sum_mode & RL_DEBUG_SUM_STASH) != 0;
+  if (stash) sum_mode &= ~RL_DEBUG_SUM_STASH;
+  if (stash && (sum_mode != RL_SUM_EXACT || !mismatch)) {
+    set_error("rl_debug_wave_sum_ex: RL_DEBUG_SUM_STASH needs RL_SUM_EXACT and a mismatch array");
     return RL_EINVAL;
   }
   if (n < 1 || n > 2 * 80 * 64) {
@@ -133,7 +167,7 @@ extern "C" int rl_debug_wave_sum_ex(const double *x, int n, int batch, int rows_
   hipError_t e;
   switch (kernel_mode(sum_mode)) {
 #define RL_ARGS S, waves, dx.as<double>(), n, groups, rows_per_group, dm, th, nth, dout.as<double>(), \
-                dstats.as<unsigned long long>()
+                dstats.as<unsigned long long>(), stash
     case 0: e = launch_sum<0>(RL_ARGS); break;
     case 1: e = launch_sum<1>(RL_ARGS); break;
     default: e = launch_sum<2>(RL_ARGS); break;

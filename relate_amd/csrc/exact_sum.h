@@ -113,6 +113,91 @@ struct MaskTerm {  // backward, lane-mask panel: e(i) * beta[i] with the site's 
   }
 };
 
+// K1's backward pass: the update loop has just produced every weighted term (backward4); the first KS of them are
+// kept in a wave-private LDS region instead of being recomputed by each pass of the sum (the chains, a rerun of
+// the walk, the literal fallback) -- 2 VALU, 1.25 SALU and a quarter of a mask chunk per term and pass.  The region
+// is [pair of terms][lane][2] doubles, one ds_write_b128 / ds_read_b128 per lane and pair; a lane reads back only
+// what it wrote, bit for bit, so no barrier is needed and the sum cannot change.  The remaining S - KS terms are
+// recomputed as in MaskTerm.
+//
+// KS: the stash never takes LDS that another wave needs.  A tile's registers allow tile_waves_per_simd(S) waves on
+// a SIMD (tools/kernel_resources.sh); the stash gets that wave's share of the CU's 160 KB less 512 B (WaveLink, the
+// counters of experiment builds, allocation granule), in whole chunks of 4 terms, 36 at the most: 36 of the 80
+// terms at the headline tile (18 KB per wave, eight waves per CU).  (Config #4's tile with all its 32 terms
+// stashed: 16 KB per wave, 10 instead of 16 waves per CU, the Paint 35 % slower.)
+constexpr int STASH_MAX = 36;
+constexpr int LDS_PER_CU = 160 * 1024;
+constexpr int tile_waves_per_simd(int S) { return S <= 8 ? 7 : S <= 16 ? 5 : S <= 32 ? 4 : S <= 48 ? 3 : 2; }
+constexpr int stash_terms(int S) {
+  const int fit = (LDS_PER_CU / (4 * tile_waves_per_simd(S)) - 512) / (64 * (int)sizeof(double));
+  const int ks = fit < S ? fit : S;
+  return (ks < STASH_MAX ? ks : STASH_MAX) / 4 * 4;
+}
+constexpr int stash_bytes(int S) { return stash_terms(S) * 64 * (int)sizeof(double); }
+constexpr int STASH_AHEAD = 2;  // pairs of terms requested ahead of the one in work (StashTerm::for_each)
+typedef double f64x2 __attribute__((ext_vector_type(2)));
+// (may_alias: the region shares storage with the float staging strip of the stones)
+typedef f64x2 __attribute__((may_alias)) StashPair;
+typedef __attribute__((address_space(3))) StashPair *StashPtr;
+// this lane's view of its wave's region (16-byte aligned): pair p = terms 2p, 2p + 1 at sp[64 * p]
+RL_DEV StashPtr stash_of(void *wave_region) { return (StashPtr)wave_region + (threadIdx.x & 63); }
+RL_DEV void stash_put4(StashPtr sp, int chunk, const double (&x)[4]) {
+  StashPair lo, hi;
+  lo.x = x[0]; lo.y = x[1]; hi.x = x[2]; hi.y = x[3];
+  sp[128 * chunk] = lo;
+  sp[128 * chunk + 64] = hi;
+}
+template <int S>
+struct StashTerm {
+  static constexpr bool REG = false;
+  static constexpr int KS = stash_terms(S);
+  MaskRow row;  // mismatch row of the site (S words)
+  const double (&b)[S];
+  double th, nth;
+  unsigned long long *stats = nullptr;
+  StashPtr sp = nullptr;  // terms 0 .. KS-1 as the update loop left them
+  template <typename F>
+  RL_DEV void for_each(double &t, double &n, F &&f) const {
+    constexpr int NP = KS / 2, NS = KS / 4, NC = S / 4, A = STASH_AHEAD;
+    // The LDS reads run A pairs of terms ahead, as the mask loads of for_each_chunk run a chunk ahead: wait for pair
+    // p, request pair p + A, then work on pair p.  (Without the tie to pair p the scheduler requests all KS terms at
+    // once and keeps them.)
+    StashPtr q = sp;
+    MaskRow r = row;
+    asm volatile("" : "+v"(q));  // (the fallback's round loop must not hoist the reads either)
+    StashPair w[A + 1];
+#pragma unroll
+    for (int pr = 0; pr < A && pr < NP; pr++) w[pr] = q[64 * pr];
+    u64x4 m = {0, 0, 0, 0};
+#pragma unroll
+    for (int pr = 0; pr < NP; pr++) {
+      const StashPair &cur = w[pr % (A + 1)];
+      if (pr + A < NP) {
+        asm volatile("" : "+v"(q) : "v"(cur));
+        w[(pr + A) % (A + 1)] = q[64 * (pr + A)];
+      } else if (pr + 1 == NP && NS < NC) {  // no LDS read is left in flight: the masks of the first recomputed chunk
+        asm volatile("" : "+s"(r) : "v"(cur));
+        m = load_masks<4>(r, NS);
+      }
+      f(2 * pr, cur.x);
+      f(2 * pr + 1, cur.y);
+    }
+#pragma unroll
+    for (int c = NS; c < NC; c++) {
+      u64x4 nm = m;
+      if (c + 1 < NC) {
+        asm volatile("" : "+s"(r) : "s"(m[0]));
+        nm = load_masks<4>(r, c + 1);
+      }
+      double x[4];
+      weighted4(x, b[4 * c], b[4 * c + 1], b[4 * c + 2], b[4 * c + 3], m, t, n);
+#pragma unroll
+      for (int jj = 0; jj < 4; jj++) f(4 * c + jj, x[jj]);
+      m = nm;
+    }
+  }
+};
+
 // ---- targets spread over several waves ------------------------------------
 // For N > 5120 the stepping-stone kernel gives a target to a workgroup of
 // WAVES = 2 waves (virtual lanes 0..127, wave w holds lanes 64w..64w+63) so

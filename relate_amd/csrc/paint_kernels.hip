@@ -10,6 +10,7 @@
 // shared with paint32_kernels.hip and repaint_kernels.hip; the backward pass
 // keeps its own (DESIGN_NOTES.md 13).
 #include <cstdlib>
+#include <type_traits>
 #include "paint_pass.h"
 #include "launch.h"
 
@@ -121,6 +122,11 @@ RL_DEV void paint_backward(const PaintParams &p, int k, float *stage, WaveLink<W
   const auto [D, st, cfp, nx] = plan_slice(p, k);
 
   double b[S];
+  // exact: the first KS weighted terms of a step go from the update loop to the sum through LDS (StashTerm,
+  // exact_sum.h), in the wave's strip, which no stone uses during a step
+  constexpr int KS = MODE == 1 ? stash_terms(S) : 0;
+  StashPtr sp = stash_of(stage);  // (not const: kept opaque in place, see the update loop)
+  (void)sp;
 
   // ---- last SNP (:396-448)
   double ls = c.log_Nm1 - D * c.log_ntheta;  // normalizing_constant :399
@@ -149,6 +155,14 @@ RL_DEV void paint_backward(const PaintParams &p, int k, float *stage, WaveLink<W
   const double K1 = in_vgpr(c.K1), theta = in_vgpr(c.theta), ntheta = in_vgpr(c.ntheta);
   unsigned long long bseg1 = 0, bseg2 = 0, bseg3 = 0, bseg4 = 0;
   (void)bseg1; (void)bseg2; (void)bseg3; (void)bseg4;
+  typedef typename std::conditional<MODE == 1, StashTerm<S>, MaskTerm<S>>::type BackwardTerm;
+  const auto make_term = [&](MaskRow row) {
+    unsigned long long *const stats = p.stats ? p.stats + 8 : nullptr;
+    if constexpr (MODE == 1)
+      return BackwardTerm{row, b, theta, ntheta, stats, sp};
+    else
+      return BackwardTerm{row, b, theta, ntheta, stats};
+  };
   const int j_last = backward_last(k);  // (paint_device.h: D and ls above keep the whole pass, the walk ends at the range's first stone)
   for (int j = D - 2; j >= j_last; j--) {
     retire_touch(touched);
@@ -165,9 +179,16 @@ RL_DEV void paint_backward(const PaintParams &p, int k, float *stage, WaveLink<W
     MaskRow vrow = (MaskRow)(p.masks + ((size_t)(p.L + 1) * WAVES + wv) * S);
     asm volatile("" : "+s"(vrow));
     RL_TICK(1);
+    double xp[4] = {0.0, 0.0, 0.0, 0.0};  // exact: the previous chunk's terms on their way to the stash
     for_each_chunk2_tail<S, 4, TAIL>(rown, rowh, vrow, firstn, firsth,
                                      [&](int j0, const u64x4 &mn, const u64x4 &mh, const u64x4 &va) {
       double v[4], x[4];
+      // Stored a chunk late, behind the loop's wait for this chunk's masks and the request of the next: an LDS write
+      // counts on lgkmcnt like the mask loads, and issued at the end of its own chunk it would be waited for at once.
+      if (KS > 0 && j0 > 0 && j0 - 4 < KS) {
+        asm volatile("" : "+v"(sp));  // (pins the store behind the wait)
+        stash_put4(sp, j0 / 4 - 1, xp);
+      }
 #pragma unroll
       for (int jj = 0; jj < 4; jj++) v[jj] = b[j0 + jj];
       if (j0 + 4 <= S - TAIL)
@@ -178,10 +199,12 @@ RL_DEV void paint_backward(const PaintParams &p, int k, float *stage, WaveLink<W
       for (int jj = 0; jj < 4; jj++) {
         b[j0 + jj] = v[jj];
         lsum += x[jj];  // the lane's share of :495-503
+        if (KS > 0 && j0 < KS) xp[jj] = x[jj];
       }
     });
+    if (KS == S) stash_put4(sp, S / 4 - 1, xp);
     RL_TICK(2);
-    const MaskTerm<S> term{rowh, b, theta, ntheta, p.stats ? p.stats + 8 : nullptr};
+    const BackwardTerm term = make_term(rowh);
     rown = rowh;
     rowh = site_row(p.masks, S, p.L, s1, WAVES, wv);
     if (MODE == 0) {  // lanes: the sum reads no masks, request the next step's first chunks across it
@@ -224,7 +247,11 @@ RL_DEV void paint_backward(const PaintParams &p, int k, float *stage, WaveLink<W
 // WAVES = 2: a workgroup of two waves paints one target (N > 5120).
 template <int S, int TAIL, int MODE, int WAVES, int DIR>
 __global__ void __launch_bounds__(64 * WAVES, 2) paint_kernel(const PaintParams p) {
-  __shared__ float stage[WAVES][16 * 64];
+  // per wave: the staging strip of the stones (4 KB) and, where an exact backward pass runs, its stash of weighted
+  // terms (up to 18 KB) in the same storage -- a stone is never written during a sum
+  constexpr int STASH = (MODE == 1 && DIR != 0) ? stash_bytes(S) : 0;
+  constexpr int WAVE_FLOATS = STASH > 16 * 64 * 4 ? STASH / 4 : 16 * 64;
+  __shared__ __attribute__((aligned(16))) float stage[WAVES][WAVE_FLOATS];
   __shared__ WaveLinkStorage link;
   WaveLink<WAVES> lk = make_wave_link<WAVES>(&link);
   int b = blockIdx.x;
