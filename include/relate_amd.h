@@ -143,6 +143,18 @@ int rl_paint(rl_ctx *ctx, int sum_mode, float *kernel_ms);
  * vs :380-586).  split != 0: one launch per direction (backward, then forward),
  * which is what rl_paint_times reports on. */
 int rl_set_paint_split(rl_ctx *ctx, int split);
+/* K1's FP64 kernels come in up to four variants per register tile, fitted to how far the N donors fill it
+ * (relate_amd/csrc/launch.h tile_fit): fit != 0 (the default) runs the one the rule picks for the chunk, fit = 0
+ * always the loose one, which every N of the tile may run.  The stones are the same bit for bit either way; the
+ * switch is there to time and to test the one against the other. */
+int rl_set_paint_fit(rl_ctx *ctx, int fit);
+/* The rule itself, pure host code: the tile of N haplotypes (S, waves as rl_register_tile reports them), the number
+ * `tail` of its last registers that take the backward pass's validity masks and the number `live` of registers that
+ * hold a donor in some lane (S or S - 1).  Any pointer may be NULL.  RL_EINVAL for N < 2 or N > 10240.
+ * This is the rule, not necessarily the kernel launched: rl_set_paint_fit(ctx, 0) overrides it, RL_SUM_LANES32 has
+ * one kernel per tile, and RL_SUM_LANES keeps the loose variant at S = 32 with one wave and S = 64 with two
+ * (launch.h tile_fit_built). */
+int rl_tile_fit(int N, int *S, int *waves, int *tail, int *live);
 /* HIP-event durations of the last rl_paint's two launches (forward kernel,
  * backward kernel), in milliseconds; both 0 unless rl_set_paint_split(ctx, 1). */
 int rl_paint_times(const rl_ctx *ctx, float *fwd_ms, float *bwd_ms);

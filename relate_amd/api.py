@@ -117,6 +117,13 @@ def debug_wave_sum(x, sum_mode, rows_per_group=1, mismatch=None, th=0.001, nth=0
     return out, {"sums": int(st[0]), "fallbacks": int(st[1]), "walked": int(st[2]), "reruns": int(st[3])}
 
 
+def tile_fit(N):
+    """rl_tile_fit: -> (S, waves, tail, live) of K1's register tile for N haplotypes (host code, no GPU)"""
+    s, w, t, l = C.c_int(), C.c_int(), C.c_int(), C.c_int()
+    _check(lib().rl_tile_fit(int(N), C.byref(s), C.byref(w), C.byref(t), C.byref(l)))
+    return s.value, w.value, t.value, l.value
+
+
 class Context:
     """One chunk on one GPU (rl_ctx)."""
 
@@ -209,6 +216,10 @@ class Context:
     def set_paint_split(self, split):
         """one launch per direction (so that paint_times() has something to report) instead of one for both"""
         _check(lib().rl_set_paint_split(C.c_void_p(self._h), int(split)))
+
+    def set_paint_fit(self, fit):
+        """K1 runs the variant of the register tile fitted to N (True, the default) or always the loose one"""
+        _check(lib().rl_set_paint_fit(C.c_void_p(self._h), int(fit)))
 
     @property
     def tile(self):

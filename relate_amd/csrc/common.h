@@ -213,6 +213,7 @@ struct rl_ctx {
   std::atomic<long long> repaint_us{0};        // ... and their time on the device (HIP events), microseconds
   float ms_fwd = 0.f, ms_bwd = 0.f, ms_paint = 0.f;
   int paint_split = 0;  // rl_set_paint_split: one launch per direction instead of one for both
+  int paint_fit = 1;    // rl_set_paint_fit: K1 runs the variant of the register tile that launch.h tile_fit picks (0: the loose one)
 };
 
 namespace rl {

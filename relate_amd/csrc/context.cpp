@@ -1019,8 +1019,8 @@ int rl_paint(rl_ctx *ctx, int sum_mode, float *kernel_ms) {
     // experiment: the two directions as two launches on two streams
     RL_HIP(hipEventRecord(ctx->ev0, ctx->s0));
     RL_HIP(hipStreamWaitEvent(ctx->s1, ctx->ev0, 0));
-    RL_HIP(launch_paint(p, ctx->S, ctx->waves, 1, ctx->s0));
-    RL_HIP(launch_paint(p, ctx->S, ctx->waves, 0, ctx->s1));
+    RL_HIP(launch_paint(p, ctx->S, ctx->waves, 1, ctx->s0, ctx->paint_fit));
+    RL_HIP(launch_paint(p, ctx->S, ctx->waves, 0, ctx->s1, ctx->paint_fit));
     RL_HIP(hipEventRecord(ctx->ev1, ctx->s1));
     RL_HIP(hipStreamWaitEvent(ctx->s0, ctx->ev1, 0));
     RL_HIP(hipEventRecord(ctx->ev2, ctx->s0));
@@ -1030,9 +1030,9 @@ int rl_paint(rl_ctx *ctx, int sum_mode, float *kernel_ms) {
   } else if (ctx->paint_split) {
     // one direction per launch, backward then forward on one stream, each bracketed by HIP events
     RL_HIP(hipEventRecord(ctx->ev0, ctx->s0));
-    RL_HIP(launch_paint(p, ctx->S, ctx->waves, 1, ctx->s0));
+    RL_HIP(launch_paint(p, ctx->S, ctx->waves, 1, ctx->s0, ctx->paint_fit));
     RL_HIP(hipEventRecord(ctx->ev1, ctx->s0));
-    RL_HIP(launch_paint(p, ctx->S, ctx->waves, 0, ctx->s0));
+    RL_HIP(launch_paint(p, ctx->S, ctx->waves, 0, ctx->s0, ctx->paint_fit));
     RL_HIP(hipEventRecord(ctx->ev2, ctx->s0));
     RL_HIP(hipEventSynchronize(ctx->ev2));
     RL_HIP(hipEventElapsedTime(&ctx->ms_bwd, ctx->ev0, ctx->ev1));
@@ -1041,7 +1041,7 @@ int rl_paint(rl_ctx *ctx, int sum_mode, float *kernel_ms) {
   } else {
     // both directions in one launch of 2 * nloc workgroups (paint_kernels.hip)
     RL_HIP(hipEventRecord(ctx->ev0, ctx->s0));
-    RL_HIP(launch_paint(p, ctx->S, ctx->waves, 2, ctx->s0));
+    RL_HIP(launch_paint(p, ctx->S, ctx->waves, 2, ctx->s0, ctx->paint_fit));
     RL_HIP(hipEventRecord(ctx->ev2, ctx->s0));
     RL_HIP(hipEventSynchronize(ctx->ev2));
     RL_HIP(hipEventElapsedTime(&ctx->ms_paint, ctx->ev0, ctx->ev2));
@@ -1071,6 +1071,35 @@ int rl_set_paint_split(rl_ctx *ctx, int split) {
     return RL_EINVAL;
   }
   ctx->paint_split = split;
+  return RL_OK;
+}
+
+int rl_set_paint_fit(rl_ctx *ctx, int fit) {
+  if (!ctx) {
+    set_error("rl_set_paint_fit: no context");
+    return RL_EINVAL;
+  }
+  ctx->paint_fit = fit != 0;
+  return RL_OK;
+}
+
+int rl_tile_fit(int N, int *S, int *waves, int *tail, int *live) {
+  if (N < 2) {
+    set_error("rl_tile_fit: N < 2");
+    return RL_EINVAL;
+  }
+  const int w = target_waves(N);
+  const Layout lay = make_layout(N, w);
+  const int s = choose_S(lay);
+  if (s == 0) {
+    set_error("rl_tile_fit: N exceeds the largest register tile");
+    return RL_EINVAL;
+  }
+  const TileFit f = tile_fit(lay, s);
+  if (S) *S = s;
+  if (waves) *waves = w;
+  if (tail) *tail = f.tail;
+  if (live) *live = f.live;
   return RL_OK;
 }
 

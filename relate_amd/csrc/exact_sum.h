@@ -82,7 +82,9 @@ RL_DEV double pow2_field(int f) { return __longlong_as_double((long long)f << 52
 // sum_exact_fast can use its own opaque copies: otherwise the compiler shares
 // the S selected weights (or the S products) between the passes and keeps them
 // alive in registers.
-template <int S>
+// LIVE (S or S - 1): the registers that hold a donor in some lane; a K1 tile fitted to N (launch.h tile_fit) leaves
+// the last one out of every pass.  Its term would be +0.0, which changes no partial sum.
+template <int S, int LIVE = S>
 struct RegTerm {  // forward: the terms are the alpha registers themselves
   static constexpr bool REG = true;
   const double (&a)[S];
@@ -92,10 +94,10 @@ struct RegTerm {  // forward: the terms are the alpha registers themselves
   template <typename F>
   RL_DEV void for_each(double &, double &, F &&f) const {
 #pragma unroll
-    for (int i = 0; i < S; i++) f(i, a[i]);
+    for (int i = 0; i < LIVE; i++) f(i, a[i]);
   }
 };
-template <int S>
+template <int S, int LIVE = S>
 struct MaskTerm {  // backward, lane-mask panel: e(i) * beta[i] with the site's row words as EXEC masks
   static constexpr bool REG = false;
   MaskRow row;  // mismatch row of the site (S words)
@@ -106,9 +108,13 @@ struct MaskTerm {  // backward, lane-mask panel: e(i) * beta[i] with the site's 
   RL_DEV void for_each(double &t, double &n, F &&f) const {
     for_each_chunk<S, 4>(row, [&](int j0, const u64x4 &m) {
       double x[4];
-      weighted4(x, b[j0], b[j0 + 1], b[j0 + 2], b[j0 + 3], m, t, n);
+      if (j0 + 4 <= LIVE)
+        weighted4(x, b[j0], b[j0 + 1], b[j0 + 2], b[j0 + 3], m, t, n);
+      else
+        weighted3(x, b[j0], b[j0 + 1], b[j0 + 2], m, t, n);
 #pragma unroll
-      for (int jj = 0; jj < 4; jj++) f(j0 + jj, x[jj]);
+      for (int jj = 0; jj < 4; jj++)
+        if (j0 + jj < LIVE) f(j0 + jj, x[jj]);
     });
   }
 };
@@ -147,7 +153,15 @@ RL_DEV void stash_put4(StashPtr sp, int chunk, const double (&x)[4]) {
   sp[128 * chunk] = lo;
   sp[128 * chunk + 64] = hi;
 }
-template <int S>
+// a chunk whose fourth term does not exist (LIVE = S - 1 where the stash holds all S terms, S = 8): its half of the
+// second pair stays unwritten and unread
+RL_DEV void stash_put3(StashPtr sp, int chunk, const double (&x)[4]) {
+  StashPair lo;
+  lo.x = x[0]; lo.y = x[1];
+  sp[128 * chunk] = lo;
+  *(__attribute__((address_space(3))) double __attribute__((may_alias)) *)&sp[128 * chunk + 64] = x[2];
+}
+template <int S, int LIVE = S>
 struct StashTerm {
   static constexpr bool REG = false;
   static constexpr int KS = stash_terms(S);
@@ -180,7 +194,7 @@ struct StashTerm {
         m = load_masks<4>(r, NS);
       }
       f(2 * pr, cur.x);
-      f(2 * pr + 1, cur.y);
+      if (2 * pr + 1 < LIVE) f(2 * pr + 1, cur.y);
     }
 #pragma unroll
     for (int c = NS; c < NC; c++) {
@@ -190,9 +204,13 @@ struct StashTerm {
         nm = load_masks<4>(r, c + 1);
       }
       double x[4];
-      weighted4(x, b[4 * c], b[4 * c + 1], b[4 * c + 2], b[4 * c + 3], m, t, n);
+      if (4 * c + 4 <= LIVE)
+        weighted4(x, b[4 * c], b[4 * c + 1], b[4 * c + 2], b[4 * c + 3], m, t, n);
+      else
+        weighted3(x, b[4 * c], b[4 * c + 1], b[4 * c + 2], m, t, n);
 #pragma unroll
-      for (int jj = 0; jj < 4; jj++) f(4 * c + jj, x[jj]);
+      for (int jj = 0; jj < 4; jj++)
+        if (4 * c + jj < LIVE) f(4 * c + jj, x[jj]);
       m = nm;
     }
   }

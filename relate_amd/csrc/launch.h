@@ -27,6 +27,40 @@ inline int choose_S(const Layout &lay) {
   return 0;
 }
 
+// The tile as K1's FP64 kernels take it for a layout (paint_kernels.hip): which of a tile's instantiations runs.
+//   tail   registers S - tail .. S - 1 take the backward pass's per-lane validity masks.  The tile list's value
+//          (loose: 8 or 16) while q < S - 4; else 4, the backward chunk: one chunk of validity masks per step
+//   live   registers 0 .. live - 1 hold a donor in some lane: S, or S - 1 when need = q + (rem > 0) is S - 1.  The
+//          kernels leave a dead register out of every pass, so it costs neither instructions nor VGPRs
+//   ftail  registers S - ftail .. live - 1 take the forward pass's validity compare (one v_cmp each)
+//   variant  the instantiation: 0 loose (tail, S, tail) -- every layout of the tile may run it, and it is the only
+//          kernel of the tile before the fit --, 1 tight (4, S, 1) for need = S, 2 tight (4, S, 4) for q >= S - 4 with
+//          need <= S - 2, 3 tight minus one (4, S - 1, 2) for need = S - 1
+// (q = S with rem = 0 runs variant 1: its one compare cannot fail.)
+struct TileFit {
+  int tail, live, ftail, variant;
+};
+inline TileFit tile_fit(const Layout &lay, int S, bool fit = true) {
+  const int need = lay.q + (lay.rem > 0 ? 1 : 0);
+  if (!fit || lay.q < S - 4) {
+    int t = 0;
+#define RL_TAIL_OF(s, tl) \
+  if (s == S) t = tl;
+    RL_FOR_EACH_S(RL_TAIL_OF)
+#undef RL_TAIL_OF
+    return {t, S, t, 0};
+  }
+  if (need == S) return {4, S, 1, 1};
+  if (need == S - 1) return {4, S - 1, 2, 3};
+  return {4, S, 4, 2};
+}
+// Two tiles of the `lanes` order keep their loose variant alone: fitted, the kernel of the merged launch comes out
+// of the register allocator with 68 B of scratch per lane (S = 32 with one wave, S = 64 with two; the sensitivity
+// DESIGN_NOTES.md 13 describes).  launch_paint_mode asks before it follows tile_fit, and the variants are not built.
+constexpr bool tile_fit_built(int mode, int S, int waves) {
+  return !(mode == 0 && ((S == 32 && waves == 1) || (S == 64 && waves == 2)));
+}
+
 // the layout of all kernels: all N donors, the target keeps a slot that is pinned to +0.0;
 // cut into 64*waves balanced runs (target_waves)
 inline Layout make_layout(int N, int waves = 1) {
@@ -90,25 +124,38 @@ hipError_t launch_lane_masks(const uint32_t *bits, int row_words, int L, const L
 //   0 = lanes (RL_SUM_LANES), 1 = exact, parallel (RL_SUM_EXACT), 2 = exact, literal serial (RL_SUM_EXACT_SERIAL),
 //   3 = lanes on a packed-FP32 state (RL_SUM_LANES32; K1 only, paint32_kernels.hip -- K2 then runs its `lanes` kernels)
 // dir: 0 forward pass, 1 backward pass, 2 both in one launch of 2 * nloc workgroups
+// fit: K1's FP64 kernels run the tile's instantiation that tile_fit picks for p.lay (1, rl_set_paint_fit's default) or
+// always the loose one (0)
 template <int MODE>
-hipError_t launch_paint_mode(const PaintParams &p, int S, int waves, int dir, hipStream_t stream);
+hipError_t launch_paint_mode(const PaintParams &p, int S, int waves, int dir, hipStream_t stream, int fit);
+// ... each of whose variants is a translation unit of its own (paint_kernels.hip at -DRL_FIT=VARIANT, so that the
+// build compiles them side by side), with its own launcher
+template <int MODE, int VARIANT>
+hipError_t launch_paint_variant(const PaintParams &p, int S, int waves, int dir, hipStream_t stream);
 template <int MODE>
 hipError_t launch_repaint_mode(const RepaintParams &p, int S, int waves, hipStream_t stream);
-template <> hipError_t launch_paint_mode<0>(const PaintParams &, int, int, int, hipStream_t);
-template <> hipError_t launch_paint_mode<1>(const PaintParams &, int, int, int, hipStream_t);
-template <> hipError_t launch_paint_mode<2>(const PaintParams &, int, int, int, hipStream_t);
-template <> hipError_t launch_paint_mode<3>(const PaintParams &, int, int, int, hipStream_t);
+template <> hipError_t launch_paint_mode<0>(const PaintParams &, int, int, int, hipStream_t, int);
+template <> hipError_t launch_paint_mode<1>(const PaintParams &, int, int, int, hipStream_t, int);
+template <> hipError_t launch_paint_mode<2>(const PaintParams &, int, int, int, hipStream_t, int);
+template <> hipError_t launch_paint_mode<3>(const PaintParams &, int, int, int, hipStream_t, int);
+#define RL_DECLARE_VARIANTS(m)                                                                          \
+  template <> hipError_t launch_paint_variant<m, 0>(const PaintParams &, int, int, int, hipStream_t); \
+  template <> hipError_t launch_paint_variant<m, 1>(const PaintParams &, int, int, int, hipStream_t); \
+  template <> hipError_t launch_paint_variant<m, 2>(const PaintParams &, int, int, int, hipStream_t); \
+  template <> hipError_t launch_paint_variant<m, 3>(const PaintParams &, int, int, int, hipStream_t);
+RL_DECLARE_VARIANTS(0) RL_DECLARE_VARIANTS(1) RL_DECLARE_VARIANTS(2)
+#undef RL_DECLARE_VARIANTS
 template <> hipError_t launch_repaint_mode<0>(const RepaintParams &, int, int, hipStream_t);
 template <> hipError_t launch_repaint_mode<1>(const RepaintParams &, int, int, hipStream_t);
 template <> hipError_t launch_repaint_mode<2>(const RepaintParams &, int, int, hipStream_t);
 
 inline int kernel_mode(int sum_mode) { return sum_mode == 0 ? 1 : (sum_mode == 1 || sum_mode == 3 ? 0 : 2); }
-inline hipError_t launch_paint(const PaintParams &p, int S, int waves, int dir, hipStream_t stream) {
-  if (p.sum_mode == 3) return launch_paint_mode<3>(p, S, waves, dir, stream);  // RL_SUM_LANES32
+inline hipError_t launch_paint(const PaintParams &p, int S, int waves, int dir, hipStream_t stream, int fit = 1) {
+  if (p.sum_mode == 3) return launch_paint_mode<3>(p, S, waves, dir, stream, fit);  // RL_SUM_LANES32 (one variant)
   switch (kernel_mode(p.sum_mode)) {
-    case 0: return launch_paint_mode<0>(p, S, waves, dir, stream);
-    case 1: return launch_paint_mode<1>(p, S, waves, dir, stream);
-    default: return launch_paint_mode<2>(p, S, waves, dir, stream);
+    case 0: return launch_paint_mode<0>(p, S, waves, dir, stream, fit);
+    case 1: return launch_paint_mode<1>(p, S, waves, dir, stream, fit);
+    default: return launch_paint_mode<2>(p, S, waves, dir, stream, fit);
   }
 }
 // K2: the forward kernel (checkpoint rows + side records of every target), then the backward kernel, one workgroup

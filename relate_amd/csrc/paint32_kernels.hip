@@ -400,7 +400,7 @@ __global__ void __launch_bounds__(64 * WAVES, WAVES == 1 ? RL32_WAVES_PER_SIMD :
 }
 
 template <>
-hipError_t launch_paint_mode<3>(const PaintParams &p, int tile, int waves, int dir, hipStream_t stream) {
+hipError_t launch_paint_mode<3>(const PaintParams &p, int tile, int waves, int dir, hipStream_t stream, int) {
   return dispatch_tile(tile, waves, [&](auto s, auto t, auto w) {
     constexpr int S = s(), TAIL = t(), WAVES = w();
     const auto kernel_of = [](auto d) { return &paint32_kernel<S, TAIL, WAVES, decltype(d)::value>; };

@@ -272,6 +272,22 @@ RL_DEV void masked_mul8(double *v, const M &m, double k) {
       : "s"(m[OFF]), "s"(m[OFF + 1]), "s"(m[OFF + 2]), "s"(m[OFF + 3]), "s"(m[OFF + 4]), "s"(m[OFF + 5]),
         "s"(m[OFF + 6]), "s"(m[OFF + 7]), "v"(k));
 }
+// the same for a group whose eighth register holds no donor (a tile with LIVE = S - 1)
+template <int OFF = 0, typename M>
+RL_DEV void masked_mul7(double *v, const M &m, double k) {
+  asm volatile(
+      "s_mov_b64 exec, %7\n\tv_mul_f64 %0, %0, %14\n\t"
+      "s_mov_b64 exec, %8\n\tv_mul_f64 %1, %1, %14\n\t"
+      "s_mov_b64 exec, %9\n\tv_mul_f64 %2, %2, %14\n\t"
+      "s_mov_b64 exec, %10\n\tv_mul_f64 %3, %3, %14\n\t"
+      "s_mov_b64 exec, %11\n\tv_mul_f64 %4, %4, %14\n\t"
+      "s_mov_b64 exec, %12\n\tv_mul_f64 %5, %5, %14\n\t"
+      "s_mov_b64 exec, %13\n\tv_mul_f64 %6, %6, %14\n\t"
+      "s_mov_b64 exec, -1"
+      : "+v"(v[0]), "+v"(v[1]), "+v"(v[2]), "+v"(v[3]), "+v"(v[4]), "+v"(v[5]), "+v"(v[6])
+      : "s"(m[OFF]), "s"(m[OFF + 1]), "s"(m[OFF + 2]), "s"(m[OFF + 3]), "s"(m[OFF + 4]), "s"(m[OFF + 5]),
+        "s"(m[OFF + 6]), "v"(k));
+}
 // v += k in the lanes whose run reaches register j (j < len; j a constant
 // after unrolling): the validity test of a TAIL register, one v_cmp from the
 // lane's run length
@@ -293,6 +309,18 @@ RL_DEV void weighted4(double (&x)[4], double b0, double b1, double b2, double b3
       "s_mov_b64 exec, -1"
       : "=&v"(x[0]), "=&v"(x[1]), "=&v"(x[2]), "=&v"(x[3])
       : "v"(b0), "v"(b1), "v"(b2), "v"(b3), "s"(m[0]), "s"(m[1]), "s"(m[2]), "s"(m[3]), "v"(th), "v"(nth));
+}
+// ... of a chunk whose fourth register holds no donor (LIVE = S - 1)
+template <typename M>
+RL_DEV void weighted3(double (&x)[4], double b0, double b1, double b2, const M &m, double th, double nth) {
+  asm volatile(
+      "v_mul_f64 %0, %3, %10\n\tv_mul_f64 %1, %4, %10\n\tv_mul_f64 %2, %5, %10\n\t"
+      "s_mov_b64 exec, %6\n\tv_mul_f64 %0, %3, %9\n\t"
+      "s_mov_b64 exec, %7\n\tv_mul_f64 %1, %4, %9\n\t"
+      "s_mov_b64 exec, %8\n\tv_mul_f64 %2, %5, %9\n\t"
+      "s_mov_b64 exec, -1"
+      : "=&v"(x[0]), "=&v"(x[1]), "=&v"(x[2])
+      : "v"(b0), "v"(b1), "v"(b2), "s"(m[0]), "s"(m[1]), "s"(m[2]), "v"(th), "v"(nth));
 }
 // backward update of four registers (fast_painting.cpp:483-484):
 //   v = ((v + mis*bt) + b1) * (mis ? K1 : 1.0), mis = lanes of mn[i],
@@ -351,6 +379,31 @@ RL_DEV void backward4_tail(double (&v)[4], double (&x)[4], const M &mn, const M 
         "v"(b1), "v"(K1), "v"(th), "v"(nth), "s"(va[0]), "s"(va[1]), "s"(va[2]), "s"(va[3]));
 }
 
+// ... and of a TAIL chunk whose fourth register holds no donor (LIVE = S - 1): three registers
+template <typename M>
+RL_DEV void backward3_tail(double (&v)[4], double (&x)[4], const M &mn, const M &mh, const M &va, double bt,
+                           double b1, double K1, double th, double nth) {
+  asm volatile(
+      "s_mov_b64 exec, %6\n\tv_add_f64 %0, %0, %12\n\t"
+      "s_mov_b64 exec, %7\n\tv_add_f64 %1, %1, %12\n\t"
+      "s_mov_b64 exec, %8\n\tv_add_f64 %2, %2, %12\n\t"
+      "s_mov_b64 exec, %17\n\tv_add_f64 %0, %0, %13\n\t"
+      "s_mov_b64 exec, %18\n\tv_add_f64 %1, %1, %13\n\t"
+      "s_mov_b64 exec, %19\n\tv_add_f64 %2, %2, %13\n\t"
+      "s_mov_b64 exec, %6\n\tv_mul_f64 %0, %0, %14\n\t"
+      "s_mov_b64 exec, %7\n\tv_mul_f64 %1, %1, %14\n\t"
+      "s_mov_b64 exec, %8\n\tv_mul_f64 %2, %2, %14\n\t"
+      "s_mov_b64 exec, -1\n\t"
+      "v_mul_f64 %3, %0, %16\n\tv_mul_f64 %4, %1, %16\n\tv_mul_f64 %5, %2, %16\n\t"
+      "s_mov_b64 exec, %9\n\tv_mul_f64 %3, %0, %15\n\t"
+      "s_mov_b64 exec, %10\n\tv_mul_f64 %4, %1, %15\n\t"
+      "s_mov_b64 exec, %11\n\tv_mul_f64 %5, %2, %15\n\t"
+      "s_mov_b64 exec, -1"
+      : "+v"(v[0]), "+v"(v[1]), "+v"(v[2]), "=&v"(x[0]), "=&v"(x[1]), "=&v"(x[2])
+      : "s"(mn[0]), "s"(mn[1]), "s"(mn[2]), "s"(mh[0]), "s"(mh[1]), "s"(mh[2]), "v"(bt), "v"(b1), "v"(K1), "v"(th),
+        "v"(nth), "s"(va[0]), "s"(va[1]), "s"(va[2]));
+}
+
 // a[j] = v in the lanes of `bit`, j wave-uniform but not a compile-time
 // constant: a branch tree over static cases, each one exec-masked v_mov_b64.
 // Written the obvious way ("+v"(a[J]) in every case) the cases define new
@@ -363,29 +416,35 @@ RL_DEV void backward4_tail(double (&v)[4], double (&x)[4], const M &mn, const M 
 RL_DEV void poke_slot(const double &t, u64 mask, double v) {
   asm volatile("s_mov_b64 exec, %1\n\tv_mov_b64 %0, %2\n\ts_mov_b64 exec, -1" : : "v"(t), "s"(mask), "v"(v));
 }
-template <int S>
+// (LIVE: the registers that hold a donor in some lane, S or S - 1 -- a register named here stays allocated)
+template <int S, int LIVE = S>
 RL_DEV void pin_registers(double (&a)[S]) {
   static_assert(S % 8 == 0, "S must be a multiple of 8");
+  static_assert(LIVE == S || LIVE == S - 1, "at most the last register is dead");
 #pragma unroll
   for (int i = 0; i < S; i += 8)
-    asm volatile("" : "+v"(a[i]), "+v"(a[i + 1]), "+v"(a[i + 2]), "+v"(a[i + 3]), "+v"(a[i + 4]), "+v"(a[i + 5]),
-                 "+v"(a[i + 6]), "+v"(a[i + 7]));
+    if (i + 8 <= LIVE)
+      asm volatile("" : "+v"(a[i]), "+v"(a[i + 1]), "+v"(a[i + 2]), "+v"(a[i + 3]), "+v"(a[i + 4]), "+v"(a[i + 5]),
+                   "+v"(a[i + 6]), "+v"(a[i + 7]));
+    else
+      asm volatile("" : "+v"(a[i]), "+v"(a[i + 1]), "+v"(a[i + 2]), "+v"(a[i + 3]), "+v"(a[i + 4]), "+v"(a[i + 5]),
+                   "+v"(a[i + 6]));
 }
 #define RL_SLOT(J) \
   case J:          \
-    if constexpr ((J) < S) poke_slot(a[(J) < S ? (J) : 0], bit, v); \
+    if constexpr ((J) < LIVE) poke_slot(a[(J) < LIVE ? (J) : 0], bit, v); \
     break;
 #define RL_SLOT8(B) RL_SLOT(B) RL_SLOT(B + 1) RL_SLOT(B + 2) RL_SLOT(B + 3) RL_SLOT(B + 4) RL_SLOT(B + 5) RL_SLOT(B + 6) RL_SLOT(B + 7)
-template <int S>
+template <int S, int LIVE = S>
 RL_DEV void set_slot(double (&a)[S], int j, u64 bit, double v) {
   static_assert(S <= 80, "extend the case list");
-  pin_registers<S>(a);
+  pin_registers<S, LIVE>(a);
   switch (j) {
     RL_SLOT8(0) RL_SLOT8(8) RL_SLOT8(16) RL_SLOT8(24) RL_SLOT8(32) RL_SLOT8(40) RL_SLOT8(48) RL_SLOT8(56)
     RL_SLOT8(64) RL_SLOT8(72)
     default: break;
   }
-  pin_registers<S>(a);
+  pin_registers<S, LIVE>(a);
 }
 #undef RL_SLOT8
 #undef RL_SLOT

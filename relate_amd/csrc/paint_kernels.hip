@@ -17,6 +17,9 @@
 #ifndef RL_MODE
 #error "compile with -DRL_MODE=0 (lanes), 1 (exact, parallel), 2 (exact, literal serial)"
 #endif
+#ifndef RL_FIT
+#define RL_FIT 0  // the variant of every tile this translation unit holds (below, launch_paint_variant)
+#endif
 
 namespace rl {
 
@@ -29,7 +32,11 @@ namespace rl {
 #define RL_TOCK(acc, a, b) do { } while (0)
 #endif
 
-template <int S, int TAIL, int MODE, int WAVES>
+// A tile as the kernels see it (launch.h tile_fit): S registers per lane, of which the first LIVE (S or S - 1) hold a
+// donor in some lane -- every unrolled loop leaves the rest out, so a dead register costs neither instructions nor
+// VGPRs; the last TAIL registers take the backward pass's per-lane validity masks (whole chunks of 4), and registers
+// S - FTAIL .. LIVE - 1 the forward pass's validity compare.
+template <int S, int FTAIL, int MODE, int WAVES, int LIVE>
 RL_DEV void paint_forward(const PaintParams &p, int k, float *stage, WaveLink<WAVES> &lk) {
   const int wv = lk.w;  // this wave of the target's workgroup (wave-uniform)
   PaintLane<S> pl;
@@ -44,18 +51,20 @@ RL_DEV void paint_forward(const PaintParams &p, int k, float *stage, WaveLink<WA
   for_each_chunk<S, 8>(site_row(p.masks, S, p.L, st[0], WAVES, wv), [&](int j0, const u64x8 &m) {
 #pragma unroll
     for (int jj = 0; jj < 8; jj++) {
+      if (j0 + jj >= LIVE) continue;
       double v = c.init0;
       masked_mov(v, m[jj], c.init1);
-      if (j0 + jj >= S - TAIL) masked_mov(v, ~pl.valid(j0 + jj), 0.0);
+      if (j0 + jj >= S - FTAIL) masked_mov(v, ~pl.valid(j0 + jj), 0.0);
       a[j0 + jj] = v;
     }
   });
-  set_slot<S>(a, pl.jk, pl.kbit, 0.0);
-  double ssum = wave_sum<MODE, S, WAVES>(RegTerm<S>{a, 0.0, 0.0, p.stats}, local_sum<S>(RegTerm<S>{a}), lk);
+  typedef RegTerm<S, LIVE> Term;
+  set_slot<S, LIVE>(a, pl.jk, pl.kbit, 0.0);
+  double ssum = wave_sum<MODE, S, WAVES>(Term{a, 0.0, 0.0, p.stats}, local_sum<S>(Term{a}), lk);
   double ls = 0.0;
   int wa = 0, next_stone = forward_stone_index(k, 0);
   while (next_stone == 0) {
-    write_forward_stone<S>(wa, pl, wv, a, ls, stage);
+    write_forward_stone<S, LIVE>(wa, pl, wv, a, ls, stage);
     next_stone = forward_stone_index(k, wa);
   }
   double cfac = cfp[0] * ssum;  // :260
@@ -75,19 +84,19 @@ RL_DEV void paint_forward(const PaintParams &p, int k, float *stage, WaveLink<WA
     pipe.advance(p, i, pl.lane, wv);
     // requested here, used after the sum: the chunk loop's waits cover the latency
     const double nx_i = nx[i - 1], cf_i = cfp[i];
-    set_slot<S>(a, pl.jk, pl.kbit, -cfac);  // donor k: (-c) + c = +0.0
+    set_slot<S, LIVE>(a, pl.jk, pl.kbit, -cfac);  // donor k: (-c) + c = +0.0
     RL_TICK(2);
-    const double lsum = forward_update<S, TAIL, CH>(a, row, first, pl.len, cfac, K1);  // :288-295
+    const double lsum = forward_update<S, FTAIL, CH, LIVE>(a, row, first, pl.len, cfac, K1);  // :288-295
     RL_TICK(3);
     row = pipe.row(p, wv);
     first = load_masks<CH>(row, 0);
-    ssum = wave_sum<MODE, S, WAVES>(RegTerm<S>{a, 0.0, 0.0, p.stats}, lsum, lk);
+    ssum = wave_sum<MODE, S, WAVES>(Term{a, 0.0, 0.0, p.stats}, lsum, lk);
     RL_TICK(4);
     ls += nx_i;  // :281-282
     cfac = ssum;
     if (cfac < c.lower || cfac > c.upper) {  // :334-347
 #pragma unroll
-      for (int j = 0; j < S; j++) a[j] /= ssum;
+      for (int j = 0; j < LIVE; j++) a[j] /= ssum;
       ls += log(ssum);
       cfac = 1.0;
     }
@@ -95,7 +104,7 @@ RL_DEV void paint_forward(const PaintParams &p, int k, float *stage, WaveLink<WA
     RL_TICK(5);
     RL_TOCK(seg1, 0, 1); RL_TOCK(seg2, 1, 2); RL_TOCK(seg3, 2, 3); RL_TOCK(seg4, 3, 4); RL_TOCK(seg5, 4, 5);
     while (next_stone == i) {  // :354-374
-      write_forward_stone<S>(wa, pl, wv, a, ls, stage);
+      write_forward_stone<S, LIVE>(wa, pl, wv, a, ls, stage);
       next_stone = forward_stone_index(k, wa);
     }
   }
@@ -113,7 +122,7 @@ RL_DEV void paint_forward(const PaintParams &p, int k, float *stage, WaveLink<WA
 #endif
 }
 
-template <int S, int TAIL, int MODE, int WAVES>
+template <int S, int TAIL, int MODE, int WAVES, int LIVE>
 RL_DEV void paint_backward(const PaintParams &p, int k, float *stage, WaveLink<WAVES> &lk) {
   const int wv = lk.w;
   PaintLane<S> pl;
@@ -131,16 +140,16 @@ RL_DEV void paint_backward(const PaintParams &p, int k, float *stage, WaveLink<W
   // ---- last SNP (:396-448)
   double ls = c.log_Nm1 - D * c.log_ntheta;  // normalizing_constant :399
 #pragma unroll
-  for (int i = 0; i < S; i++) {
+  for (int i = 0; i < LIVE; i++) {
     double v = 1.0;
     if (i >= S - TAIL) masked_mov(v, ~pl.valid(i), 0.0);
     b[i] = v;
   }
-  set_slot<S>(b, pl.jk, pl.kbit, 0.0);  // written as beta[k] = 1 below, +0.0 from then on
+  set_slot<S, LIVE>(b, pl.jk, pl.kbit, 0.0);  // written as beta[k] = 1 below, +0.0 from then on
   double bsum = p.binit[k];  // serial sum of theta/ntheta minus ntheta (:421-431)
   int we = p.W - 1, next_stone = backward_stone_index(k, we);
   while (next_stone == D - 1) {
-    write_backward_stone<S>(we, pl, wv, b, ls, 1.0f, stage);  // beta[k] = 1 at the last SNP
+    write_backward_stone<S, LIVE>(we, pl, wv, b, ls, 1.0f, stage);  // beta[k] = 1 at the last SNP
     next_stone = backward_stone_index(k, we);
   }
   double cfac = cfp[D - 1] * bsum;  // :454-455
@@ -155,7 +164,7 @@ RL_DEV void paint_backward(const PaintParams &p, int k, float *stage, WaveLink<W
   const double K1 = in_vgpr(c.K1), theta = in_vgpr(c.theta), ntheta = in_vgpr(c.ntheta);
   unsigned long long bseg1 = 0, bseg2 = 0, bseg3 = 0, bseg4 = 0;
   (void)bseg1; (void)bseg2; (void)bseg3; (void)bseg4;
-  typedef typename std::conditional<MODE == 1, StashTerm<S>, MaskTerm<S>>::type BackwardTerm;
+  typedef typename std::conditional<MODE == 1, StashTerm<S, LIVE>, MaskTerm<S, LIVE>>::type BackwardTerm;
   const auto make_term = [&](MaskRow row) {
     unsigned long long *const stats = p.stats ? p.stats + 8 : nullptr;
     if constexpr (MODE == 1)
@@ -174,7 +183,7 @@ RL_DEV void paint_backward(const PaintParams &p, int k, float *stage, WaveLink<W
     const double nx_j = nx[j + 1], cf_j = cfp[j];  // used after the sum (see paint_forward)
     const double b1 = div_by_const(cfac, ntheta, c.inv_ntheta);     // cfac / ntheta, :474
     const double bt = div_by_const(cfac, theta, c.inv_theta) - b1;  // cfac / theta - b1, :475
-    set_slot<S>(b, pl.jk, pl.kbit, -b1);   // donor k: (-b1) + b1 = +0.0 (never a mismatch with itself)
+    set_slot<S, LIVE>(b, pl.jk, pl.kbit, -b1);   // donor k: (-b1) + b1 = +0.0 (never a mismatch with itself)
     double lsum = 0.0;
     MaskRow vrow = (MaskRow)(p.masks + ((size_t)(p.L + 1) * WAVES + wv) * S);
     asm volatile("" : "+s"(vrow));
@@ -190,19 +199,28 @@ RL_DEV void paint_backward(const PaintParams &p, int k, float *stage, WaveLink<W
         stash_put4(sp, j0 / 4 - 1, xp);
       }
 #pragma unroll
-      for (int jj = 0; jj < 4; jj++) v[jj] = b[j0 + jj];
+      for (int jj = 0; jj < 4; jj++)
+        if (j0 + jj < LIVE) v[jj] = b[j0 + jj];
       if (j0 + 4 <= S - TAIL)
         backward4(v, x, mn, mh, bt, b1, K1, theta, ntheta);
-      else
+      else if (j0 + 4 <= LIVE)
         backward4_tail(v, x, mn, mh, va, bt, b1, K1, theta, ntheta);
+      else  // (TAIL >= 4: the chunk of the dead register is a tail chunk)
+        backward3_tail(v, x, mn, mh, va, bt, b1, K1, theta, ntheta);
 #pragma unroll
       for (int jj = 0; jj < 4; jj++) {
+        if (j0 + jj >= LIVE) continue;
         b[j0 + jj] = v[jj];
         lsum += x[jj];  // the lane's share of :495-503
         if (KS > 0 && j0 < KS) xp[jj] = x[jj];
       }
     });
-    if (KS == S) stash_put4(sp, S / 4 - 1, xp);
+    if (KS == S) {
+      if (LIVE == S)
+        stash_put4(sp, S / 4 - 1, xp);
+      else
+        stash_put3(sp, S / 4 - 1, xp);
+    }
     RL_TICK(2);
     const BackwardTerm term = make_term(rowh);
     rown = rowh;
@@ -221,7 +239,7 @@ RL_DEV void paint_backward(const PaintParams &p, int k, float *stage, WaveLink<W
     cfac = bsum;
     if (cfac < c.lower || cfac > c.upper) {  // :538-551
 #pragma unroll
-      for (int i = 0; i < S; i++) b[i] /= bsum;
+      for (int i = 0; i < LIVE; i++) b[i] /= bsum;
       ls += fast_log_dev((float)bsum);
       cfac = 1.0;
     }
@@ -229,7 +247,7 @@ RL_DEV void paint_backward(const PaintParams &p, int k, float *stage, WaveLink<W
     RL_TICK(4);
     RL_TOCK(bseg1, 0, 1); RL_TOCK(bseg2, 1, 2); RL_TOCK(bseg3, 2, 3); RL_TOCK(bseg4, 3, 4);
     while (next_stone == j) {  // :559-578
-      write_backward_stone<S>(we, pl, wv, b, ls, 0.0f, stage);
+      write_backward_stone<S, LIVE>(we, pl, wv, b, ls, 0.0f, stage);
       next_stone = backward_stone_index(k, we);
     }
   }
@@ -245,7 +263,7 @@ RL_DEV void paint_backward(const PaintParams &p, int k, float *stage, WaveLink<W
 
 // S <= 80: hold the kernel to 256 registers so that two waves share a SIMD.
 // WAVES = 2: a workgroup of two waves paints one target (N > 5120).
-template <int S, int TAIL, int MODE, int WAVES, int DIR>
+template <int S, int TAIL, int MODE, int WAVES, int DIR, int LIVE = S, int FTAIL = TAIL>
 __global__ void __launch_bounds__(64 * WAVES, 2) paint_kernel(const PaintParams p) {
   // per wave: the staging strip of the stones (4 KB) and, where an exact backward pass runs, its stash of weighted
   // terms (up to 18 KB) in the same storage -- a stone is never written during a sum
@@ -277,26 +295,50 @@ __global__ void __launch_bounds__(64 * WAVES, 2) paint_kernel(const PaintParams 
   PaintParams q = p;
   if (p.stats) q.stats = lstats;
   if (backward)
-    paint_backward<S, TAIL, MODE, WAVES>(q, k, stage[lk.w], lk);
+    paint_backward<S, TAIL, MODE, WAVES, LIVE>(q, k, stage[lk.w], lk);
   else
-    paint_forward<S, TAIL, MODE, WAVES>(q, k, stage[lk.w], lk);
+    paint_forward<S, FTAIL, MODE, WAVES, LIVE>(q, k, stage[lk.w], lk);
   __syncthreads();
   if (p.stats && threadIdx.x < 32 && lstats[threadIdx.x]) atomicAdd(&p.stats[threadIdx.x], lstats[threadIdx.x]);
 #else
   if (backward)
-    paint_backward<S, TAIL, MODE, WAVES>(p, k, stage[lk.w], lk);
+    paint_backward<S, TAIL, MODE, WAVES, LIVE>(p, k, stage[lk.w], lk);
   else
-    paint_forward<S, TAIL, MODE, WAVES>(p, k, stage[lk.w], lk);
+    paint_forward<S, FTAIL, MODE, WAVES, LIVE>(p, k, stage[lk.w], lk);
 #endif
 }
 
+// This translation unit holds one variant of every tile (launch.h tile_fit): RL_FIT = 0 the loose one, which is the
+// tile list's, 1 / 2 the tight ones, 3 tight minus one.
 template <>
-hipError_t launch_paint_mode<RL_MODE>(const PaintParams &p, int tile, int waves, int dir, hipStream_t stream) {
+hipError_t launch_paint_variant<RL_MODE, RL_FIT>(const PaintParams &p, int tile, int waves, int dir,
+                                                 hipStream_t stream) {
   return dispatch_tile(tile, waves, [&](auto s, auto t, auto w) {
-    constexpr int S = s(), TAIL = t(), WAVES = w();
-    const auto kernel_of = [](auto d) { return &paint_kernel<S, TAIL, RL_MODE, WAVES, decltype(d)::value>; };
-    return launch_paint_dir(kernel_of, p, WAVES, dir, stream);
+    constexpr int S = s(), WAVES = w();
+    constexpr int TAIL = RL_FIT == 0 ? t() : 4, LIVE = RL_FIT == 3 ? S - 1 : S;
+    constexpr int FTAIL = RL_FIT == 0 ? TAIL : RL_FIT == 1 ? 1 : RL_FIT == 2 ? 4 : 2;
+    if constexpr (RL_FIT == 0 || tile_fit_built(RL_MODE, S, WAVES)) {
+      const auto kernel_of = [](auto d) {
+        return &paint_kernel<S, TAIL, RL_MODE, WAVES, decltype(d)::value, LIVE, FTAIL>;
+      };
+      return launch_paint_dir(kernel_of, p, WAVES, dir, stream);
+    } else {
+      return hipErrorInvalidValue;
+    }
   });
 }
+
+#if RL_FIT == 0
+template <>
+hipError_t launch_paint_mode<RL_MODE>(const PaintParams &p, int tile, int waves, int dir, hipStream_t stream,
+                                      int fit) {
+  switch (tile_fit(p.lay, tile, fit != 0 && tile_fit_built(RL_MODE, tile, waves)).variant) {
+    case 0: return launch_paint_variant<RL_MODE, 0>(p, tile, waves, dir, stream);
+    case 1: return launch_paint_variant<RL_MODE, 1>(p, tile, waves, dir, stream);
+    case 2: return launch_paint_variant<RL_MODE, 2>(p, tile, waves, dir, stream);
+    default: return launch_paint_variant<RL_MODE, 3>(p, tile, waves, dir, stream);
+  }
+}
+#endif
 
 }  // namespace rl

@@ -34,8 +34,10 @@ RL_DEV PlanSlice plan_slice(const P &p, int k) {  // all of them
 
 // ---- the forward step body (FP64) -------------------------------------------
 // forward: a = (a + cfac) * (mismatch ? K1 : 1.0) over the masks of `row`, chunk 0 of it already requested
-// (fast_painting.cpp:288-295); returns the lane's share of the serial sum (:300-303)
-template <int S, int TAIL, int CH>
+// (fast_painting.cpp:288-295); returns the lane's share of the serial sum (:300-303).  Registers S - TAIL .. LIVE - 1
+// carry the validity test; registers from LIVE on (a K1 tile fitted to N: at most the last one) hold no donor in any
+// lane and are left out.
+template <int S, int TAIL, int CH, int LIVE = S>
 RL_DEV double forward_update(double (&a)[S], MaskRow row, typename MaskChunk<CH>::type first, const int &len,
                              const double &cfac, const double &K1) {
   typedef typename MaskChunk<CH>::type Chunk;
@@ -44,16 +46,27 @@ RL_DEV double forward_update(double (&a)[S], MaskRow row, typename MaskChunk<CH>
     double v[CH];
 #pragma unroll
     for (int jj = 0; jj < CH; jj++) {
+      if (j0 + jj >= LIVE) continue;
       v[jj] = a[j0 + jj];
       if (j0 + jj < S - TAIL)
         v[jj] = v[jj] + cfac;
       else
         tail_add(v[jj], len, j0 + jj, cfac);  // slots past the lane's run stay +0.0
     }
-    masked_mul8<0>(v, m, K1);  // v *= (mismatch ? K1 : 1.0)
-    if constexpr (CH == 16) masked_mul8<8>(v + 8, m, K1);
+    // v *= (mismatch ? K1 : 1.0)
+    if (j0 + 8 <= LIVE)
+      masked_mul8<0>(v, m, K1);
+    else
+      masked_mul7<0>(v, m, K1);
+    if constexpr (CH == 16) {
+      if (j0 + 16 <= LIVE)
+        masked_mul8<8>(v + 8, m, K1);
+      else
+        masked_mul7<8>(v + 8, m, K1);
+    }
 #pragma unroll
     for (int jj = 0; jj < CH; jj++) {
+      if (j0 + jj >= LIVE) continue;
       a[j0 + jj] = v[jj];
       lsum += v[jj];
     }
@@ -94,7 +107,7 @@ struct ForwardRows {
 // rolled loop (each lane reads back only what it wrote: no barrier needed).
 // The slot of donor k itself (held at +0.0) is written as self_value.
 // Two overloads, for the two forms of state: doubles, one per register ...
-template <int S>
+template <int S, int LIVE = S>
 RL_DEV void emit_stone(const PaintLane<S> &pl, const double (&v)[S], float *__restrict__ out, float self_value,
                        float *stage) {
   static_assert(S % 8 == 0, "S must be a multiple of 8");
@@ -104,6 +117,7 @@ RL_DEV void emit_stone(const PaintLane<S> &pl, const double (&v)[S], float *__re
 #pragma unroll
     for (int ii = 0; ii < R; ii++) {
       // pin the conversion to its chunk: hoisted, all S floats would be live at once
+      if (c * R + ii >= LIVE) continue;  // (no lane's run reaches it: never read back below)
       double x = v[c * R + ii];
       asm volatile("" : "+v"(x) : : "memory");
       stage[ii * 64 + pl.lane] = (float)x;
@@ -118,7 +132,7 @@ RL_DEV void emit_stone(const PaintLane<S> &pl, const double (&v)[S], float *__re
 }
 // ... and packed floats, two per register (paint32_kernels.hip).  (One body over a per-chunk staging helper costs the
 // packed-FP32 kernel registers: DESIGN_NOTES.md 13.)
-template <int S>
+template <int S, int LIVE = S>
 RL_DEV void emit_stone(const PaintLane<S> &pl, const f32x2 (&v)[S / 2], float *__restrict__ out, float self_value,
                        float *stage) {
   constexpr int R = S % 16 == 0 ? 16 : 8;
@@ -150,25 +164,25 @@ RL_DEV int backward_stone_index(int k, int w) {
   return w >= cp->w_first ? cp->stone_ie[(size_t)k * cp->W + w] : -2;
 }
 // forward stone w: the state a, its logscale ls; then on to stone w + 1
-template <int S, typename V>
+template <int S, int LIVE = S, typename V>
 RL_DEV void write_forward_stone(int &w, const PaintLane<S> &pl, const int &wv, const V &a, const double &ls,
                                 float *stage) {
   const ColdParams cp = cold_params<PaintParams>();
   if (w >= cp->w_first) {
     const size_t N = cp->lay.N, row = (size_t)(w - cp->w_first) * cp->nloc + (pl.k - cp->k0);
-    emit_stone<S>(pl, a, cp->alpha + row * N, 0.0f, stage);
+    emit_stone<S, LIVE>(pl, a, cp->alpha + row * N, 0.0f, stage);
     if (pl.lane == 0 && wv == 0) cp->ls_alpha[row] = (float)ls;
   }
   w++;
 }
 // backward stone w (self_value: beta[k] = 1 at the last SNP, +0.0 from then on); then on to stone w - 1
-template <int S, typename V>
+template <int S, int LIVE = S, typename V>
 RL_DEV void write_backward_stone(int &w, const PaintLane<S> &pl, const int &wv, const V &b, const double &ls,
                                  float self_value, float *stage) {
   const ColdParams cp = cold_params<PaintParams>();
   if (w <= cp->w_last) {
     const size_t N = cp->lay.N, row = (size_t)(w - cp->w_first) * cp->nloc + (pl.k - cp->k0);
-    emit_stone<S>(pl, b, cp->beta + row * N, self_value, stage);
+    emit_stone<S, LIVE>(pl, b, cp->beta + row * N, self_value, stage);
     if (pl.lane == 0 && wv == 0) cp->ls_beta[row] = (float)ls;
   }
   w--;

@@ -13,6 +13,10 @@ for m in 0 1 2; do
     /opt/rocm/bin/hipcc $FLAGS $EXTRA -DRL_MODE=$m -c $f.hip -o ../../build/variants/${f}_m${m}_$NAME.o &
     pids+=($!)
   done
+  for v in 1 2 3; do  # the fitted variants of K1's register tiles (launch.h tile_fit)
+    /opt/rocm/bin/hipcc $FLAGS $EXTRA -DRL_MODE=$m -DRL_FIT=$v -c paint_kernels.hip -o ../../build/variants/paint_kernels_m${m}_f${v}_$NAME.o &
+    pids+=($!)
+  done
 done
 for p in "${pids[@]}"; do wait $p; done
 OBJS=$(ls ../../build/obj/*.o | grep -v "paint_kernels_m")
