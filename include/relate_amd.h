@@ -183,12 +183,21 @@ int rl_register_tile(const rl_ctx *ctx, int *S, int *waves);
  * RL_DEBUG_SUM_STASH (with RL_SUM_EXACT and a mismatch array only): the
  * terms are computed once into the wave's LDS stash and every pass of the sum
  * reads them back, as the exact backward pass of rl_paint does; geometry and
- * counters as without it.  Bad arguments: RL_EINVAL before any device work. */
+ * counters as without it.  RL_DEBUG_SUM_REGSTASH (same conditions, not
+ * together with RL_DEBUG_SUM_STASH): the terms split three ways as that pass
+ * splits them -- the first through the stash, the last held in registers from
+ * the loop that computed them, the rest recomputed (rl_debug_term_split).
+ * Bad arguments: RL_EINVAL before any device work. */
 #define RL_DEBUG_SUM_STASH 0x100
+#define RL_DEBUG_SUM_REGSTASH 0x200
 int rl_debug_wave_sum(const double *x, int n, int batch, int sum_mode, double *out);
 int rl_debug_wave_sum_ex(const double *x, int n, int batch, int rows_per_group, int sum_mode,
                          const uint8_t *mismatch, double th, double nth, double *out,
                          unsigned long long *stats8);
+/* Host only: of the S weighted terms of a backward step of register tile S
+ * (8, 16, 32, 48, 64, 80), the exact order keeps the first *ks in LDS and the
+ * last *r in registers and recomputes the rest.  RL_EINVAL for another S. */
+int rl_debug_term_split(int S, int *ks, int *r);
 
 /* Experiment builds only (kernels compiled with -DRL_STATS and
  * RELATE_AMD_TEST_STATS set): 16 event counters of the last rl_paint. */

@@ -17,6 +17,7 @@ RL_SUM_LANES = 1
 RL_SUM_EXACT_SERIAL = 2
 RL_SUM_LANES32 = 3
 RL_DEBUG_SUM_STASH = 0x100  # rl_debug_wave_sum_ex: or-ed into RL_SUM_EXACT, the terms go through the LDS stash
+RL_DEBUG_SUM_REGSTASH = 0x200  # ... split three ways: LDS stash, registers, recomputed (K1's exact backward pass)
 
 _lib = None
 
@@ -97,12 +98,15 @@ def device_count():
     return lib().rl_device_count()
 
 
-def debug_wave_sum(x, sum_mode, rows_per_group=1, mismatch=None, th=0.001, nth=0.999, stash=False):
+def debug_wave_sum(x, sum_mode, rows_per_group=1, mismatch=None, th=0.001, nth=0.999, stash=False, regstash=False):
     """rl_debug_wave_sum_ex: the kernels' sum of each row of x [batch][n] (terms (mismatch ? th : nth) * x if
-    mismatch is given; stash: computed once into the LDS stash of K1's exact backward pass and read back from it)
-    -> (sums [batch], stats), stats = the RL_SUM_EXACT path counters, counted per wave"""
+    mismatch is given; stash: computed once into the LDS stash of K1's exact backward pass and read back from it;
+    regstash: split as that pass splits them, term_split(S): the first through the stash, the last held in registers,
+    the rest recomputed) -> (sums [batch], stats), stats = the RL_SUM_EXACT path counters, counted per wave"""
     if stash:
         sum_mode |= RL_DEBUG_SUM_STASH
+    if regstash:
+        sum_mode |= RL_DEBUG_SUM_REGSTASH
     x = np.ascontiguousarray(x, dtype=np.float64)
     batch, n = x.shape
     if mismatch is not None:
@@ -115,6 +119,14 @@ def debug_wave_sum(x, sum_mode, rows_per_group=1, mismatch=None, th=0.001, nth=0
                   C.c_void_p]
     _check(f(_p(x), n, batch, rows_per_group, sum_mode, _p(mismatch), th, nth, _p(out), _p(st)))
     return out, {"sums": int(st[0]), "fallbacks": int(st[1]), "walked": int(st[2]), "reruns": int(st[3])}
+
+
+def term_split(S):
+    """rl_debug_term_split: -> (KS, R): of the S weighted terms of a backward step of tile S the exact order keeps
+    the first KS in LDS and the last R in registers (host code, no GPU)"""
+    ks, r = C.c_int(), C.c_int()
+    _check(lib().rl_debug_term_split(int(S), C.byref(ks), C.byref(r)))
+    return ks.value, r.value
 
 
 def tile_fit(N):

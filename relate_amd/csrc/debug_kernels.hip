@@ -10,7 +10,9 @@
 // the forward passes) or (mismatch ? th : nth) * x under the EXEC masks of a
 // lane-mask panel (MaskTerm, the backward passes), or those terms computed once
 // into the wave's LDS stash and read back from it by every pass of the sum
-// (StashTerm, K1's exact backward pass).
+// (StashTerm, K1's exact backward pass), or split three ways as that pass splits
+// them: the first KS through the stash, the last R held in registers from the
+// loop that computed them, the rest recomputed.
 //
 // This translation unit alone is compiled with the path counters of exact_sum.h
 // (RL_STATS); the Makefile has no -fgpu-rdc, so the paint and repaint objects
@@ -27,7 +29,7 @@ namespace rl {
 
 constexpr int SUM_STATS = 8;  // exact_sum.h RL_STAT: sums, fallbacks, walked lanes, reruns, then 4 cycle counts
 
-enum { TERM_REG = 0, TERM_MASK = 1, TERM_STASH = 2 };
+enum { TERM_REG = 0, TERM_MASK = 1, TERM_STASH = 2, TERM_REGSTASH = 3 };
 
 template <int S, int MODE, int WAVES, int KIND>
 __global__ void __launch_bounds__(64 * WAVES) sum_kernel(const double *__restrict__ x, int n, int rows_per_group,
@@ -37,7 +39,9 @@ __global__ void __launch_bounds__(64 * WAVES) sum_kernel(const double *__restric
   __shared__ WaveLinkStorage link;
   __shared__ unsigned long long lstats[SUM_STATS];
   // the stash of each wave, as in paint_kernel (only the stashing kind has one)
-  constexpr int STASH = KIND == TERM_STASH ? stash_bytes(S) : 16;
+  constexpr bool STASHING = KIND == TERM_STASH || KIND == TERM_REGSTASH;
+  constexpr int STASH = STASHING ? stash_bytes(S) : 16;
+  constexpr int R = KIND == TERM_REGSTASH ? reg_stash_terms(S) : 0;  // (the stashing kind: LDS and recomputed alone)
   __shared__ __attribute__((aligned(16))) char stash[WAVES][STASH];
   WaveLink<WAVES> lk = make_wave_link<WAVES>(&link);
   if (threadIdx.x < SUM_STATS) lstats[threadIdx.x] = 0;
@@ -52,19 +56,23 @@ __global__ void __launch_bounds__(64 * WAVES) sum_kernel(const double *__restric
 #pragma unroll
     for (int i = 0; i < S; i++) a[i] = (i < len) ? xb[start + i] : 0.0;
     double sum;
-    if constexpr (KIND == TERM_STASH) {
-      // as K1's update loop: every weighted term once, its first KS into the stash, the lane's local sum alongside
+    if constexpr (STASHING) {
+      // as K1's update loop: every weighted term once, its first KS into the stash, its last R into registers of
+      // their own, the lane's local sum alongside
       const MaskRow mrow = (MaskRow)(masks + (row * WAVES + lk.w) * S);
       const StashPtr sp = stash_of(stash[lk.w]);
-      double L = 0.0;
+      double L = 0.0, xr[R > 0 ? R : 1];
       for_each_chunk<S, 4>(mrow, [&](int j0, const u64x4 &m) {
         double w[4];
         weighted4(w, a[j0], a[j0 + 1], a[j0 + 2], a[j0 + 3], m, th, nth);
         if (j0 < stash_terms(S)) stash_put4(sp, j0 / 4, w);
 #pragma unroll
-        for (int jj = 0; jj < 4; jj++) L += w[jj];
+        for (int jj = 0; jj < 4; jj++) {
+          L += w[jj];
+          hold_term<S, R>(xr, j0 + jj, w[jj]);
+        }
       });
-      const StashTerm<S> t{mrow, a, th, nth, lstats, sp};
+      const StashTerm<S, S, R> t{mrow, a, th, nth, lstats, sp, xr};
       sum = wave_sum<MODE, S, WAVES>(t, L, lk);
     } else if constexpr (KIND == TERM_MASK) {
       const MaskTerm<S> t{(MaskRow)(masks + (row * WAVES + lk.w) * S), a, th, nth, lstats};
@@ -81,11 +89,16 @@ __global__ void __launch_bounds__(64 * WAVES) sum_kernel(const double *__restric
 
 template <int S, int MODE, int WAVES>
 static hipError_t launch_sum_t(const double *x, int n, int groups, int rows_per_group, const unsigned long long *masks,
-                               double th, double nth, double *out, unsigned long long *stats, bool stash) {
+                               double th, double nth, double *out, unsigned long long *stats, int kind) {
   if constexpr (MODE == 1) {  // (the stash exists for the exact order alone)
-    if (stash) {
+    if (kind == TERM_STASH) {
       hipLaunchKernelGGL((sum_kernel<S, MODE, WAVES, TERM_STASH>), dim3(groups), dim3(64 * WAVES), 0, nullptr, x, n,
                          rows_per_group, masks, th, nth, out, stats);
+      return hipGetLastError();
+    }
+    if (kind == TERM_REGSTASH) {
+      hipLaunchKernelGGL((sum_kernel<S, MODE, WAVES, TERM_REGSTASH>), dim3(groups), dim3(64 * WAVES), 0, nullptr, x,
+                         n, rows_per_group, masks, th, nth, out, stats);
       return hipGetLastError();
     }
   }
@@ -101,9 +114,9 @@ static hipError_t launch_sum_t(const double *x, int n, int groups, int rows_per_
 template <int MODE>
 static hipError_t launch_sum(int S, int waves, const double *x, int n, int groups, int rows_per_group,
                              const unsigned long long *masks, double th, double nth, double *out,
-                             unsigned long long *stats, bool stash) {
+                             unsigned long long *stats, int kind) {
   return dispatch_tile(S, waves, [&](auto s, auto, auto w) {
-    return launch_sum_t<s(), MODE, w()>(x, n, groups, rows_per_group, masks, th, nth, out, stats, stash);
+    return launch_sum_t<s(), MODE, w()>(x, n, groups, rows_per_group, masks, th, nth, out, stats, kind);
   });
 }
 
@@ -117,12 +130,18 @@ extern "C" int rl_debug_wave_sum_ex(const double *x, int n, int batch, int rows_
     set_error("rl_debug_wave_sum_ex: null x or out");
     return RL_EINVAL;
   }
-  const bool stash = (sum_mode & RL_DEBUG_SUM_STASH) != 0;
-  if (stash) sum_mode &= ~RL_DEBUG_SUM_STASH;
-  if (stash && (sum_mode != RL_SUM_EXACT || !mismatch)) {
-    set_error("rl_debug_wave_sum_ex: RL_DEBUG_SUM_STASH needs RL_SUM_EXACT and a mismatch array");
+  const bool stash = (sum_mode & RL_DEBUG_SUM_STASH) != 0, regstash = (sum_mode & RL_DEBUG_SUM_REGSTASH) != 0;
+  sum_mode &= ~(RL_DEBUG_SUM_STASH | RL_DEBUG_SUM_REGSTASH);
+  if (stash && regstash) {
+    set_error("rl_debug_wave_sum_ex: RL_DEBUG_SUM_STASH and RL_DEBUG_SUM_REGSTASH exclude each other");
     return RL_EINVAL;
   }
+  if ((stash || regstash) && (sum_mode != RL_SUM_EXACT || !mismatch)) {
+    set_error("rl_debug_wave_sum_ex: %s needs RL_SUM_EXACT and a mismatch array",
+              stash ? "RL_DEBUG_SUM_STASH" : "RL_DEBUG_SUM_REGSTASH");
+    return RL_EINVAL;
+  }
+  const int kind = stash ? TERM_STASH : regstash ? TERM_REGSTASH : mismatch ? TERM_MASK : TERM_REG;
   if (n < 1 || n > 2 * 80 * 64) {
     set_error("rl_debug_wave_sum_ex: n=%d outside 1..%d", n, 2 * 80 * 64);
     return RL_EINVAL;
@@ -167,7 +186,7 @@ extern "C" int rl_debug_wave_sum_ex(const double *x, int n, int batch, int rows_
   hipError_t e;
   switch (kernel_mode(sum_mode)) {
 #define RL_ARGS S, waves, dx.as<double>(), n, groups, rows_per_group, dm, th, nth, dout.as<double>(), \
-                dstats.as<unsigned long long>(), stash
+                dstats.as<unsigned long long>(), kind
     case 0: e = launch_sum<0>(RL_ARGS); break;
     case 1: e = launch_sum<1>(RL_ARGS); break;
     default: e = launch_sum<2>(RL_ARGS); break;
@@ -182,4 +201,20 @@ extern "C" int rl_debug_wave_sum_ex(const double *x, int n, int batch, int rows_
 
 extern "C" int rl_debug_wave_sum(const double *x, int n, int batch, int sum_mode, double *out) {
   return rl_debug_wave_sum_ex(x, n, batch, 1, sum_mode, nullptr, 0.0, 0.0, out, nullptr);
+}
+
+// host only: how K1's exact backward pass splits the S weighted terms of tile S (exact_sum.h) -- the first *ks through
+// LDS, the last *r in registers, the rest recomputed
+extern "C" int rl_debug_term_split(int S, int *ks, int *r) {
+  using namespace rl;
+  const hipError_t e = dispatch_tile(S, 1, [&](auto s, auto, auto) {
+    *ks = stash_terms(s());
+    *r = reg_stash_terms(s());
+    return hipSuccess;
+  });
+  if (e != hipSuccess) {
+    set_error("rl_debug_term_split: no register tile S=%d", S);
+    return RL_EINVAL;
+  }
+  return RL_OK;
 }

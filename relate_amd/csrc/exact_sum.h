@@ -123,8 +123,8 @@ struct MaskTerm {  // backward, lane-mask panel: e(i) * beta[i] with the site's 
 // kept in a wave-private LDS region instead of being recomputed by each pass of the sum (the chains, a rerun of
 // the walk, the literal fallback) -- 2 VALU, 1.25 SALU and a quarter of a mask chunk per term and pass.  The region
 // is [pair of terms][lane][2] doubles, one ds_write_b128 / ds_read_b128 per lane and pair; a lane reads back only
-// what it wrote, bit for bit, so no barrier is needed and the sum cannot change.  The remaining S - KS terms are
-// recomputed as in MaskTerm.
+// what it wrote, bit for bit, so no barrier is needed and the sum cannot change.  Of the remaining S - KS terms
+// the last R stay in registers (reg_stash_terms below), the others are recomputed as in MaskTerm.
 //
 // KS: the stash never takes LDS that another wave needs.  A tile's registers allow tile_waves_per_simd(S) waves on
 // a SIMD (tools/kernel_resources.sh); the stash gets that wave's share of the CU's 160 KB less 512 B (WaveLink, the
@@ -140,6 +140,21 @@ constexpr int stash_terms(int S) {
   return (ks < STASH_MAX ? ks : STASH_MAX) / 4 * 4;
 }
 constexpr int stash_bytes(int S) { return stash_terms(S) * 64 * (int)sizeof(double); }
+// The LAST R weighted terms of a step stay where the update loop produced them, in registers (StashTerm::xr): the
+// chunks produced last add the least pressure inside the update loop, and a held term costs no LDS traffic at all.
+// R is what the tile's registers leave free: the largest multiple of 4 at which every exact K1 kernel of the tile --
+// four fit variants, one and two waves per target, each launch direction -- keeps zero scratch and the waves per SIMD
+// of tile_waves_per_simd (tools/kernel_resources.sh, profiles/regstash_kernel_resources.txt).  The two tiles of the
+// two-wave-per-SIMD configurations have the most terms left to recompute (28 and 44): S = 64 holds all of them
+// (KS + R = S, its recompute loop is empty), S = 80 the 12 that fit; the smaller tiles have no register to spare and
+// keep their step loops instruction for instruction.
+constexpr int reg_stash_terms(int S) { return S == 80 ? 12 : S == 64 ? 28 : 0; }
+// the update loop's side: term i of the step (register j0 + jj of chunk j0) goes into xr if it is one of the last R
+template <int S, int R>
+RL_DEV void hold_term(double (&xr)[R > 0 ? R : 1], int i, double x) {
+  if constexpr (R > 0)
+    if (i >= S - R) xr[i - (S - R)] = x;
+}
 constexpr int STASH_AHEAD = 2;  // pairs of terms requested ahead of the one in work (StashTerm::for_each)
 typedef double f64x2 __attribute__((ext_vector_type(2)));
 // (may_alias: the region shares storage with the float staging strip of the stones)
@@ -161,18 +176,21 @@ RL_DEV void stash_put3(StashPtr sp, int chunk, const double (&x)[4]) {
   sp[128 * chunk] = lo;
   *(__attribute__((address_space(3))) double __attribute__((may_alias)) *)&sp[128 * chunk + 64] = x[2];
 }
-template <int S, int LIVE = S>
+// Terms 0 .. KS-1 come from LDS, terms S-R .. LIVE-1 from registers, terms KS .. S-R-1 are recomputed.
+template <int S, int LIVE = S, int R = reg_stash_terms(S)>
 struct StashTerm {
   static constexpr bool REG = false;
   static constexpr int KS = stash_terms(S);
+  static_assert(R % 4 == 0 && KS + R <= S, "the register-held chunks lie behind the stashed ones");
   MaskRow row;  // mismatch row of the site (S words)
   const double (&b)[S];
   double th, nth;
-  unsigned long long *stats = nullptr;
-  StashPtr sp = nullptr;  // terms 0 .. KS-1 as the update loop left them
+  unsigned long long *stats;
+  StashPtr sp;                       // terms 0 .. KS-1 as the update loop left them
+  const double (&xr)[R > 0 ? R : 1];  // terms S-R .. LIVE-1 as the update loop left them (R = 0: never read)
   template <typename F>
   RL_DEV void for_each(double &t, double &n, F &&f) const {
-    constexpr int NP = KS / 2, NS = KS / 4, NC = S / 4, A = STASH_AHEAD;
+    constexpr int NP = KS / 2, NS = KS / 4, NC = (S - R) / 4, A = STASH_AHEAD;
     // The LDS reads run A pairs of terms ahead, as the mask loads of for_each_chunk run a chunk ahead: wait for pair
     // p, request pair p + A, then work on pair p.  (Without the tie to pair p the scheduler requests all KS terms at
     // once and keeps them.)
@@ -213,6 +231,8 @@ struct StashTerm {
         if (4 * c + jj < LIVE) f(4 * c + jj, x[jj]);
       m = nm;
     }
+#pragma unroll
+    for (int i = S - R; i < LIVE; i++) f(i, xr[i - (S - R)]);
   }
 };
 

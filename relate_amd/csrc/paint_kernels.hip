@@ -133,9 +133,12 @@ RL_DEV void paint_backward(const PaintParams &p, int k, float *stage, WaveLink<W
   double b[S];
   // exact: the first KS weighted terms of a step go from the update loop to the sum through LDS (StashTerm,
   // exact_sum.h), in the wave's strip, which no stone uses during a step
-  constexpr int KS = MODE == 1 ? stash_terms(S) : 0;
+  // ... and the last R stay in registers of their own from the update loop to the end of the sum
+  constexpr int KS = MODE == 1 ? stash_terms(S) : 0, R = MODE == 1 ? reg_stash_terms(S) : 0;
   StashPtr sp = stash_of(stage);  // (not const: kept opaque in place, see the update loop)
   (void)sp;
+  double xr[R > 0 ? R : 1];
+  (void)xr;
 
   // ---- last SNP (:396-448)
   double ls = c.log_Nm1 - D * c.log_ntheta;  // normalizing_constant :399
@@ -168,7 +171,7 @@ RL_DEV void paint_backward(const PaintParams &p, int k, float *stage, WaveLink<W
   const auto make_term = [&](MaskRow row) {
     unsigned long long *const stats = p.stats ? p.stats + 8 : nullptr;
     if constexpr (MODE == 1)
-      return BackwardTerm{row, b, theta, ntheta, stats, sp};
+      return BackwardTerm{row, b, theta, ntheta, stats, sp, xr};
     else
       return BackwardTerm{row, b, theta, ntheta, stats};
   };
@@ -213,6 +216,7 @@ RL_DEV void paint_backward(const PaintParams &p, int k, float *stage, WaveLink<W
         b[j0 + jj] = v[jj];
         lsum += x[jj];  // the lane's share of :495-503
         if (KS > 0 && j0 < KS) xp[jj] = x[jj];
+        hold_term<S, R>(xr, j0 + jj, x[jj]);
       }
     });
     if (KS == S) {
