@@ -32,7 +32,8 @@ enum {
   RL_EIO = -4,       /* file could not be opened / read / written     */
   RL_EFORMAT = -5,   /* malformed chunk / paint file                  */
   RL_ESTATE = -6,    /* call sequence error (e.g. paint before load)  */
-  RL_ENOMEM = -7
+  RL_ENOMEM = -7,
+  RL_ETIMEOUT = -8   /* a segmented rl_paint gave up waiting for a hand-off */
 };
 
 /* Summation order of the per-site normalising constants.
@@ -148,6 +149,28 @@ int rl_set_paint_split(rl_ctx *ctx, int split);
  * always the loose one, which every N of the tile may run.  The stones are the same bit for bit either way; the
  * switch is there to time and to test the one against the other. */
 int rl_set_paint_fit(rl_ctx *ctx, int fit);
+/* The merged launch may cut every pass into segments that hand their state over through HBM and deal the segments
+ * segment by segment over all targets, so that all passes advance together and the launch ends with a full chip
+ * (DESIGN.md "Segmented passes").  backward / forward: segments per backward / forward pass; 1 = off (one workgroup
+ * per pass, the unsegmented kernels), 0 = automatic (the default): off when the launch's 2 * targets workgroups all
+ * fit the chip at once -- there is no tail to fill then --, else the measured default.  The stones are the same bit
+ * for bit for any setting.  RL_SUM_EXACT_SERIAL, RL_SUM_LANES32 and rl_set_paint_split never segment.  A segmented
+ * launch whose hand-off does not arrive within tens of seconds (it normally waits not at all) gives up:
+ * rl_paint returns RL_ETIMEOUT.  RL_EINVAL for a count below 0 or above 64. */
+int rl_set_paint_segments(rl_ctx *ctx, int backward, int forward);
+/* What the next rl_paint of the context will use in the RL_SUM_EXACT and RL_SUM_LANES orders (1, 1: unsegmented).
+ * Needs a chunk; the automatic rule asks the device for its CUs.  One exception: the loose variant of the S = 8 tile
+ * has no segmented kernel in the RL_SUM_LANES order (N <= 512 under rl_set_paint_fit(ctx, 0), or q < 4): this call
+ * then reports the RL_SUM_EXACT order's answer and the RL_SUM_LANES Paint runs unsegmented. */
+int rl_paint_segments(rl_ctx *ctx, int *backward, int *forward);
+/* What the last rl_paint did launch: the segments per backward / forward pass of its merged launch, (1, 1) for the
+ * unsegmented kernels whatever the setting (serial order, RL_SUM_LANES32, rl_set_paint_split, no twin).  RL_ESTATE
+ * before the first rl_paint. */
+int rl_paint_launched_segments(const rl_ctx *ctx, int *backward, int *forward);
+/* The bounds rule of the segments, pure host code (the kernels run the same function): segment s of seg walks
+ * [*first, *last) of the step range [lo, hi) -- every step once, in order; empty segments where hi - lo < seg.
+ * RL_EINVAL unless 0 <= s < seg. */
+int rl_paint_segment_range(int lo, int hi, int seg, int s, int *first, int *last);
 /* The rule itself, pure host code: the tile of N haplotypes (S, waves as rl_register_tile reports them), the number
  * `tail` of its last registers that take the backward pass's validity masks and the number `live` of registers that
  * hold a donor in some lane (S or S - 1).  Any pointer may be NULL.  RL_EINVAL for N < 2 or N > 10240.
@@ -204,6 +227,10 @@ int rl_debug_term_split(int S, int *ks, int *r);
 int rl_debug_stats(rl_ctx *ctx, unsigned long long *out16);
 /* ... and all 32 (16..24: cycles of the forward / backward step by segment, paint_kernels.hip) */
 int rl_debug_stats32(rl_ctx *ctx, unsigned long long *out32);
+/* Experiment builds (-DRL_STATS) with RELATE_AMD_TEST_TIMELINE set: when every workgroup of the last merged rl_paint was
+ * resident -- [*groups][2] counts of the device's 100 MHz wall clock at its start and end (tools/paint_timeline.py).
+ * cap: the pairs `out` holds; out may be NULL.  RL_ESTATE in the product build. */
+int rl_debug_timeline(rl_ctx *ctx, unsigned long long *out, long long cap, long long *groups);
 
 /* Copy stepping stones of window w to the host: alpha, beta: N*N floats
  * ([target][donor]); ls_alpha, ls_beta: N floats; bsnp_begin/end: N ints.

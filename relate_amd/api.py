@@ -85,7 +85,16 @@ def lib():
     return _lib
 
 
+class PaintTimeout(RelateError):
+    """RL_ETIMEOUT: a segmented paint() gave up waiting for a hand-off"""
+
+
+RL_ETIMEOUT = -8
+
+
 def _check(rc):
+    if rc == RL_ETIMEOUT:
+        raise PaintTimeout("librelate_amd error %d: %s" % (rc, lib().rl_last_error().decode()))
     if rc != 0:
         raise RelateError("librelate_amd error %d: %s" % (rc, lib().rl_last_error().decode()))
 
@@ -127,6 +136,14 @@ def term_split(S):
     ks, r = C.c_int(), C.c_int()
     _check(lib().rl_debug_term_split(int(S), C.byref(ks), C.byref(r)))
     return ks.value, r.value
+
+
+def paint_segment_range(lo, hi, seg, s):
+    """rl_paint_segment_range: -> (first, last): segment s of seg walks [first, last) of the step range [lo, hi)
+    (host code, no GPU; the kernels run the same function)"""
+    a, b = C.c_int(), C.c_int()
+    _check(lib().rl_paint_segment_range(int(lo), int(hi), int(seg), int(s), C.byref(a), C.byref(b)))
+    return a.value, b.value
 
 
 def tile_fit(N):
@@ -228,6 +245,22 @@ class Context:
     def set_paint_split(self, split):
         """one launch per direction (so that paint_times() has something to report) instead of one for both"""
         _check(lib().rl_set_paint_split(C.c_void_p(self._h), int(split)))
+
+    def set_paint_segments(self, backward, forward):
+        """segments per backward / forward pass of the merged launch: 0 automatic, 1 off (rl_set_paint_segments)"""
+        _check(lib().rl_set_paint_segments(C.c_void_p(self._h), int(backward), int(forward)))
+
+    def paint_segments(self):
+        """-> (backward, forward) segments per pass that the next exact / lanes paint() will use"""
+        b, f = C.c_int(), C.c_int()
+        _check(lib().rl_paint_segments(C.c_void_p(self._h), C.byref(b), C.byref(f)))
+        return b.value, f.value
+
+    def paint_launched_segments(self):
+        """-> (backward, forward) segments per pass that the last paint() launched (rl_paint_launched_segments)"""
+        b, f = C.c_int(), C.c_int()
+        _check(lib().rl_paint_launched_segments(C.c_void_p(self._h), C.byref(b), C.byref(f)))
+        return b.value, f.value
 
     def set_paint_fit(self, fit):
         """K1 runs the variant of the register tile fitted to N (True, the default) or always the loose one"""

@@ -214,6 +214,14 @@ struct rl_ctx {
   float ms_fwd = 0.f, ms_bwd = 0.f, ms_paint = 0.f;
   int paint_split = 0;  // rl_set_paint_split: one launch per direction instead of one for both
   int paint_fit = 1;    // rl_set_paint_fit: K1 runs the variant of the register tile that launch.h tile_fit picks (0: the loose one)
+  // rl_set_paint_segments: segments per backward / forward pass of the merged launch (0: the rule of
+  // paint_segments_rule, context.cpp; 1: off).  Their hand-off state, the chains' records and the launch's control
+  // block (device_types.h PaintSegs) exist only while a Paint of this context would be segmented.
+  int seg_b = 0, seg_f = 0;
+  int launched_seg_b = 1, launched_seg_f = 1;  // rl_paint_launched_segments: what the last rl_paint launched
+  rl::DevBuf d_seg_state, d_seg_rec, d_seg_ctl;
+  rl::DevBuf d_timeline;  // experiment builds (-DRL_STATS, RELATE_AMD_TEST_TIMELINE): rl_debug_timeline
+  long long timeline_groups = 0;
 };
 
 namespace rl {

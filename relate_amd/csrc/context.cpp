@@ -691,6 +691,54 @@ static int alloc_stones(rl_ctx *ctx) {
   return rc ? rc : ctx->d_beta.alloc(bytes);
 }
 
+// the segmented twin of the kernel that a Paint of this context launches in kernel mode `mode` exists
+static bool paint_twin_built(const rl_ctx *ctx, int mode) {
+  const int variant = tile_fit(ctx->lay, ctx->S, ctx->paint_fit && tile_fit_built(mode, ctx->S, ctx->waves)).variant;
+  return paint_segments_built(mode, ctx->S, ctx->waves, variant);
+}
+// Segments per pass of the next Paint in the `exact` and `lanes` orders (rl_set_paint_segments; 0 = this rule).
+// A launch of 2 * nloc one-pass workgroups that all fit the chip at once has no tail to fill: off.  Else the
+// measured default (launch.h).
+// mode: the kernel mode the Paint runs in (launch.h kernel_mode; 3: paint32), or -1: any order that has the twin
+static int paint_segments_rule(rl_ctx *ctx, int mode, int *nb, int *nf) {
+  int b = ctx->seg_b, f = ctx->seg_f;
+  if (b == 0 || f == 0) {
+    int cus = 0;
+    RL_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, ctx->device));
+    const long long slots = (long long)cus * 4 * tile_waves_per_simd(ctx->S) / ctx->waves;
+    const bool tail = 2LL * ctx->nloc > slots;
+    if (b == 0) b = tail ? PAINT_SEGMENTS_AUTO_BACKWARD : 1;
+    if (f == 0) f = tail ? PAINT_SEGMENTS_AUTO_FORWARD : 1;
+  }
+  const bool twin = mode < 0 ? paint_twin_built(ctx, 0) || paint_twin_built(ctx, 1) : mode < 3 && paint_twin_built(ctx, mode);
+  if (ctx->paint_split || !twin) b = f = 1;
+  *nb = b;
+  *nf = f;
+  return RL_OK;
+}
+// ... and their buffers, ahead of alloc_stones so that its choice between HBM and pinned memory sees them: the state
+// registers of every chain (2 * nloc * waves * 64 * S doubles: 0.4 GB at N = 5000, 1.6 GB at N = 10,000), a record per
+// chain, the control block.  None while segments are off.
+// mode as above: rl_prepare does not know the order yet (-1); rl_paint does, and a Paint that runs unsegmented in
+// its order allocates nothing (what an earlier Paint of another order left stays)
+static int alloc_segments(rl_ctx *ctx, int mode, int *nb, int *nf) {
+  int rc = paint_segments_rule(ctx, mode, nb, nf);
+  if (rc) return rc;
+  if (*nb <= 1 && *nf <= 1) {
+    int ab = 1, af = 1;
+    if (mode >= 0 && (rc = paint_segments_rule(ctx, -1, &ab, &af))) return rc;
+    if (ab > 1 || af > 1) return RL_OK;
+    ctx->d_seg_state.release();
+    ctx->d_seg_rec.release();
+    ctx->d_seg_ctl.release();
+    return RL_OK;
+  }
+  const size_t chains = 2 * (size_t)ctx->nloc;
+  if ((rc = ctx->d_seg_state.alloc(chains * ctx->waves * 64 * ctx->S * sizeof(double)))) return rc;
+  if ((rc = ctx->d_seg_rec.alloc(chains * PAINT_SEG_REC * sizeof(double)))) return rc;
+  return ctx->d_seg_ctl.alloc(paint_seg_ctl_bytes(ctx->nloc));
+}
+
 static int set_common(rl_ctx *ctx, int N, int L, const double *r, const double *rpos, const int *wb, int W) {
   if (!ctx || N < 2 || L < 2 || W < 1 || !r || !rpos || !wb) {
     set_error("rl_set_chunk: bad arguments");
@@ -949,6 +997,8 @@ int rl_prepare(rl_ctx *ctx) {
   int rc = upload_plan(ctx);
   if (rc) return rc;
   const size_t nloc = ctx->nloc, Wr = ctx->w_last - ctx->w_first + 1;  // stones: this context's target rows and windows only
+  int seg_b = 1, seg_f = 1;
+  if ((rc = alloc_segments(ctx, -1, &seg_b, &seg_f))) return rc;
   if ((rc = alloc_stones(ctx))) return rc;
   if ((rc = ctx->d_lsa.alloc(Wr * nloc * sizeof(float)))) return rc;
   if ((rc = ctx->d_lsb.alloc(Wr * nloc * sizeof(float)))) return rc;
@@ -969,6 +1019,8 @@ int rl_paint(rl_ctx *ctx, int sum_mode, float *kernel_ms) {
   int rc = upload_plan(ctx);
   if (rc) return rc;
   const size_t nloc = ctx->nloc, Wr = ctx->w_last - ctx->w_first + 1;  // stones: this context's target rows and windows only
+  int seg_b = 1, seg_f = 1;
+  if ((rc = alloc_segments(ctx, sum_mode == RL_SUM_LANES32 ? 3 : kernel_mode(sum_mode), &seg_b, &seg_f))) return rc;
   if ((rc = alloc_stones(ctx))) return rc;
   if ((rc = ctx->d_lsa.alloc(Wr * nloc * sizeof(float)))) return rc;
   if ((rc = ctx->d_lsb.alloc(Wr * nloc * sizeof(float)))) return rc;
@@ -1009,11 +1061,27 @@ int rl_paint(rl_ctx *ctx, int sum_mode, float *kernel_ms) {
   p.sum_mode = sum_mode;
   p.merge_order = 0;
   p.stats = nullptr;
+  const bool segmented = seg_b > 1 || seg_f > 1;
+  p.seg.nb = seg_b;
+  p.seg.nf = seg_f;
+  p.seg.state = segmented ? ctx->d_seg_state.as<double>() : nullptr;
+  p.seg.rec = segmented ? ctx->d_seg_rec.as<double>() : nullptr;
+  p.seg.ctl = segmented ? ctx->d_seg_ctl.as<unsigned>() : nullptr;
   if (getenv("RELATE_AMD_TEST_STATS")) {  // experiment builds (-DRL_STATS): 16 counters, see tools/exp_stats.py
     if ((rc = ctx->d_stats.alloc(32 * sizeof(unsigned long long)))) return rc;
     RL_HIP(hipMemset(ctx->d_stats.p, 0, 32 * sizeof(unsigned long long)));
     p.stats = ctx->d_stats.as<unsigned long long>();
   }
+#ifdef RL_STATS
+  p.seg.timeline = nullptr;
+  ctx->timeline_groups = 0;
+  if (getenv("RELATE_AMD_TEST_TIMELINE") && !ctx->paint_split) {  // (without the counters: they cost time of their own)
+    ctx->timeline_groups = (segmented ? (long long)(seg_b + seg_f) : 2LL) * ctx->nloc;
+    if ((rc = ctx->d_timeline.alloc((size_t)ctx->timeline_groups * 2 * sizeof(unsigned long long)))) return rc;
+    RL_HIP(hipMemset(ctx->d_timeline.p, 0, (size_t)ctx->timeline_groups * 2 * sizeof(unsigned long long)));
+    p.seg.timeline = ctx->d_timeline.as<unsigned long long>();
+  }
+#endif
 
   if (ctx->paint_split == 2) {
     // experiment: the two directions as two launches on two streams
@@ -1046,8 +1114,20 @@ int rl_paint(rl_ctx *ctx, int sum_mode, float *kernel_ms) {
     RL_HIP(hipEventSynchronize(ctx->ev2));
     RL_HIP(hipEventElapsedTime(&ctx->ms_paint, ctx->ev0, ctx->ev2));
     ctx->ms_bwd = ctx->ms_fwd = 0.f;
+    if (segmented) {  // the error word: a hand-off that never came (paint_pass.h seg_wait)
+      unsigned gave_up = 0;
+      RL_HIP(hipMemcpy(&gave_up, p.seg.ctl + 1, sizeof gave_up, hipMemcpyDeviceToHost));
+      if (gave_up) {
+        ctx->painted = false;
+        set_error("rl_paint: a segment of the launch (%d backward, %d forward per pass) waited over %d s for the "
+                  "state of the one before it; the stones are not valid", seg_b, seg_f, PAINT_SEG_TIMEOUT_S);
+        return RL_ETIMEOUT;
+      }
+    }
   }
   if (kernel_ms) *kernel_ms = ctx->ms_paint;
+  ctx->launched_seg_b = ctx->paint_split ? 1 : seg_b;
+  ctx->launched_seg_f = ctx->paint_split ? 1 : seg_f;
   ctx->painted = true;
   ctx->paint_mode = sum_mode;
   return RL_OK;
@@ -1056,6 +1136,18 @@ int rl_paint(rl_ctx *ctx, int sum_mode, float *kernel_ms) {
 int rl_debug_stats(rl_ctx *ctx, unsigned long long *out16) {
   if (!ctx || !ctx->d_stats.p || !out16) return RL_ESTATE;
   RL_HIP(hipMemcpy(out16, ctx->d_stats.p, 16 * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+  return RL_OK;
+}
+
+// experiment builds (-DRL_STATS): the last merged Paint's workgroups, [*groups][2] wall_clock64 counts (100 MHz) at
+// start and end; cap: pairs that `out` holds.  RL_ESTATE in any other build or without RELATE_AMD_TEST_TIMELINE.
+int rl_debug_timeline(rl_ctx *ctx, unsigned long long *out, long long cap, long long *groups) {
+  if (!ctx || !ctx->d_timeline.p || ctx->timeline_groups <= 0) return RL_ESTATE;
+  if (groups) *groups = ctx->timeline_groups;
+  if (out) {
+    const long long n = cap < ctx->timeline_groups ? cap : ctx->timeline_groups;
+    RL_HIP(hipMemcpy(out, ctx->d_timeline.p, (size_t)n * 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+  }
   return RL_OK;
 }
 
@@ -1071,6 +1163,49 @@ int rl_set_paint_split(rl_ctx *ctx, int split) {
     return RL_EINVAL;
   }
   ctx->paint_split = split;
+  return RL_OK;
+}
+
+int rl_set_paint_segments(rl_ctx *ctx, int backward, int forward) {
+  if (!ctx || backward < 0 || forward < 0 || backward > 64 || forward > 64) {
+    set_error("rl_set_paint_segments: needs a context and 0 (automatic) .. 64 segments per pass");
+    return RL_EINVAL;
+  }
+  ctx->seg_b = backward;
+  ctx->seg_f = forward;
+  return RL_OK;
+}
+
+int rl_paint_segments(rl_ctx *ctx, int *backward, int *forward) {
+  if (!ctx || !ctx->have_chunk) {
+    set_error("rl_paint_segments: no chunk loaded");
+    return RL_ESTATE;
+  }
+  int b = 1, f = 1;
+  const int rc = paint_segments_rule(ctx, -1, &b, &f);
+  if (rc) return rc;
+  if (backward) *backward = b;
+  if (forward) *forward = f;
+  return RL_OK;
+}
+
+int rl_paint_launched_segments(const rl_ctx *ctx, int *backward, int *forward) {
+  if (!ctx || !ctx->painted) {
+    set_error("rl_paint_launched_segments: call rl_paint first");
+    return RL_ESTATE;
+  }
+  if (backward) *backward = ctx->launched_seg_b;
+  if (forward) *forward = ctx->launched_seg_f;
+  return RL_OK;
+}
+
+int rl_paint_segment_range(int lo, int hi, int seg, int s, int *first, int *last) {
+  if (seg < 1 || s < 0 || s >= seg) {
+    set_error("rl_paint_segment_range: segment %d of %d", s, seg);
+    return RL_EINVAL;
+  }
+  if (first) *first = paint_segment_first(lo, hi, seg, s);
+  if (last) *last = paint_segment_first(lo, hi, seg, s + 1);
   return RL_OK;
 }
 

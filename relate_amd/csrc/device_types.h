@@ -25,6 +25,39 @@ struct PaintConsts {
   double inv_theta, inv_ntheta;  // RN(1 / theta), RN(1 / ntheta): div_by_const (paint_device.h)
 };
 
+// waves of K1's FP64 kernels of tile S that share a SIMD (exact_sum.h stash_terms; context.cpp paint_segments_rule)
+constexpr int tile_waves_per_simd(int S) { return S <= 8 ? 7 : S <= 16 ? 5 : S <= 32 ? 4 : S <= 48 ? 3 : 2; }
+
+// ---- segmented passes (paint_kernels.hip, DESIGN.md "Segmented passes") ----------------------------------------
+#ifdef __HIPCC__
+#define RL_HD __host__ __device__
+#else
+#define RL_HD
+#endif
+// Segment s of seg walks [paint_segment_first(lo, hi, seg, s), paint_segment_first(lo, hi, seg, s + 1)) of the step
+// range [lo, hi): every step exactly once and in order, for any length (0 and lengths below seg leave segments empty).
+// One function for the kernels and the host (rl_paint_segment_range); the product is formed in 64 bits.
+RL_HD inline int paint_segment_first(int lo, int hi, int seg, int s) {
+  const int64_t n = hi > lo ? (int64_t)hi - lo : 0;
+  return lo + (int)(n * s / seg);
+}
+constexpr int PAINT_SEG_TIMEOUT_S = 30;  // a segment gives up waiting for the one before it after this many seconds
+constexpr int PAINT_SEG_REC = 4;  // doubles of a chain's record: ls, cfac, the stone cursor, (spare)
+constexpr int PAINT_SEG_CTL = 4;  // words in front of the flags: the ticket counter, the error word, two spare
+// per-launch control block of a segmented Paint: ctl[0] ticket counter, ctl[1] error word, ctl[PAINT_SEG_CTL + c]
+// the flag of chain c (c = b for the backward pass of p.order[b], nloc + b for its forward pass): the number of
+// segments of the chain that have published their state.  Zeroed by the launch function before every launch.
+inline size_t paint_seg_ctl_bytes(int nloc) { return (((size_t)PAINT_SEG_CTL + 2 * (size_t)nloc) * 4 + 15) & ~(size_t)15; }
+struct PaintSegs {
+  int nb, nf;        // segments of a backward / a forward pass (1, 1: the unsegmented kernels)
+  double *state;     // [2 * nloc][WAVES][LIVE][64] the state registers of a chain between two of its segments
+  double *rec;       // [2 * nloc][PAINT_SEG_REC]
+  unsigned *ctl;
+#ifdef RL_STATS
+  unsigned long long *timeline;  // experiment builds: [workgroups][2] wall_clock64 at a workgroup's start and end, or null
+#endif
+};
+
 struct PaintParams {
   Layout lay;
   PaintConsts c;
@@ -49,6 +82,7 @@ struct PaintParams {
                             // forward ones.  (1 = interleaved is dead; the field and its branch in paint_kernel stay
                             // because that kernel gets 68 B of scratch without them, DESIGN_NOTES.md 13)
   unsigned long long *stats;  // 16 event counters (experiment builds with -DRL_STATS), else null
+  PaintSegs seg;              // read by the segmented kernels alone (last: every other field keeps its offset)
 };
 
 // RePaintSection over one window, all targets.

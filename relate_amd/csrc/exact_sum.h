@@ -133,7 +133,7 @@ struct MaskTerm {  // backward, lane-mask panel: e(i) * beta[i] with the site's 
 // stashed: 16 KB per wave, 10 instead of 16 waves per CU, the Paint 35 % slower.)
 constexpr int STASH_MAX = 36;
 constexpr int LDS_PER_CU = 160 * 1024;
-constexpr int tile_waves_per_simd(int S) { return S <= 8 ? 7 : S <= 16 ? 5 : S <= 32 ? 4 : S <= 48 ? 3 : 2; }
+// (tile_waves_per_simd: device_types.h, the host sizes the segmented launch by it)
 constexpr int stash_terms(int S) {
   const int fit = (LDS_PER_CU / (4 * tile_waves_per_simd(S)) - 512) / (64 * (int)sizeof(double));
   const int ks = fit < S ? fit : S;

@@ -61,6 +61,17 @@ constexpr bool tile_fit_built(int mode, int S, int waves) {
   return !(mode == 0 && ((S == 32 && waves == 1) || (S == 64 && waves == 2)));
 }
 
+// The segmented twins of the merged launch (paint_kernels.hip at -DRL_SEG) exist for the `lanes` and `exact` orders,
+// for every tile, variant and wave count whose twin keeps the unsegmented kernel's scratch (none) and waves per SIMD
+// (tools/kernel_resources.sh, profiles/paint_segments_kernel_resources.txt).  One does not and stays unsegmented:
+// the loose variant of S = 8 in the `lanes` order comes out with 68 B of scratch per lane (its fitted variants do not).
+constexpr bool paint_segments_built(int mode, int S, int waves, int variant) {
+  return (mode == 0 || mode == 1) && !(mode == 0 && S == 8 && variant == 0);
+}
+// segments per backward / forward pass where the rule segments at all (context.cpp paint_segments_rule): the
+// smallest setting that passed the A/B rule at C3 (profiles/paint_segments_ab.json)
+constexpr int PAINT_SEGMENTS_AUTO_BACKWARD = 1, PAINT_SEGMENTS_AUTO_FORWARD = 8;
+
 // the layout of all kernels: all N donors, the target keeps a slot that is pinned to +0.0;
 // cut into 64*waves balanced runs (target_waves)
 inline Layout make_layout(int N, int waves = 1) {
@@ -117,6 +128,16 @@ hipError_t launch_paint_dir(K kernel_of, const PaintParams &p, int waves, int di
     hipLaunchKernelGGL(kernel_of(std::integral_constant<int, 0>{}), grid, block, 0, stream, p);
   return hipGetLastError();
 }
+// the segmented merged launch: (nb + nf) * nloc workgroups that draw their work by ticket; the control block (ticket
+// counter, error word, flags) is zeroed on the stream in front of every launch
+template <typename K>
+hipError_t launch_paint_segments(K kernel, const PaintParams &p, int waves, hipStream_t stream) {
+  const hipError_t e = hipMemsetAsync(p.seg.ctl, 0, paint_seg_ctl_bytes(p.nloc), stream);
+  if (e != hipSuccess) return e;
+  const dim3 grid((unsigned)(p.seg.nb + p.seg.nf) * (unsigned)p.nloc), block(64 * waves);
+  hipLaunchKernelGGL(kernel, grid, block, 0, stream, p);
+  return hipGetLastError();
+}
 hipError_t launch_lane_masks(const uint32_t *bits, int row_words, int L, const Layout &lay, int S, int waves,
                              unsigned long long *masks, hipStream_t stream);
 
@@ -132,6 +153,8 @@ hipError_t launch_paint_mode(const PaintParams &p, int S, int waves, int dir, hi
 // build compiles them side by side), with its own launcher
 template <int MODE, int VARIANT>
 hipError_t launch_paint_variant(const PaintParams &p, int S, int waves, int dir, hipStream_t stream);
+template <int MODE, int VARIANT>
+hipError_t launch_paint_seg_variant(const PaintParams &p, int S, int waves, hipStream_t stream);
 template <int MODE>
 hipError_t launch_repaint_mode(const RepaintParams &p, int S, int waves, hipStream_t stream);
 template <> hipError_t launch_paint_mode<0>(const PaintParams &, int, int, int, hipStream_t, int);
@@ -145,6 +168,13 @@ template <> hipError_t launch_paint_mode<3>(const PaintParams &, int, int, int, 
   template <> hipError_t launch_paint_variant<m, 3>(const PaintParams &, int, int, int, hipStream_t);
 RL_DECLARE_VARIANTS(0) RL_DECLARE_VARIANTS(1) RL_DECLARE_VARIANTS(2)
 #undef RL_DECLARE_VARIANTS
+#define RL_DECLARE_SEG_VARIANTS(m)                                                                \
+  template <> hipError_t launch_paint_seg_variant<m, 0>(const PaintParams &, int, int, hipStream_t); \
+  template <> hipError_t launch_paint_seg_variant<m, 1>(const PaintParams &, int, int, hipStream_t); \
+  template <> hipError_t launch_paint_seg_variant<m, 2>(const PaintParams &, int, int, hipStream_t); \
+  template <> hipError_t launch_paint_seg_variant<m, 3>(const PaintParams &, int, int, hipStream_t);
+RL_DECLARE_SEG_VARIANTS(0) RL_DECLARE_SEG_VARIANTS(1)
+#undef RL_DECLARE_SEG_VARIANTS
 template <> hipError_t launch_repaint_mode<0>(const RepaintParams &, int, int, hipStream_t);
 template <> hipError_t launch_repaint_mode<1>(const RepaintParams &, int, int, hipStream_t);
 template <> hipError_t launch_repaint_mode<2>(const RepaintParams &, int, int, hipStream_t);

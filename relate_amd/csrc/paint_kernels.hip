@@ -36,8 +36,10 @@ namespace rl {
 // donor in some lane -- every unrolled loop leaves the rest out, so a dead register costs neither instructions nor
 // VGPRs; the last TAIL registers take the backward pass's per-lane validity masks (whole chunks of 4), and registers
 // S - FTAIL .. LIVE - 1 the forward pass's validity compare.
-template <int S, int FTAIL, int MODE, int WAVES, int LIVE>
-RL_DEV void paint_forward(const PaintParams &p, int k, float *stage, WaveLink<WAVES> &lk) {
+// SEG: the pass is one segment of a segmented pass (paint_pass.h): it walks its share of the steps, takes the state
+// over from the segment before it instead of running the prologue and leaves it to the next one.
+template <int S, int FTAIL, int MODE, int WAVES, int LIVE, bool SEG = false>
+RL_DEV void paint_forward(const PaintParams &p, int k, float *stage, WaveLink<WAVES> &lk, SegShared *sh = nullptr) {
   const int wv = lk.w;  // this wave of the target's workgroup (wave-uniform)
   PaintLane<S> pl;
   pl.init(p.lay, k, wv);
@@ -46,7 +48,17 @@ RL_DEV void paint_forward(const PaintParams &p, int k, float *stage, WaveLink<WA
   const int D = forward_steps(k, Dk);  // (paint_device.h: ends at the range's last stone)
 
   double a[S];
-
+  typedef RegTerm<S, LIVE> Term;
+  double ssum, ls, cfac;
+  int wa, next_stone, i0 = 1, i1 = D;
+  if constexpr (SEG) {
+    i0 = paint_segment_first(1, D, sh->nseg, sh->s);
+    i1 = paint_segment_first(1, D, sh->nseg, sh->s + 1);
+  }
+  if (SEG && sh->s > 0) {
+    seg_restore<S, LIVE, WAVES>(p, a, pl.lane, wv, sh->chain, ls, cfac, wa);
+    next_stone = forward_stone_index(k, wa);
+  } else {
   // ---- SNP 0 (fast_painting.cpp:207-253)
   for_each_chunk<S, 8>(site_row(p.masks, S, p.L, st[0], WAVES, wv), [&](int j0, const u64x8 &m) {
 #pragma unroll
@@ -58,18 +70,18 @@ RL_DEV void paint_forward(const PaintParams &p, int k, float *stage, WaveLink<WA
       a[j0 + jj] = v;
     }
   });
-  typedef RegTerm<S, LIVE> Term;
   set_slot<S, LIVE>(a, pl.jk, pl.kbit, 0.0);
-  double ssum = wave_sum<MODE, S, WAVES>(Term{a, 0.0, 0.0, p.stats}, local_sum<S>(Term{a}), lk);
-  double ls = 0.0;
-  int wa = 0, next_stone = forward_stone_index(k, 0);
+  ssum = wave_sum<MODE, S, WAVES>(Term{a, 0.0, 0.0, p.stats}, local_sum<S>(Term{a}), lk);
+  ls = 0.0;
+  wa = 0, next_stone = forward_stone_index(k, 0);
   while (next_stone == 0) {
     write_forward_stone<S, LIVE>(wa, pl, wv, a, ls, stage);
     next_stone = forward_stone_index(k, wa);
   }
-  double cfac = cfp[0] * ssum;  // :260
+  cfac = cfp[0] * ssum;  // :260
+  }
 
-  ForwardRows<S, WAVES> pipe(st, D, 1);
+  ForwardRows<S, WAVES> pipe(st, D, i0);
   const double K1 = in_vgpr(c.K1);
   constexpr int CH = S % 16 == 0 ? 16 : 8;  // registers per chunk of masks
   typedef typename MaskChunk<CH>::type Chunk;
@@ -77,7 +89,7 @@ RL_DEV void paint_forward(const PaintParams &p, int k, float *stage, WaveLink<WA
   Chunk first = load_masks<CH>(row, 0);
   unsigned long long seg1 = 0, seg2 = 0, seg3 = 0, seg4 = 0, seg5 = 0;
   (void)seg1; (void)seg2; (void)seg3; (void)seg4; (void)seg5;
-  for (int i = 1; i < D; i++) {
+  for (int i = i0; i < i1; i++) {
     RL_TICK(0);
     pipe.retire();
     RL_TICK(1);
@@ -109,6 +121,9 @@ RL_DEV void paint_forward(const PaintParams &p, int k, float *stage, WaveLink<WA
     }
   }
   pipe.retire();
+  if constexpr (SEG) {
+    if (sh->s + 1 < sh->nseg) seg_save<S, LIVE, WAVES>(a, pl.lane, wv, ls, cfac, wa, sh);
+  }
 #ifdef RL_STATS
   if (MODE != 0 && p.stats && pl.lane == 0 && wv == 0) {  // whole step | chunk loop | sum | rescale test + factor
     atomicAdd(&p.stats[16], seg1 + seg2 + seg3 + seg4 + seg5);
@@ -122,8 +137,8 @@ RL_DEV void paint_forward(const PaintParams &p, int k, float *stage, WaveLink<WA
 #endif
 }
 
-template <int S, int TAIL, int MODE, int WAVES, int LIVE>
-RL_DEV void paint_backward(const PaintParams &p, int k, float *stage, WaveLink<WAVES> &lk) {
+template <int S, int TAIL, int MODE, int WAVES, int LIVE, bool SEG = false>
+RL_DEV void paint_backward(const PaintParams &p, int k, float *stage, WaveLink<WAVES> &lk, SegShared *sh = nullptr) {
   const int wv = lk.w;
   PaintLane<S> pl;
   pl.init(p.lay, k, wv);
@@ -140,8 +155,23 @@ RL_DEV void paint_backward(const PaintParams &p, int k, float *stage, WaveLink<W
   double xr[R > 0 ? R : 1];
   (void)xr;
 
+  // the walk: j from j_first down to j_last (a segment: its share of the steps D - 2 .. backward_last, counted from
+  // the top)
+  int j_first = D - 2, j_last = 0;
+  if constexpr (SEG) {
+    j_last = backward_last(k);
+    const int n = D - 1 - j_last;
+    j_first = D - 2 - paint_segment_first(0, n, sh->nseg, sh->s);
+    j_last = D - 1 - paint_segment_first(0, n, sh->nseg, sh->s + 1);
+  }
+  double ls, bsum, cfac;
+  int we, next_stone;
+  if (SEG && sh->s > 0) {
+    seg_restore<S, LIVE, WAVES>(p, b, pl.lane, wv, sh->chain, ls, cfac, we);
+    next_stone = backward_stone_index(k, we);
+  } else {
   // ---- last SNP (:396-448)
-  double ls = c.log_Nm1 - D * c.log_ntheta;  // normalizing_constant :399
+  ls = c.log_Nm1 - D * c.log_ntheta;  // normalizing_constant :399
 #pragma unroll
   for (int i = 0; i < LIVE; i++) {
     double v = 1.0;
@@ -149,17 +179,19 @@ RL_DEV void paint_backward(const PaintParams &p, int k, float *stage, WaveLink<W
     b[i] = v;
   }
   set_slot<S, LIVE>(b, pl.jk, pl.kbit, 0.0);  // written as beta[k] = 1 below, +0.0 from then on
-  double bsum = p.binit[k];  // serial sum of theta/ntheta minus ntheta (:421-431)
-  int we = p.W - 1, next_stone = backward_stone_index(k, we);
+  bsum = p.binit[k];  // serial sum of theta/ntheta minus ntheta (:421-431)
+  we = p.W - 1, next_stone = backward_stone_index(k, we);
   while (next_stone == D - 1) {
     write_backward_stone<S, LIVE>(we, pl, wv, b, ls, 1.0f, stage);  // beta[k] = 1 at the last SNP
     next_stone = backward_stone_index(k, we);
   }
-  double cfac = cfp[D - 1] * bsum;  // :454-455
+  cfac = cfp[D - 1] * bsum;  // :454-455
+  }
 
   // row pipeline as in paint_forward: step j reads the rows of s0 (site j+1)
   // and s1 (site j); the row of s2 (site j-1) goes to L2 during the step
   int s0 = st[D - 1], s1 = D > 1 ? st[D - 2] : 0, s2 = D > 2 ? st[D - 3] : 0;
+  if constexpr (SEG) s0 = st[j_first + 1], s1 = j_first >= 0 ? st[j_first] : 0, s2 = j_first >= 1 ? st[j_first - 1] : 0;
   uint32_t touched = 0;
   MaskRow rown = site_row(p.masks, S, p.L, s0, WAVES, wv);  // the later site's mismatches drive the update (:481-488)
   MaskRow rowh = site_row(p.masks, S, p.L, s1, WAVES, wv);
@@ -175,8 +207,8 @@ RL_DEV void paint_backward(const PaintParams &p, int k, float *stage, WaveLink<W
     else
       return BackwardTerm{row, b, theta, ntheta, stats};
   };
-  const int j_last = backward_last(k);  // (paint_device.h: D and ls above keep the whole pass, the walk ends at the range's first stone)
-  for (int j = D - 2; j >= j_last; j--) {
+  if constexpr (!SEG) j_last = backward_last(k);  // (paint_device.h: D and ls above keep the whole pass, the walk ends at the range's first stone)
+  for (int j = j_first; j >= j_last; j--) {
     retire_touch(touched);
     if (j > 0) touched = touch_row(p.masks, S, s2, pl.lane, WAVES, wv);
     s0 = s1;
@@ -256,6 +288,9 @@ RL_DEV void paint_backward(const PaintParams &p, int k, float *stage, WaveLink<W
     }
   }
   retire_touch(touched);
+  if constexpr (SEG) {
+    if (sh->s + 1 < sh->nseg) seg_save<S, LIVE, WAVES>(b, pl.lane, wv, ls, cfac, we, sh);
+  }
 #ifdef RL_STATS
   if (p.stats && pl.lane == 0 && wv == 0) {  // whole step | divisions + slot + loads | chunk loop | sum | rescale test + factor
     atomicAdd(&p.stats[20], bseg1 + bseg2 + bseg3 + bseg4);
@@ -267,7 +302,8 @@ RL_DEV void paint_backward(const PaintParams &p, int k, float *stage, WaveLink<W
 
 // S <= 80: hold the kernel to 256 registers so that two waves share a SIMD.
 // WAVES = 2: a workgroup of two waves paints one target (N > 5120).
-template <int S, int TAIL, int MODE, int WAVES, int DIR, int LIVE = S, int FTAIL = TAIL>
+// SEGMENTED (DIR = 2 only): a workgroup is one segment of one pass, drawn by ticket (paint_pass.h seg_draw).
+template <int S, int TAIL, int MODE, int WAVES, int DIR, int LIVE = S, int FTAIL = TAIL, bool SEGMENTED = false>
 __global__ void __launch_bounds__(64 * WAVES, 2) paint_kernel(const PaintParams p) {
   // per wave: the staging strip of the stones (4 KB) and, where an exact backward pass runs, its stash of weighted
   // terms (up to 18 KB) in the same storage -- a stone is never written during a sum
@@ -276,6 +312,31 @@ __global__ void __launch_bounds__(64 * WAVES, 2) paint_kernel(const PaintParams 
   __shared__ __attribute__((aligned(16))) float stage[WAVES][WAVE_FLOATS];
   __shared__ WaveLinkStorage link;
   WaveLink<WAVES> lk = make_wave_link<WAVES>(&link);
+#ifdef RL_STATS
+  // experiment builds: when the workgroup was resident (tools/paint_timeline.py); its end is stamped by WorkgroupStamp's
+  // destructor on every way out
+  struct WorkgroupStamp {
+    unsigned long long *at, t0;
+    __device__ ~WorkgroupStamp() {
+      if (at && threadIdx.x == 0) {
+        at[0] = t0;
+        at[1] = (unsigned long long)wall_clock64();
+      }
+    }
+  } stamp{p.seg.timeline ? p.seg.timeline + 2 * (size_t)blockIdx.x : nullptr, (unsigned long long)wall_clock64()};
+#endif
+  if constexpr (SEGMENTED) {
+    static_assert(DIR == 2, "segmented twins exist for the merged launch only");
+    __shared__ SegShared sh;
+    if (!seg_draw(p, &sh)) return;
+    const int k = p.order[sh.b];
+    if (sh.s > 0 && !seg_wait(p, &sh)) return;
+    if (sh.backward)
+      paint_backward<S, TAIL, MODE, WAVES, LIVE, true>(p, k, stage[lk.w], lk, &sh);
+    else
+      paint_forward<S, FTAIL, MODE, WAVES, LIVE, true>(p, k, stage[lk.w], lk, &sh);
+    return;
+  }
   int b = blockIdx.x;
   bool backward = DIR == 1;
   if (DIR == 2) {
@@ -314,6 +375,22 @@ __global__ void __launch_bounds__(64 * WAVES, 2) paint_kernel(const PaintParams 
 
 // This translation unit holds one variant of every tile (launch.h tile_fit): RL_FIT = 0 the loose one, which is the
 // tile list's, 1 / 2 the tight ones, 3 tight minus one.
+#ifdef RL_SEG
+// ... and, at -DRL_SEG, the segmented twins of that variant's merged launch, alone in a translation unit of their own
+template <>
+hipError_t launch_paint_seg_variant<RL_MODE, RL_FIT>(const PaintParams &p, int tile, int waves, hipStream_t stream) {
+  return dispatch_tile(tile, waves, [&](auto s, auto t, auto w) {
+    constexpr int S = s(), WAVES = w();
+    constexpr int TAIL = RL_FIT == 0 ? t() : 4, LIVE = RL_FIT == 3 ? S - 1 : S;
+    constexpr int FTAIL = RL_FIT == 0 ? TAIL : RL_FIT == 1 ? 1 : RL_FIT == 2 ? 4 : 2;
+    if constexpr ((RL_FIT == 0 || tile_fit_built(RL_MODE, S, WAVES)) && paint_segments_built(RL_MODE, S, WAVES, RL_FIT)) {
+      return launch_paint_segments(&paint_kernel<S, TAIL, RL_MODE, WAVES, 2, LIVE, FTAIL, true>, p, WAVES, stream);
+    } else {
+      return hipErrorInvalidValue;
+    }
+  });
+}
+#else
 template <>
 hipError_t launch_paint_variant<RL_MODE, RL_FIT>(const PaintParams &p, int tile, int waves, int dir,
                                                  hipStream_t stream) {
@@ -336,7 +413,19 @@ hipError_t launch_paint_variant<RL_MODE, RL_FIT>(const PaintParams &p, int tile,
 template <>
 hipError_t launch_paint_mode<RL_MODE>(const PaintParams &p, int tile, int waves, int dir, hipStream_t stream,
                                       int fit) {
-  switch (tile_fit(p.lay, tile, fit != 0 && tile_fit_built(RL_MODE, tile, waves)).variant) {
+  const int variant = tile_fit(p.lay, tile, fit != 0 && tile_fit_built(RL_MODE, tile, waves)).variant;
+#if RL_MODE < 2
+  if (p.seg.nb > 1 || p.seg.nf > 1) {  // (context.cpp paint_segments_rule: the merged launch alone)
+    if (dir != 2) return hipErrorInvalidValue;
+    switch (variant) {
+      case 0: return launch_paint_seg_variant<RL_MODE, 0>(p, tile, waves, stream);
+      case 1: return launch_paint_seg_variant<RL_MODE, 1>(p, tile, waves, stream);
+      case 2: return launch_paint_seg_variant<RL_MODE, 2>(p, tile, waves, stream);
+      default: return launch_paint_seg_variant<RL_MODE, 3>(p, tile, waves, stream);
+    }
+  }
+#endif
+  switch (variant) {
     case 0: return launch_paint_variant<RL_MODE, 0>(p, tile, waves, dir, stream);
     case 1: return launch_paint_variant<RL_MODE, 1>(p, tile, waves, dir, stream);
     case 2: return launch_paint_variant<RL_MODE, 2>(p, tile, waves, dir, stream);
@@ -344,5 +433,6 @@ hipError_t launch_paint_mode<RL_MODE>(const PaintParams &p, int tile, int waves,
   }
 }
 #endif
+#endif  // RL_SEG
 
 }  // namespace rl

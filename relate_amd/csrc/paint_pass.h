@@ -188,4 +188,106 @@ RL_DEV void write_backward_stone(int &w, const PaintLane<S> &pl, const int &wv, 
   w--;
 }
 
+// ---- segmented passes (K1's merged launch) ------------------------------------
+// A pass cut into segments that hand their state over through HBM: the workgroups of a launch are dealt segment by
+// segment over all chains (a chain: one pass of one target), so that all chains advance together and the launch ends
+// with one segment's tail instead of one pass's (DESIGN.md "Segmented passes").  A workgroup draws a ticket; tickets
+// map to items direction-major and segment-major -- every chain's backward segment 0 in launch order, then segment 1,
+// ..., then the forward segments alike --, so an item waits only for an item with a smaller ticket, whose holder is
+// resident or done: no wait can form a cycle whatever order the dispatcher starts workgroups in.
+// Hand-off: plain stores of the state, every storing wave's vmcnt(0), the workgroup's barrier, one lane's agent-scope
+// release and wait, a relaxed agent-scope store of the chain's flag; the consumer polls that word relaxed, acquires
+// once at agent scope, waits and joins the barrier in front of the other lanes' loads.  The state comes back by vector
+// loads alone (nothing handed over goes through the scalar cache).
+typedef __attribute__((address_space(1))) unsigned SegWord;
+struct SegShared {
+  int backward, b, chain, s, nseg;  // this workgroup's item: segment s of nseg of chain `chain` (launch position b)
+  int left, failed;                 // the launch was given up before / while this workgroup waited
+};
+constexpr unsigned long long PAINT_SEG_TIMEOUT = PAINT_SEG_TIMEOUT_S * 100000000ull;  // wall_clock64 counts at 100 MHz
+#define RL_RELAXED_AGENT __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT
+
+// draw the workgroup's ticket and look at the error word; false: leave
+RL_DEV bool seg_draw(const PaintParams &p, SegShared *sh) {
+  if (threadIdx.x == 0) {
+    SegWord *const ctl = (SegWord *)p.seg.ctl;
+    int t = (int)__hip_atomic_fetch_add(ctl, 1u, RL_RELAXED_AGENT);
+    sh->left = __hip_atomic_load(ctl + 1, RL_RELAXED_AGENT) != 0u;
+    const int nback = p.seg.nb * p.nloc;
+    sh->backward = t < nback;
+    if (t >= nback) t -= nback;
+    sh->s = t / p.nloc;
+    sh->b = t % p.nloc;
+    sh->nseg = sh->backward ? p.seg.nb : p.seg.nf;
+    sh->chain = (sh->backward ? 0 : p.nloc) + sh->b;
+  }
+  __syncthreads();
+  return !sh->left;
+}
+// wait until the segment before this one has published the chain's state; false: the wait ran out (or another
+// workgroup's had) and the launch is given up -- the error word is set, every later workgroup leaves at its ticket
+RL_DEV bool seg_wait(const PaintParams &p, SegShared *sh) {
+  if (threadIdx.x == 0) {
+    SegWord *const ctl = (SegWord *)p.seg.ctl, *const flag = ctl + PAINT_SEG_CTL + sh->chain;
+    const unsigned want = (unsigned)sh->s;
+    const unsigned long long t0 = wall_clock64();
+    int failed = 0;
+    while (__hip_atomic_load(flag, RL_RELAXED_AGENT) != want) {
+      __builtin_amdgcn_s_sleep(32);
+      if (wall_clock64() - t0 > PAINT_SEG_TIMEOUT || __hip_atomic_load(ctl + 1, RL_RELAXED_AGENT) != 0u) {
+        __hip_atomic_store(ctl + 1, 1u, RL_RELAXED_AGENT);
+        failed = 1;
+        break;
+      }
+    }
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    sh->failed = failed;
+  }
+  __syncthreads();
+  return !sh->failed;
+}
+RL_DEV double uniform_f64(double v) {
+  const long long x = __double_as_longlong(v);
+  const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)x), hi = __builtin_amdgcn_readfirstlane((unsigned)(x >> 32));
+  return __longlong_as_double((long long)(((unsigned long long)hi << 32) | lo));
+}
+// the state of a chain as its last segment left it: the LIVE state registers of every lane, raw; the logscale, the
+// step's factor and the stone cursor from the chain's record (stored by one lane, loaded by all, made uniform)
+template <int S, int LIVE, int WAVES>
+RL_DEV void seg_restore(const PaintParams &p, double (&v)[S], int lane, int wv, int chain, double &ls, double &cfac,
+                        int &cursor) {
+  const double *st = p.seg.state + ((size_t)chain * WAVES + wv) * (LIVE * 64) + lane;
+  const double *rec = p.seg.rec + (size_t)chain * PAINT_SEG_REC;
+  asm volatile("" : "+v"(st), "+v"(rec));  // vector loads
+#pragma unroll
+  for (int j = 0; j < LIVE; j++) v[j] = st[j * 64];
+  ls = uniform_f64(rec[0]);
+  cfac = uniform_f64(rec[1]);
+  cursor = __builtin_amdgcn_readfirstlane((int)rec[2]);
+}
+// ... and left for the next one, behind the last step's stones; then the chain's flag says so
+template <int S, int LIVE, int WAVES>
+RL_DEV void seg_save(const double (&v)[S], int lane, int wv, const double &ls, const double &cfac, int cursor,
+                     const SegShared *sh) {
+  const ColdParams cp = cold_params<PaintParams>();
+  const int chain = sh->chain;
+  double *st = cp->seg.state + ((size_t)chain * WAVES + wv) * (LIVE * 64) + lane;
+#pragma unroll
+  for (int j = 0; j < LIVE; j++) st[j * 64] = v[j];
+  if (lane == 0 && wv == 0) {
+    double *rec = cp->seg.rec + (size_t)chain * PAINT_SEG_REC;
+    rec[0] = ls;
+    rec[1] = cfac;
+    rec[2] = (double)cursor;
+  }
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __hip_atomic_store((SegWord *)cp->seg.ctl + PAINT_SEG_CTL + chain, (unsigned)(sh->s + 1), RL_RELAXED_AGENT);
+  }
+}
+
 }  // namespace rl

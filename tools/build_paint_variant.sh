@@ -18,6 +18,12 @@ for m in 0 1 2; do
     pids+=($!)
   done
 done
+for m in 0 1; do  # the segmented twins of the merged launch (RL_SEG; `lanes` and `exact`)
+  for v in 0 1 2 3; do
+    /opt/rocm/bin/hipcc $FLAGS $EXTRA -DRL_MODE=$m -DRL_FIT=$v -DRL_SEG -c paint_kernels.hip -o ../../build/variants/paint_kernels_m${m}_f${v}_seg_$NAME.o &
+    pids+=($!)
+  done
+done
 for p in "${pids[@]}"; do wait $p; done
 OBJS=$(ls ../../build/obj/*.o | grep -v "paint_kernels_m")
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o ../variants/librelate_amd_$NAME.so $OBJS ../../build/variants/*_$NAME.o -lpthread -lz
