@@ -675,6 +675,56 @@ int rl_copying_rows_host(const float *rows, const double *weights, int D, int N,
 int rl_stage_copying_matrix(const char *out_dir, int chunk_index, int first_section, int last_section,
                             const rl_stage_opts *opts, const char *out_path);
 
+/* ------------------------------------------------ CoalescentRateForSection */
+/* Epoch-binned pairwise coalescence counts and opportunities of a dated tree sequence, and the rates they give: the
+ * reference's `RelateCoalescentRate --mode CoalescentRateForSection` and `--mode FinalizePopulationSize`
+ * (include/evaluate/coalescent_rate/), whose .bin and .coal files these entries reproduce byte for byte.
+ *   Epochs ep[0..E-1]: floats, ep[0] = 0, rising; 2 <= E <= 64.  Trees as CompareTopology takes them (2N-1 parents,
+ *   binary, parent[v] > v, node 2N-2 the root); branch lengths >= 0 and finite; anything else is RL_EINVAL with a
+ *   message naming the tree and the node.
+ *   Per tree with the float `factor`: t(leaf) = 0, t(m) = (float)((double)t(c) + branch_length[c]), c the first child
+ *   of m in node order -- a float at every node (GetCoalescentRate, CoalescentRateForSection.cpp:17-89).  For i < j
+ *   with t = t(MRCA(i,j)) and e = 0 .. E-2 in turn: if t < ep[e+1]: D[e][i][j] += factor,
+ *   D[e][j][i] += factor * (t - ep[e]), stop; else D[e][j][i] += factor * (ep[e+1] - ep[e]).  Float arithmetic, the
+ *   product rounded before the sum; plane E-1 and the diagonals stay 0.  One addition per element and tree, the trees
+ *   in order: the host and the device return the reference's bits.
+ *   rl_coalrate_epochs (replaces :296-380): the default 31 epochs of years_per_gen (the reference's default: 28), or
+ *     those of `--bins lower,upper,step`.  *nepochs: on entry the room in epochs, on return the count (RL_EINVAL if it
+ *     does not fit, the count still set).
+ *   rl_coalrate_trees (replaces :17-89 and the loop body :475-479): parents, branch_length [ntrees][2N-1], factors
+ *     [ntrees] (any finite value), out [E][N][N] floats, overwritten.  device >= 0: on that GPU
+ *     (relate_amd/csrc/coalrate_kernels.hip; 2 <= N <= 10240, D kept on the device -- 4 E N^2 bytes, RL_ENOMEM if the
+ *     device has not that much free -- while the trees go up in batches of rl_coalrate_batch_trees(N); RL_ENODEVICE
+ *     without one); device < 0: the host implementation (coalrate.cpp), one thread, any N >= 2.
+ *   rl_coalrate_anc (replaces :265-294, :441-481 and AncMutIterators, src/mutations.cpp:713-774, :854-912): the trees
+ *     of a TEXT .anc, one in memory at a time, each with the factor of NextTree from the .mut -- half the dist before
+ *     its first SNP, plus its SNPs' dists, minus half the last; 0 for a tree without SNPs -- and, as the reference's
+ *     loop runs once more after NextTree has returned -1, the last tree again with the factor -1.  *N_out = N; with
+ *     out NULL nothing else happens.  RL_EINVAL: sample ages in the header, .gz inputs, tree indices that fall in the
+ *     .mut.  (--mask and --dist are refused by the CLI.)
+ *   rl_coalrate_write_bin / rl_coalrate_read_bin (replace :565-583 and FinalizePopulationSize.cpp:43-53): int32 E,
+ *     E floats, then E times CollapsedMatrix<float>::DumpToFile (src/collapsed_matrix.hpp:204-213): two 64-bit words
+ *     N, N and N*N floats.  read_bin with data NULL (and epochs NULL or room for *nepochs of the first call) returns
+ *     E and N alone.
+ *   rl_coalrate_finalize (replaces FinalizePopulationSize.cpp:57-91, :191-235): over i < j in that order, float sums
+ *     of D[e][i][j] (num) and D[e][j][i] (denom) per (group pair, epoch e < E-1); rates [g][g][E] = num / denom of the
+ *     unordered group pair, a float division (0 / 0 in the last epoch and for a pair of groups without pairs).
+ *     group_of_haplotype NULL: one group (ngroups = 1).
+ *   rl_coalrate_finalize_files (replaces FinalizePopulationSize.cpp:13-136, :138-291 and Sample::Read,
+ *     src/sample.cpp:4-110): bin_path -> coal_path as the reference writes it with operator<<; poplabels: the second
+ *     column is the group, two haplotypes per line unless a fourth column is `1`; `hap` is RL_EINVAL. */
+int rl_coalrate_batch_trees(int N);
+int rl_coalrate_epochs(float years_per_gen, const char *bins_or_null, float *epochs, int *nepochs);
+int rl_coalrate_trees(const int *parents, const double *branch_length, const float *factors, int N, int ntrees,
+                      const float *epochs, int nepochs, int device, float *out);
+int rl_coalrate_anc(const char *anc_path, const char *mut_path, const float *epochs, int nepochs, int device,
+                    float *out_or_null, int *N_out);
+int rl_coalrate_write_bin(const char *path, const float *epochs, int nepochs, const float *data, int N);
+int rl_coalrate_read_bin(const char *path, float *epochs_or_null, int *nepochs, float *data_or_null, int *N);
+int rl_coalrate_finalize(const float *data, int N, int nepochs, const int *group_of_haplotype_or_null, int ngroups,
+                         double *rates);
+int rl_coalrate_finalize_files(const char *bin_path, const char *poplabels_or_null, const char *coal_path);
+
 /* ------------------------------------------------------------------ tools */
 /* Synthetic block-coalescent panel (stand-in for MakeChunks input,
  * SURVEY.md 8d).  seq_chars (L*N) and/or bits (L*row_words) may be NULL. */

@@ -75,6 +75,16 @@ def lib():
         L.rl_pairwise_anc.restype = C.c_int
         L.rl_pairwise_anc.argtypes = [C.POINTER(C.c_char_p), C.c_int, C.c_int, C.c_int, C.c_void_p,
                                       C.POINTER(C.c_longlong), C.POINTER(C.c_int)]
+        L.rl_coalrate_batch_trees.argtypes = [C.c_int]
+        L.rl_coalrate_epochs.argtypes = [C.c_float, C.c_char_p, C.c_void_p, C.POINTER(C.c_int)]
+        L.rl_coalrate_trees.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int,
+                                        C.c_int, C.c_void_p]
+        L.rl_coalrate_anc.argtypes = [C.c_char_p, C.c_char_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p,
+                                      C.POINTER(C.c_int)]
+        L.rl_coalrate_write_bin.argtypes = [C.c_char_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int]
+        L.rl_coalrate_read_bin.argtypes = [C.c_char_p, C.c_void_p, C.POINTER(C.c_int), C.c_void_p, C.POINTER(C.c_int)]
+        L.rl_coalrate_finalize.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p]
+        L.rl_coalrate_finalize_files.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p]
         L.rl_window_copying.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
         L.rl_window_copying_host.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
         L.rl_copying_matrix.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.POINTER(C.c_longlong)]
@@ -794,6 +804,86 @@ def pairwise_anc(paths, metric="size", device=None):
     S = np.zeros((N.value, N.value), dtype)
     _check(lib().rl_pairwise_anc(arr, len(paths), m, dev, _p(S), C.byref(W), C.byref(N)))
     return S, W.value
+
+
+def coalrate_batch_trees(N):
+    """trees per batch of the device path of coalrate_trees / coalrate_anc at N leaves"""
+    return lib().rl_coalrate_batch_trees(int(N))
+
+
+def coalrate_epochs(years_per_gen=28.0, bins=None):
+    """rl_coalrate_epochs: the reference's default 31 epoch boundaries (generations), or those of
+    `--bins lower,upper,step` -> float32 [E]"""
+    ep = np.zeros(4096, np.float32)
+    n = C.c_int(len(ep))
+    _check(lib().rl_coalrate_epochs(float(years_per_gen), None if bins is None else str(bins).encode(), _p(ep),
+                                    C.byref(n)))
+    return ep[:n.value].copy()
+
+
+def coalrate_trees(parents, branch_length, factors, epochs, device=None):
+    """rl_coalrate_trees: the epoch-binned counts (D[e][i][j], i < j) and opportunities (D[e][j][i]) of
+    CoalescentRateForSection.  parents, branch_length: [trees][2N-1] (or one tree); factors: [trees] floats; epochs:
+    [E] floats, epochs[0] = 0, rising; device: None = the host implementation, an int = that GPU.
+    -> D [E][N][N] float32"""
+    pa = np.ascontiguousarray(np.atleast_2d(parents), dtype=np.int32)
+    bl = np.ascontiguousarray(np.atleast_2d(branch_length), dtype=np.float64)
+    f = np.ascontiguousarray(np.atleast_1d(factors), dtype=np.float32)
+    ep = np.ascontiguousarray(epochs, dtype=np.float32)
+    if pa.shape[1] % 2 == 0 or bl.shape != pa.shape or len(f) != len(pa) or ep.ndim != 1:
+        raise RelateError("coalrate_trees: parents %s, branch lengths %s, %d factors" % (pa.shape, bl.shape, len(f)))
+    N = (pa.shape[1] + 1) // 2
+    D = np.empty((len(ep), N, N), np.float32)
+    _check(lib().rl_coalrate_trees(_p(pa), _p(bl), _p(f), N, len(pa), _p(ep), len(ep),
+                                   -1 if device is None else int(device), _p(D)))
+    return D
+
+
+def coalrate_anc(anc_path, mut_path, epochs, device=None):
+    """rl_coalrate_anc: the same over the trees of a text .anc with the factors of its .mut, the reference's loop
+    (its trailing pass included) -> D [E][N][N] float32"""
+    ep = np.ascontiguousarray(epochs, dtype=np.float32)
+    dev = -1 if device is None else int(device)
+    a, m = os.fsencode(anc_path), os.fsencode(mut_path)
+    N = C.c_int(0)
+    _check(lib().rl_coalrate_anc(a, m, _p(ep), len(ep), dev, None, C.byref(N)))
+    D = np.empty((len(ep), N.value, N.value), np.float32)
+    _check(lib().rl_coalrate_anc(a, m, _p(ep), len(ep), dev, _p(D), C.byref(N)))
+    return D
+
+
+def coalrate_write_bin(path, epochs, D):
+    ep = np.ascontiguousarray(epochs, dtype=np.float32)
+    D = np.ascontiguousarray(D, dtype=np.float32)
+    if D.ndim != 3 or D.shape[0] != len(ep) or D.shape[1] != D.shape[2]:
+        raise RelateError("coalrate_write_bin: %d epochs, planes %s" % (len(ep), D.shape))
+    _check(lib().rl_coalrate_write_bin(os.fsencode(path), _p(ep), len(ep), _p(D), D.shape[1]))
+
+
+def coalrate_read_bin(path):
+    """-> (epochs [E] float32, D [E][N][N] float32)"""
+    E, N = C.c_int(0), C.c_int(0)
+    _check(lib().rl_coalrate_read_bin(os.fsencode(path), None, C.byref(E), None, C.byref(N)))
+    ep, D = np.empty(E.value, np.float32), np.empty((E.value, N.value, N.value), np.float32)
+    _check(lib().rl_coalrate_read_bin(os.fsencode(path), _p(ep), C.byref(E), _p(D), C.byref(N)))
+    return ep, D
+
+
+def coalrate_finalize(D, group_of_haplotype=None, ngroups=1):
+    """rl_coalrate_finalize -> rates [ngroups][ngroups][E] float64 (count over opportunity per group pair and epoch)"""
+    D = np.ascontiguousarray(D, dtype=np.float32)
+    g = None if group_of_haplotype is None else np.ascontiguousarray(group_of_haplotype, dtype=np.int32)
+    if g is not None and len(g) != D.shape[1]:
+        raise RelateError("coalrate_finalize: %d groups of haplotypes for %d haplotypes" % (len(g), D.shape[1]))
+    rates = np.empty((ngroups, ngroups, D.shape[0]), np.float64)
+    _check(lib().rl_coalrate_finalize(_p(D), D.shape[1], D.shape[0], _p(g), int(ngroups), _p(rates)))
+    return rates
+
+
+def coalrate_finalize_files(bin_path, coal_path, poplabels=None):
+    """rl_coalrate_finalize_files: out.bin -> out.coal, as FinalizePopulationSize writes it"""
+    _check(lib().rl_coalrate_finalize_files(os.fsencode(bin_path), None if poplabels is None else os.fsencode(poplabels),
+                                            os.fsencode(coal_path)))
 
 
 def stage_find_equivalent_branches(out_dir, chunk_index=0):

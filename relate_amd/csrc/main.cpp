@@ -17,6 +17,12 @@
 //           their most recent common ancestor, SNP-weighted over the files' trees; out.pwc: int32 N, int32 metric
 //           (0 size, 1 time), int64 W (SNPs), then the N x N sums (uint64 / double) row-major; the summary on stdout
 //           as `key value` lines; --device -1: on the host)
+//   Relate --mode CoalescentRateForSection -i prefix -o out [--bins lower,upper,step] [--years_per_gen g] [--device d]
+//          (RelateCoalescentRate --mode CoalescentRateForSection of the reference: reads prefix.anc (text) and
+//           prefix.mut, writes out.bin, the reference's bytes; --device -1: on the host; --mask, --dist, .gz inputs
+//           and sample ages are refused)
+//   Relate --mode FinalizePopulationSize -o out [--poplabels f]
+//          (RelateCoalescentRate --mode FinalizePopulationSize: out.bin -> out.coal; --poplabels hap is refused)
 // Same options, files and stderr banners as include/pipeline/Relate.cpp:19-115,
 // Paint.cpp, BuildTopology.cpp of the reference; every other --mode is refused
 // (use the reference binary for them).  Extra options: --device n,
@@ -50,7 +56,7 @@ static void usage_line() {
   std::cerr << "---------------------------------------------------------" << std::endl << std::endl;
 }
 
-static const char *kModes = "MakeChunks|Paint|BuildTopology|PaintBuildTopology|FindEquivalentBranches|OptimizeParameters|CompareTopology|PairwiseCoalescence|CopyingMatrix";
+static const char *kModes = "MakeChunks|Paint|BuildTopology|PaintBuildTopology|FindEquivalentBranches|OptimizeParameters|CompareTopology|PairwiseCoalescence|CopyingMatrix|CoalescentRateForSection|FinalizePopulationSize";
 
 // `Relate --mode OptimizeParameters` (pipeline/OptimizeParameters.cpp:22-206): MakeChunks, then for every chunk the
 // grid of (theta, recombination factor) through rl_stage_optimize_parameters, the temporary files removed as the
@@ -341,6 +347,70 @@ static int copying_matrix(const std::string &out, int chunk, int first_section, 
   return 0;
 }
 
+// `Relate --mode CoalescentRateForSection -i prefix -o out [--bins l,u,s] [--years_per_gen g] [--device d]`
+// (evaluate/coalescent_rate/CoalescentRateForSection.cpp:227-602 without sample ages: rl_coalrate_epochs,
+// rl_coalrate_anc, rl_coalrate_write_bin)
+static int coalescent_rate_for_section(std::map<std::string, std::string> &opt) {
+  if (!opt.count("input") || !opt.count("output")) {
+    std::cout << "Not enough arguments supplied." << std::endl;
+    std::cout << "Needed: input, output. Optional: years_per_gen, bins, device." << std::endl;
+    std::cout << "Reads .anc file and calculates pairwise coalescence rate. Output is bin file." << std::endl;
+    return 0;  // (exit(0), :234-243)
+  }
+  for (const char *o : {"mask", "dist"})
+    if (opt.count(o)) {
+      std::cerr << "Error: --" << o << " is not part of this build's CoalescentRateForSection; run the reference's RelateCoalescentRate for it." << std::endl;
+      return 1;
+    }
+  std::cerr << "---------------------------------------------------------" << std::endl;
+  std::cerr << "Calculating coalescence rate for " << opt["input"] << " ..." << std::endl;
+  float years_per_gen = 28.0f;
+  try {
+    if (opt.count("years_per_gen")) years_per_gen = std::stof(opt["years_per_gen"]);
+  } catch (...) {
+    std::cerr << "Error: --years_per_gen expects a number" << std::endl;
+    return 1;
+  }
+  std::vector<float> epochs(4096);
+  int E = (int)epochs.size(), N = 0;
+  const int device = opt.count("device") ? atoi(opt["device"].c_str()) : 0;
+  const std::string anc = opt["input"] + ".anc", mut = opt["input"] + ".mut", bin = opt["output"] + ".bin";
+  bool ok = rl_coalrate_epochs(years_per_gen, opt.count("bins") ? opt["bins"].c_str() : nullptr, epochs.data(), &E) == 0 &&
+            rl_coalrate_anc(anc.c_str(), mut.c_str(), epochs.data(), E, device, nullptr, &N) == 0;
+  std::vector<float> D;
+  if (ok) {
+    D.resize((size_t)E * N * N);
+    ok = rl_coalrate_anc(anc.c_str(), mut.c_str(), epochs.data(), E, device, D.data(), &N) == 0 &&
+         rl_coalrate_write_bin(bin.c_str(), epochs.data(), E, D.data(), N) == 0;
+  }
+  if (!ok) {
+    std::cerr << "Error: " << rl_last_error() << std::endl;
+    return 1;
+  }
+  usage_line();
+  return 0;
+}
+
+// `Relate --mode FinalizePopulationSize -o out [--poplabels f]` (FinalizePopulationSize.cpp:13-136, :138-291:
+// rl_coalrate_finalize_files)
+static int finalize_population_size(std::map<std::string, std::string> &opt) {
+  if (!opt.count("output")) {
+    std::cout << "Not enough arguments supplied." << std::endl;
+    std::cout << "Needed:output. Optional: poplabels." << std::endl;
+    std::cout << "Estimate population size." << std::endl;
+    return 0;  // (exit(0), RelateCoalescentRate.cpp:109-119)
+  }
+  std::cerr << "---------------------------------------------------------" << std::endl;
+  std::cerr << "Finalizing coalescence rate..." << std::endl;
+  const std::string bin = opt["output"] + ".bin", coal = opt["output"] + ".coal";
+  if (rl_coalrate_finalize_files(bin.c_str(), opt.count("poplabels") ? opt["poplabels"].c_str() : nullptr, coal.c_str()) != 0) {
+    std::cerr << "Error: " << rl_last_error() << std::endl;
+    return 1;
+  }
+  usage_line();
+  return 0;
+}
+
 int main(int argc, char **argv) {
   // BuildTopology keeps several tree-builder launches and window kernels in flight from its section threads: more
   // hardware queues than HIP's default four (read when the runtime starts; an explicit setting wins) -- but not more
@@ -360,6 +430,8 @@ int main(int argc, char **argv) {
       {"paint_all_windows", false},  // (PaintBuildTopology of a section range: Paint keeps every window, not the range's)
       {"input", true},  // (OptimizeParameters: the grid, Relate.cpp:43)
       {"metric", true},  // (PairwiseCoalescence: size | time)
+      // (CoalescentRateForSection / FinalizePopulationSize, RelateCoalescentRate.cpp:14-34; mask is named to be refused)
+      {"bins", true}, {"years_per_gen", true}, {"poplabels", true}, {"mask", true},
       // accepted and ignored by these two modes in the reference as well
       {"haps", true}, {"sample", true}, {"map", true}, {"mutation_rate", true}, {"effectiveN", true},
       {"memory", true}, {"dist", true}, {"annot", true}, {"coal", true}, {"transversion", false}};
@@ -396,9 +468,13 @@ int main(int argc, char **argv) {
     std::cerr << "  CompareTopology: -i,--input a.anc,b.anc [-o out] [--device d]" << std::endl;
     std::cerr << "  PairwiseCoalescence: -i,--input a.anc[,b.anc,...] -o out [--metric size|time] [--device d]" << std::endl;
     std::cerr << "  CopyingMatrix: --chunk_index c -o out [--first_section a --last_section b] [--painting theta,rho] [--sum_mode m] [--device d]" << std::endl;
+    std::cerr << "  CoalescentRateForSection: -i,--input prefix -o out [--bins lower,upper,step] [--years_per_gen g] [--device d]" << std::endl;
+    std::cerr << "  FinalizePopulationSize: -o out [--poplabels f]" << std::endl;
     return opt.count("help") ? 0 : 1;
   }
   const std::string mode = opt["mode"];
+  if (mode == "CoalescentRateForSection") return coalescent_rate_for_section(opt);
+  if (mode == "FinalizePopulationSize") return finalize_population_size(opt);
   if (mode == "CompareTopology") return compare_topology(opt);
   if (mode == "PairwiseCoalescence") return pairwise_coalescence(opt);
   if (mode == "OptimizeParameters" && opt.count("output") && opt["output"].find('/') != std::string::npos) {
@@ -520,8 +596,8 @@ int main(int argc, char **argv) {
                                     atoi(opt["last_section"].c_str()), &so);
     if (rc == 1) return 1;  // first_section >= num_windows (BuildTopology.cpp:45)
   } else {
-    std::cerr << "Mode " << mode << " is not part of this build: it replaces --mode MakeChunks, Paint, BuildTopology, FindEquivalentBranches and "
-              << "OptimizeParameters only; run the reference Relate for the other stages." << std::endl;
+    std::cerr << "Mode " << mode << " is not part of this build: it replaces --mode MakeChunks, Paint, BuildTopology, FindEquivalentBranches, "
+              << "OptimizeParameters, CoalescentRateForSection and FinalizePopulationSize only; run the reference Relate for the other stages." << std::endl;
     return 1;
   }
   if (rc != 0) {

@@ -1,10 +1,11 @@
 // tree_passes.h -- the per-tree passes the tree kernels share (compare_kernels.hip: CompareTopology; pairwise_kernels.hip:
-// PairwiseCoalescence).  A tree comes as a parent array with labels rising from child to parent; its tables live in
-// LDS, internal node v at index v - N (ni = N - 1 of them).
+// PairwiseCoalescence; coalrate_kernels.hip: CoalescentRateForSection).  A tree comes as a parent array with labels
+// rising from child to parent; its tables live in LDS, internal node v at index v - N (ni = N - 1 of them).
 //   build_kids      all threads: kids of every internal node, with the validity checks that must precede any use of a
 //                   label as an index;
 //   wave_pull       one wavefront: the scan every pass below and in the kernels is an instance of;
 //   wave_clade_sizes   one wavefront: leaves below every internal node, label order;
+//   wave_float_times   one wavefront: the float time of every internal node, rounded at every node, label order;
 //   wave_left_ends     one wavefront: left end of every internal node's interval of depth-first ranks, falling order.
 // The wave passes take the internal nodes 64 at a time; a lane PULLS what it depends on -- from LDS for a node of
 // another 64, by lane shuffle for a node of its own 64 once that lane is done.  A round costs a ballot and a shuffle
@@ -132,6 +133,33 @@ __device__ inline void wave_clade_sizes(const unsigned *K, int N, u16 *SZ, int l
     }
     const unsigned sz = wave_pull<2>(act, d1, s1, d2, s2, [](unsigned a, unsigned c) { return a + c; });
     if (act) SZ[i] = (u16)sz;
+  }
+}
+
+// TM[i] = time of internal node i as the reference's coalescence-rate recursion has it: a float, rounded at every
+// node, t(m) = (float)((double)t(c) + bl[c]) with c the first child of m and t(leaf) = 0.  One wavefront calls it;
+// each lane calls visit(i, t) for its node once TM[i] is written.
+template <class F>
+__device__ inline void wave_float_times(const unsigned *K, const double *__restrict__ bl, int N, float *TM, int lane, F visit) {
+  const int ni = N - 1;
+  const auto leaf = [](int) { return 0.0f; };
+  const auto table = [&](int j) { return TM[j]; };
+  for (int b = 0; b < ni; b += 64) {
+    const int i = b + lane;
+    const bool act = i < ni;
+    int dep = -1;
+    float base = 0.0f;
+    double len = 0.0;
+    if (act) {
+      const int c1 = first_child(K, i);
+      len = bl[c1];
+      dep = child_source(c1, N, b, &base, leaf, table);
+    }
+    const float t = wave_pull(act, dep, base, [len](float below) { return (float)((double)below + len); });
+    if (act) {
+      TM[i] = t;
+      visit(i, t);
+    }
   }
 }
 
