@@ -221,6 +221,13 @@ int rl_debug_wave_sum_ex(const double *x, int n, int batch, int rows_per_group, 
  * (8, 16, 32, 48, 64, 80), the exact order keeps the first *ks in LDS and the
  * last *r in registers and recomputes the rest.  RL_EINVAL for another S. */
 int rl_debug_term_split(int S, int *ks, int *r);
+/* Host only: the exact order's hop over a tie lane (relate_amd/csrc/exact_sum.h) for the entry offsets delta_lo ..
+ * delta_hi.  A4: the exit offsets of the lane's four runs, p0 in 0..3, sh in 0..1.  out_reference[delta - delta_lo]:
+ * the literal form A_h + ((delta - B_h) >> sh), h = (p0 + delta) & 3; out_table[...]: the same through the packed
+ * table the kernels walk (walk_table_pack, walk_table_hop).  *packable = 0 where an entry of the table is no int16
+ * (the kernels then redo that lane from its exact entry value); out_table is zeroed.  RL_EINVAL for bad arguments. */
+int rl_debug_walk_table(const int *A4, int p0, int sh, int delta_lo, int delta_hi, int *packable, int *out_table,
+                        int *out_reference);
 
 /* Experiment builds only (kernels compiled with -DRL_STATS and
  * RELATE_AMD_TEST_STATS set): 16 event counters of the last rl_paint. */

@@ -148,6 +148,20 @@ def term_split(S):
     return ks.value, r.value
 
 
+def walk_table(A4, p0, sh, delta_lo, delta_hi):
+    """rl_debug_walk_table: the exact order's hop over a tie lane for delta_lo .. delta_hi -> (packable, through the
+    packed table [int32], the literal form [int32]) (host code, no GPU)"""
+    A4 = np.ascontiguousarray(A4, dtype=np.int32)
+    assert A4.shape == (4,)
+    n = int(delta_hi) - int(delta_lo) + 1
+    tab, ref = np.empty(max(n, 0), np.int32), np.empty(max(n, 0), np.int32)
+    ok = C.c_int()
+    f = lib().rl_debug_walk_table
+    f.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.c_void_p, C.c_void_p]
+    _check(f(_p(A4), int(p0), int(sh), int(delta_lo), int(delta_hi), C.byref(ok), _p(tab), _p(ref)))
+    return bool(ok.value), tab, ref
+
+
 def paint_segment_range(lo, hi, seg, s):
     """rl_paint_segment_range: -> (first, last): segment s of seg walks [first, last) of the step range [lo, hi)
     (host code, no GPU; the kernels run the same function)"""

@@ -218,3 +218,26 @@ extern "C" int rl_debug_term_split(int S, int *ks, int *r) {
   }
   return RL_OK;
 }
+
+// host only: the walk's hop over a tie lane (exact_sum.h), the packed table against the literal form, for every entry
+// offset delta_lo .. delta_hi
+extern "C" int rl_debug_walk_table(const int *A4, int p0, int sh, int delta_lo, int delta_hi, int *packable,
+                                   int *out_table, int *out_reference) {
+  using namespace rl;
+  if (!A4 || !packable || !out_table || !out_reference) {
+    set_error("rl_debug_walk_table: null argument");
+    return RL_EINVAL;
+  }
+  if (p0 < 0 || p0 > 3 || sh < 0 || sh > 1 || delta_hi < delta_lo) {
+    set_error("rl_debug_walk_table: p0=%d outside 0..3, sh=%d outside 0..1 or delta_hi=%d < delta_lo=%d", p0, sh,
+              delta_hi, delta_lo);
+    return RL_EINVAL;
+  }
+  const WalkTable t = walk_table_pack(A4[0], A4[1], A4[2], A4[3], p0, sh);
+  *packable = t.ok ? 1 : 0;
+  for (long long d = delta_lo; d <= delta_hi; d++) {
+    out_reference[d - delta_lo] = walk_hop_reference(A4[0], A4[1], A4[2], A4[3], p0, sh, (int)d);
+    out_table[d - delta_lo] = t.ok ? walk_table_hop(t.lo, t.hi, 16 * p0, sh, (int)d) : 0;
+  }
+  return RL_OK;
+}

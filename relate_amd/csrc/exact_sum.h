@@ -31,9 +31,9 @@
 // such maps compose into maps of the same form, so a segmented wavefront scan
 // composes them all at once.  What remains sequential is a walk over the few
 // lanes (measured ~3.5 per sum at N = 5000) where a tie made the four runs
-// disagree (4-entry table) or where the run jumps two or more binades (a term
-// much larger than the prefix, ~0.9 per sum: that lane redoes its run from its
-// exact entry value).  Anything else irregular (P_l within 16384 ulp of a power
+// disagree (4-entry table, walk_table_hop below) or where the run jumps two or
+// more binades (a term much larger than the prefix, ~0.9 per sum: that lane
+// redoes its run from its exact entry value).  Anything else irregular (P_l within 16384 ulp of a power
 // of two, ...) falls back to the literal serial sum for that step (measured:
 // < 1e-4 of the steps).
 // The result is ALWAYS the serial sum, bit for bit.
@@ -321,6 +321,51 @@ RL_DEV double sum_exact_fallback_linked(const T &term, const WaveLink<WAVES> &lk
   }
 }
 
+// ---- the walk's hop over a tie lane ----------------------------------------
+// A lane whose four runs disagree (a rounding tie) maps its entry offset delta to
+//   A_h + ((delta - B_h) >> sh),   h = (p0 + delta) & 3,
+// A_h the exit offsets of the four runs, B_h the entry offsets of their starts (walk_hop_reference, the literal form).
+// B_h = h - p0 (mod 4) for all four starts (G4 is a multiple of 4) and delta = h - p0 (mod 4) by the choice of h, so
+// delta - B_h is a multiple of 4 and for sh in {0, 1} the shift distributes exactly:
+//   A_h + ((delta - B_h) >> sh)  =  (delta >> sh) + U_h,   U_h = A_h - (B_h >> sh).
+// U_h is the `d` of the affine test (a run's increment less Q - P: small), so the four fit signed 16-bit fields of
+// two registers, built by all lanes at once during classification, which needs them anyway; the walk's dependent
+// path per tie lane is then a shift-and-add, a mask, a 64-bit shift, a sign extension, and one shift of delta and an
+// add -- no select of A_h or B_h by h, and every read from the lane comes before it.
+// One function each for the kernels and the host (rl_debug_walk_table); integers only.
+constexpr int WALK_G4 = 16384;  // half-width of the bracket [r_0, r_3] in ulps
+RL_HD inline int walk_hop_reference(int A0, int A1, int A2, int A3, int p0, int sh, int delta) {
+  const int h = (p0 + delta) & 3;
+  const int A = (h & 2) ? ((h & 1) ? A3 : A2) : ((h & 1) ? A1 : A0);
+  const int B = h == 0 ? (-p0 - WALK_G4) : (h == 3 ? (3 - p0 + WALK_G4) : (h - p0));
+  return A + ((delta - B) >> sh);
+}
+// U_h = A_h - (B_h >> sh): run h's exit offset less its shifted entry offset
+RL_HD inline int walk_run_offset(int A, int h, int p0, int sh) {
+  const int B = h - p0 + (h == 0 ? -WALK_G4 : h == 3 ? WALK_G4 : 0);
+  return A - (B >> sh);
+}
+struct WalkTable {
+  int lo, hi;  // U_0 | U_1 << 16,  U_2 | U_3 << 16
+  bool ok;     // every U_h is an int16
+};
+RL_HD inline WalkTable walk_table_pack_runs(int U0, int U1, int U2, int U3) {
+  WalkTable t;
+  t.ok = (short)U0 == U0 && (short)U1 == U1 && (short)U2 == U2 && (short)U3 == U3;
+  t.lo = (int)(((unsigned)U0 & 0xffffu) | ((unsigned)U1 << 16));
+  t.hi = (int)(((unsigned)U2 & 0xffffu) | ((unsigned)U3 << 16));
+  return t;
+}
+RL_HD inline WalkTable walk_table_pack(int A0, int A1, int A2, int A3, int p0, int sh) {
+  return walk_table_pack_runs(walk_run_offset(A0, 0, p0, sh), walk_run_offset(A1, 1, p0, sh),
+                              walk_run_offset(A2, 2, p0, sh), walk_run_offset(A3, 3, p0, sh));
+}
+// p16 = 16 * p0: the bit offset of the field of the run that starts at the lane's own residue
+RL_HD inline int walk_table_hop(int lo, int hi, int p16, int sh, int delta) {
+  const unsigned long long t = ((unsigned long long)(unsigned)hi << 32) | (unsigned)lo;
+  return (delta >> sh) + (int)(short)(unsigned short)(t >> (((delta << 4) + p16) & 48));
+}
+
 #ifdef RL_STATS
 #define RL_CLK() __builtin_readcyclecounter()
 #define RL_STAT(i, v) do { if (term.stats && (threadIdx.x & 63) == 0) atomicAdd(&term.stats[i], (unsigned long long)(v)); } while (0)
@@ -334,7 +379,7 @@ RL_DEV double sum_exact_fallback_linked(const T &term, const WaveLink<WAVES> &lk
 template <int S, int WAVES, typename T>
 RL_DEV double sum_exact_fast(const T &term, double L, WaveLink<WAVES> &lk) {
   constexpr bool REG_TERM = T::REG;
-  constexpr int G4 = 16384;  // half-width of the bracket [r_0, r_3] in ulps
+  constexpr int G4 = WALK_G4;  // half-width of the bracket [r_0, r_3] in ulps
 
   const unsigned long long tk0 = RL_CLK();
   // ---- A. approximate prefix from the lanes' local serial sums
@@ -426,40 +471,43 @@ RL_DEV double sum_exact_fast(const T &term, double L, WaveLink<WAVES> &lk) {
 
   // offsets are in units of the exit ulp.  Exit offsets of the four runs
   // (|A_h| < 2^15) and entry offsets B_h = (r_h - P)/ulp_in of their starts:
-  int A0 = 0, A1 = 0, A2 = 0, A3 = 0;
+  int A0 = 0;
   if (constant) A0 = exit_offset(c0);
   // exact entry: the exit is c0 itself; offset 0 wherever the approximate prefix Q is that same sum (lane 0,
   // all-zero prefixes), a few ulp for lane 1
   if (zero_entry && __double_as_longlong(c0) != __double_as_longlong(Q)) A0 = exit_offset(c0);
-  if (!invalid && !jump && !zero_entry) {
-    A0 = exit_offset(c0);
-    A1 = exit_offset(c1);
-    A2 = exit_offset(c2);
-    A3 = exit_offset(c3);
-  }
-  const int B0 = -p0 - G4, B1 = 1 - p0, B2 = 2 - p0, B3 = 3 - p0 + G4;
-  // Is the lane's map delta -> A_h + ((delta - B_h) >> sh), h = (p0 + delta) & 3,
-  // of the tie-free form ((delta + K) >> sh) + C ?   (K in {0,1} when sh = 1)
+  // Is the lane's map delta -> A_h + ((delta - B_h) >> sh), h = (p0 + delta) & 3, B_h = (r_h - P)/ulp_in the entry
+  // offsets of the four starts, of the tie-free form ((delta + K) >> sh) + C ?   (K in {0,1} when sh = 1)
+  // With U_h = A_h - (B_h >> sh) (walk_run_offset):  K = 0 iff the four U_h agree, C = U_0;  K = 1 (sh = 1 only) iff the
+  // four A_h - ((B_h + 1) >> 1) = U_h - (B_h & 1) agree, and B_h & 1 = (h + p0) & 1:  U_0 = U_2, U_1 = U_3 and
+  // U_0 - U_1 = 2 (p0 & 1) - 1,  C = U_0 - (p0 & 1).
   int mK = 0, mC = zero_entry ? A0 : 0;  // exact entry: delta is 0 on entry (nothing but exact lanes before), A0 on exit
   bool affine = zero_entry;
-  if (!invalid && !jump && !zero_entry) {
-    if (sh == 0) {
-      const int d = A0 - B0;
-      affine = (A1 - B1 == d) && (A2 - B2 == d) && (A3 - B3 == d);
-      mC = d;
-    } else {
-      const int d0 = A0 - (B0 >> 1), d1 = A0 - ((B0 + 1) >> 1);
-      const bool k0 = (A1 - (B1 >> 1) == d0) && (A2 - (B2 >> 1) == d0) && (A3 - (B3 >> 1) == d0);
-      const bool k1 = (A1 - ((B1 + 1) >> 1) == d1) && (A2 - ((B2 + 1) >> 1) == d1) && (A3 - ((B3 + 1) >> 1) == d1);
-      affine = k0 || k1;
-      mK = k0 ? 0 : 1;
-      mC = k0 ? d0 : d1;
-    }
+  const bool table = !invalid && !jump && !zero_entry;  // sh is 0 or 1
+  int U0 = A0, U1 = 0, U2 = 0, U3 = 0;  // (a `constant` lane: its A0 in the table's low field, where the walk starts)
+  if (table) {
+    U0 = walk_run_offset(exit_offset(c0), 0, p0, sh);
+    U1 = walk_run_offset(exit_offset(c1), 1, p0, sh);
+    U2 = walk_run_offset(exit_offset(c2), 2, p0, sh);
+    U3 = walk_run_offset(exit_offset(c3), 3, p0, sh);
+    const int e = p0 & 1;
+    const bool k0 = U0 == U1 && U1 == U2 && U2 == U3;
+    const bool k1 = sh != 0 && U0 == U2 && U1 == U3 && U0 - U1 == 2 * e - 1;
+    affine = k0 || k1;
+    mK = k0 ? 0 : 1;
+    mC = k0 ? U0 : U0 - e;
   }
   const int mS = (affine && !zero_entry) ? sh : 0;
   if (!affine) { mK = 0; mC = 0; }
-  const int w01 = (A0 & 0xffff) | (A1 << 16), w23 = (A2 & 0xffff) | (A3 << 16);
-  const int meta = p0 | (sh << 2) | (special ? 16 : 0);
+  // the hop table of a tie lane (walk_table_pack); the fields of every other lane are never read, but for the low
+  // field of a `constant` lane
+  const WalkTable wt = walk_table_pack_runs(U0, U1, U2, U3);
+  // A U_h beyond int16 (never seen: |U_h| is bounded by the error of Q - P, (1) above): the lane has no table and is
+  // redone from its exact entry value like a multi-binade run, which is right for every lane that is not invalid.
+  // (the flag is read for walked lanes only: !wt.ok needs no `table && !affine` beside it)
+  const bool redo = special || !wt.ok;
+  const int t01 = wt.lo, t23 = wt.hi;
+  const int meta = (p0 << 4) | (sh << 2) | (redo ? 1 : 0);  // (sh: read for tie lanes only, where it is 0 or 1)
 
   // the caller's unit: the total is returned as Q_63 + delta * ulp(Q_63); Q_63
   // must not be within the bracket width of a power of two
@@ -471,7 +519,8 @@ RL_DEV double sum_exact_fast(const T &term, double L, WaveLink<WAVES> &lk) {
   }
   // ---- C. compose the tie-free lanes with a segmented scan (segments end at
   // the lanes that need the walk), then walk those lanes
-  int sK = mK, sC = mC, sS = mS | (affine ? 0 : 64);  // bit 6: segment head
+  // bit 6: segment head; a head carries its meta in the bits above, which no step of the scan reads
+  int sK = mK, sC = mC, sS = affine ? mS : (64 | (meta << 8));
   auto combine = [&](int pK, int pC, int pS) {
     // (pK,pC,pS) = composite of the lanes further left; no-op if a head lies in between
     if (!(sS & 64)) {
@@ -511,7 +560,7 @@ RL_DEV double sum_exact_fast(const T &term, double L, WaveLink<WAVES> &lk) {
   unsigned long long todo = __ballot(!affine);
   RL_STAT(2, __builtin_popcountll(todo));
   {
-    const unsigned long long sp = __ballot(special);
+    const unsigned long long sp = __ballot(special || (table && !affine && !wt.ok));
     (void)sp;
     RL_STAT(3, __builtin_popcountll(sp));
   }
@@ -528,7 +577,7 @@ RL_DEV double sum_exact_fast(const T &term, double L, WaveLink<WAVES> &lk) {
     const unsigned long long cm = __ballot(constant);
     if (cm) {
       const int qc = 63 - __builtin_clzll(cm);
-      delta = (int)(short)__builtin_amdgcn_readlane(w01, qc);  // its A0
+      delta = (int)(short)__builtin_amdgcn_readlane(t01, qc);  // its A0
       todo &= ~((2ull << qc) - 1ull);
     }
   }
@@ -540,13 +589,16 @@ RL_DEV double sum_exact_fast(const T &term, double L, WaveLink<WAVES> &lk) {
     // wave lies before it, and delta is already its entry offset -- lane q-1 = -1 would read lane 63 (the lane select
     // keeps 6 bits), the composite of this wave's trailing lanes.  Lane 0 of wave 0 enters at exactly +0.0 and is
     // never walked.
+    // Everything read from the lanes is independent of delta and comes first: the lane's hop table and meta, the
+    // composite in front of it; delta's own path is then the composite map and the hop (walk_table_hop).
+    const int tlo = __builtin_amdgcn_readlane(t01, q), thi = __builtin_amdgcn_readlane(t23, q);
+    const int m = __builtin_amdgcn_readlane(sS, q) >> 8;
     if (WAVES == 1 || q > 0) {
       const int K = __builtin_amdgcn_readlane(sK, q - 1), C = __builtin_amdgcn_readlane(sC, q - 1);
       const int sft = __builtin_amdgcn_readlane(sS, q - 1) & 63;
       delta = ((delta + K) >> sft) + C;
     }
-    const int m = __builtin_amdgcn_readlane(meta, q);
-    if (m & 16) {
+    if (m & 1) {
       // multi-binade run: redo it from the exact entry value
       const double Pq = rd_lane_f64(P, q);
       const double uq = pow2_field(expo_field(Pq) - 52);
@@ -560,12 +612,7 @@ RL_DEV double sum_exact_fast(const T &term, double L, WaveLink<WAVES> &lk) {
       // (the true exit lies between the bracketing runs, which end in Q's binade -- else the lane were invalid)
       delta = (int)((unsigned)__double_as_longlong(v) - (unsigned)__builtin_amdgcn_readlane((int)q_lo, q));
     } else {
-      const int qp0 = m & 3, qsh = (m >> 2) & 3;
-      const int h = (qp0 + delta) & 3;
-      const int w = __builtin_amdgcn_readlane((h & 2) ? w23 : w01, q);
-      const int A = (int)(short)((h & 1) ? (w >> 16) : w);
-      const int B = h == 0 ? (-qp0 - G4) : (h == 3 ? (3 - qp0 + G4) : (h - qp0));
-      delta = A + ((delta - B) >> qsh);
+      delta = walk_table_hop(tlo, thi, m & 48, (m >> 2) & 1, delta);  // a tie lane: sh is 0 or 1
     }
   }
   {  // trailing tie-free lanes (lane 63 holds their composite; identity if it was walked)
