@@ -334,7 +334,7 @@ int rl_quickbuild(int N, double theta, float *d, const float *d_prior,
  * (min_values_CF, the stale candidate indices -- they steer the random
  * draws).  device >= 0: trees are built on that GPU, one workgroup per tree
  * with the matrices in HBM (src/tree_builder.cpp restated in
- * relate_amd/csrc/minmatch_gpu.hip); a tree that needs the symmetric
+ * relate_amd/csrc/minmatch_build.h); a tree that needs the symmetric
  * fallback (tree_builder.cpp:255-293, :968-1058) is built by the host code
  * with the same state.  device < 0: the host builder.  d is destroyed.
  * rl_builder_last_on_gpu: 1 if the last tree was built on the GPU. */

@@ -83,7 +83,7 @@ inline hipError_t make_stream(hipStream_t *s, bool tree_builder, bool section = 
 
 // Device and pinned-host memory of the library go through a cache: a released block is kept and handed to the next
 // request of (about) its size instead of going back to the driver.  hipFree / hipHostFree wait until the device
-// is idle -- with the tree builder's resident workers (minmatch_gpu.hip) that is "until no section has a tree in
+// is idle -- with the tree builder's resident workers (minmatch_worker.hip) that is "until no section has a tree in
 // flight", i.e. a window closing in the middle of a stage would stall its thread until all the others stall too.
 // Windows of a stage ask for the same sizes over and over, so the cache also saves ~25 driver calls per window.
 // device_cache_trim() gives everything back (end of a stage; when an allocation fails).
@@ -92,7 +92,7 @@ void device_cache_release(void *p, size_t bytes);
 void *pinned_cache_alloc(size_t bytes, size_t *got);
 void pinned_cache_release(void *p, size_t bytes);
 void device_cache_trim();
-// launches of tree-builder workers that are alive (minmatch_gpu.hip): while any is, a failed allocation does not
+// launches of tree-builder workers that are alive (minmatch_worker.hip): while any is, a failed allocation does not
 // trim the cache (hipFree would wait for the workers) -- it takes a larger cached block, or waits for them to leave
 extern std::atomic<int> g_worker_launches;
 // bytes of `device`'s memory the cache holds for re-use in blocks of at least min_block bytes (cache_alloc hands out

@@ -64,6 +64,41 @@ struct HostTree {
   }
 };
 
+// The nodes of a tree from its N - 1 merges in order (cluster i into cluster j; tree_builder.cpp:2437-2460, 2631-2636):
+// cluster j lives on as the new node.  -1, or the first merge that names a cluster outside [0, N) (the tree is
+// incomplete then).
+inline int tree_from_merges(HostTree &tree, int N, const int *merge_i, const int *merge_j) {
+  tree.reset(N);
+  std::vector<int> node(N);
+  for (int c = 0; c < N; c++) node[c] = c;
+  for (int mth = 0; mth < N - 1; mth++) {
+    const int ci = merge_i[mth], cj = merge_j[mth], nn = N + mth;
+    if (ci < 0 || ci >= N || cj < 0 || cj >= N) return mth;
+    tree.parent[node[ci]] = nn;
+    tree.parent[node[cj]] = nn;
+    tree.child_left[nn] = node[ci];
+    tree.child_right[nn] = node[cj];
+    node[cj] = nn;
+  }
+  return -1;
+}
+// The tables of a tree's clade prior (anc_builder.cpp:583-606) in the caller's storage -- the host's vectors
+// (clade_prior, treeseq.cpp), the device builder's pinned block (apply_prior, minmatch_builder.hip).  Per node, 2N-1
+// entries each: depth -- the internal nodes on the path node..root, the node included if internal --, size -- the
+// leaves below it -- and lo -- where they begin in a depth-first leaf order (labels increase towards the root: 2N-2
+// is the root); order [N]: that leaf order.
+inline void clade_tables(const HostTree &t, int N, int *depth, int *size, int *lo, int *order) {
+  const int T = 2 * N - 1;
+  for (int v = 0; v < T; v++) depth[v] = 0, lo[v] = 0, size[v] = 1;
+  for (int v = T - 1; v >= N; v--) depth[v] = (t.parent[v] >= 0 ? depth[t.parent[v]] : 0) + 1;
+  for (int v = N; v < T; v++) size[v] = size[t.child_left[v]] + size[t.child_right[v]];
+  for (int v = T - 1; v >= N; v--) {
+    lo[t.child_left[v]] = lo[v];
+    lo[t.child_right[v]] = lo[v] + size[t.child_left[v]];
+  }
+  for (int i = 0; i < N; i++) order[lo[i]] = i;
+}
+
 template <typename T>
 T *HugePageAllocator<T>::allocate(size_t n) {
   const size_t bytes = n * sizeof(T), huge = (size_t)2 << 20;
@@ -208,7 +243,7 @@ class MinMatchAges {
   const float *CF = nullptr;
 };
 
-// The same builder on the GPU (minmatch_gpu.hip): one workgroup per tree, matrices in HBM.  build() takes the
+// The same builder on the GPU (minmatch_builder.hip; the build kernel and its workers: minmatch_worker.hip): one workgroup per tree, matrices in HBM.  build() takes the
 // state a MinMatch carries from tree to tree from `tb` and puts it back, so the two can alternate: it returns
 // 0 when the tree is built, > 0 when this tree needs the host (symmetric fallback; tb untouched), < 0 on error.
 class DeviceMinMatch {

@@ -56,7 +56,7 @@ struct rl_treeseq {
   int start = 0, end = 0;
   std::vector<char> member;  // carriers of the current SNP
   int num_carriers = 0;
-  int build_device = -1;  // >= 0: trees are built on that GPU (minmatch_gpu.hip), the host builder as fallback
+  int build_device = -1;  // >= 0: trees are built on that GPU (minmatch_builder.hip), the host builder as fallback
   rl_matrix_dev_fn matrix_dev = nullptr;  // with it the distance matrices never leave the device
   rl_matrix_dev_ex_fn matrix_dev_ex = nullptr;  // ... and arrive with the carrier penalty applied and their row minima
   long long gpu_trees = 0, host_trees = 0;
@@ -70,7 +70,7 @@ struct rl_treeseq {
 
 namespace rl {
 
-double device_builder_shared_bytes(int N);  // (minmatch_gpu.hip) HBM of the pools the device builders share
+double device_builder_shared_bytes(int N);  // (minmatch_builder.hip) HBM of the pools the device builders share
 
 // ---- Where a SNP sits on a tree (anc_builder.cpp:1064-1413: MapMutation, ForceMapMutation and their two
 // recursions PropagateMutationGlobal / PropagateMutationLocal).
@@ -266,18 +266,11 @@ static void parallel_rows(int N, F f) {
 static void clade_prior(const HostTree &t, float val, MatrixBuf &dist) {
   const int N = t.N, T = 2 * N - 1;
   dist.resize((size_t)N * N);
-  std::vector<int> depth(T, 0);  // internal nodes on the path node..root, inclusive of node if internal
-  for (int v = T - 1; v >= N; v--) depth[v] = (t.parent[v] >= 0 ? depth[t.parent[v]] : 0) + 1;
   std::vector<float> acc((size_t)N + 1, 0.0f);
   for (int c = 1; c <= N; c++) acc[c] = acc[c - 1] + val;
-  // depth-first leaf order; [lo, hi) of every node (labels increase towards the root: T-1 is the root)
-  std::vector<int> size(T, 1), lo(T, 0), order(N);
-  for (int v = N; v < T; v++) size[v] = size[t.child_left[v]] + size[t.child_right[v]];
-  for (int v = T - 1; v >= N; v--) {
-    lo[t.child_left[v]] = lo[v];
-    lo[t.child_right[v]] = lo[v] + size[t.child_left[v]];
-  }
-  for (int i = 0; i < N; i++) order[lo[i]] = i;
+  // depth of every node, and a depth-first leaf order with [lo, lo + size) of every node (minmatch.h)
+  std::vector<int> depth(T), size(T), lo(T), order(N);
+  clade_tables(t, N, depth.data(), size.data(), lo.data(), order.data());
   parallel_rows(N, [&](int a) {
     float *row = &dist[(size_t)a * N];
     row[a] = 0.0f;
@@ -356,7 +349,7 @@ rl_treeseq *treeseq_borrowing(int N, int L, const uint32_t *bits, int row_words,
 //     sections fall into a convoy: 143 s and 185 s from the same 124 workers), so the rule stays a whole XCD round
 //     (8 workers) below that edge.  profiles/r06_worker_rule.json: the rule against 0.75x / 1.25x / 1.5x of it at
 //     N = 2000, 5000 and 10,000;
-//   * `per_cu` worker slots per CU (two for the small-N kernel, minmatch_gpu.hip worker_kind): the CU share above is a
+//   * `per_cu` worker slots per CU (two for the small-N kernel, minmatch_worker.hip worker_kind): the CU share above is a
 //     share of CUs, the slots on them follow.
 // (A tree's time in the stage does not depend on the worker count -- 142-150 ms from 116 to 148 workers,
 //  profiles/r05_c3_runs.json --; past the share above it is RePaint, on the CUs left, that every section waits for.)
@@ -403,7 +396,7 @@ int rl_treeseq_build(rl_treeseq *ts, int start, int end, rl_matrix_fn matrix, rl
   };
   MinMatch tb(N, ts->theta);
   // with sample ages (ancient samples) the candidates carry a third key and a clock: its own builder (and its own
-  // workers on the device, minmatch_gpu.hip AGES)
+  // workers on the device, minmatch_worker.hip AGES)
   std::unique_ptr<MinMatchAges> tb_ages;
   if ((int)ts->sample_ages.size() == N) tb_ages.reset(new MinMatchAges(N, ts->theta));
   DeviceMinMatch *dev = nullptr;
@@ -966,13 +959,13 @@ static int build_sections(rl_ctx *ctx, const char *out_dir, int chunk_index, int
     }
     max_rows = std::max(max_rows, rows_of[w]);
   }
-  // The trees themselves are built on the GPU too (minmatch_gpu.hip) when the call covers several sections: a tree
+  // The trees themselves are built on the GPU too (minmatch_builder.hip) when the call covers several sections: a tree
   // takes one workgroup ~115 ms at N = 5000 against ~85 ms on 8 host threads, but the workgroups of different
   // sections run side by side (40 sections: 98 s against 331 s).  RELATE_AMD_GPU_BUILD=0 / 1 decides otherwise.
   const bool gpu_build = knob("RELATE_AMD_GPU_BUILD", o.gpu_build, o.gpu_build >= 0, last_section > first_section) != 0;
   // Next to its rows a window holds cursors and small per-target arrays, a stage from paint files also the decoded
   // stones (2 N^2 floats; the fused stage re-paints from the context's own); a tree builder on the device keeps the
-  // woven float4 matrix of the build (16 N^2 B, minmatch_gpu.hip) -- the row-major matrices of a tree and the
+  // woven float4 matrix of the build (16 N^2 B, minmatch_builder.hip) -- the row-major matrices of a tree and the
   // symmetric matrix of the fallback come from pools of the device, counted once.  RePaint's strips are one buffer
   // of the context (reserved below).
   const double NN = (double)ctx->N * (ctx->N + 64.0);
@@ -1060,7 +1053,7 @@ static int build_sections(rl_ctx *ctx, const char *out_dir, int chunk_index, int
     int cus = 256;
     if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess || cus < 8) cus = 256;
     int workers = stage_worker_goal(cus, nthreads, cap_rows > 0, device_builder_workers_per_cu(ctx->N, !sample_ages.empty()));
-    if (o.workers > 0) workers = o.workers;  // (RELATE_AMD_BUILD_WORKERS overrides either, minmatch_gpu.hip)
+    if (o.workers > 0) workers = o.workers;  // (RELATE_AMD_BUILD_WORKERS overrides either, minmatch_worker.hip)
     (void)device_builder_expect(device, ctx->N, workers, !sample_ages.empty());
     asked_workers = workers;
   }
@@ -1297,6 +1290,63 @@ static int build_sections(rl_ctx *ctx, const char *out_dir, int chunk_index, int
 
 int rl_debug_stage_worker_goal(int cus, int open_sections, int bounded_windows, int workers_per_cu) {
   return rl::stage_worker_goal(cus, open_sections, bounded_windows != 0, workers_per_cu);
+}
+
+// (measurement hook, tools/bench_builder_many.py) `builders` device builders, a host thread each, build the SAME tree
+// `reps` times side by side -- the matrices stay on the device: a copy per build into the builder's staging pair, as
+// K3 and the prior kernel would leave them -- with `workers` resident workgroups at most (0: the queue's own limit).
+// seconds: wall-clock from the first submit to the last tree; mismatches: builds whose parent array differs from
+// builder 0's of the same repetition (0 expected: every builder carries the same state through the same trees).
+int rl_debug_builder_throughput(int N, double theta, int device, int builders, int reps, int workers, const float *d,
+                                const float *prior, double *seconds, int *mismatches, int *first_parents) {
+  if (N < 2 || builders < 1 || reps < 1 || !d || !seconds || !mismatches) return RL_EINVAL;
+  RL_HIP(hipSetDevice(device));
+  const size_t NN = (size_t)N * N;
+  DevBuf masterD, masterCF;
+  if (masterD.alloc(NN * 4) || (prior && masterCF.alloc(NN * 4))) return RL_ENOMEM;
+  RL_HIP(hipMemcpy(masterD.p, d, NN * 4, hipMemcpyHostToDevice));
+  if (prior) RL_HIP(hipMemcpy(masterCF.p, prior, NN * 4, hipMemcpyHostToDevice));
+  std::vector<std::unique_ptr<MinMatch>> tbs;
+  std::vector<std::unique_ptr<DeviceMinMatch>> devs;
+  for (int b = 0; b < builders; b++) {
+    tbs.emplace_back(new MinMatch(N, theta));
+    devs.emplace_back(new DeviceMinMatch(N, device));
+    if (devs.back()->reserve(false)) return RL_ENOMEM;
+  }
+  if (device_builder_expect(device, N, workers, false)) return RL_EHIP;
+  std::vector<std::vector<int>> parents((size_t)builders * reps);
+  std::atomic<int> ready(0), failed(0);
+  std::atomic<bool> go(false);
+  std::vector<std::thread> th;
+  for (int b = 0; b < builders; b++)
+    th.emplace_back([&, b] {
+      (void)hipSetDevice(device);
+      ready.fetch_add(1);
+      while (!go.load()) std::this_thread::sleep_for(std::chrono::microseconds(50));
+      for (int r = 0; r < reps && !failed.load(); r++) {
+        HostTree t;
+        if (devs[b]->stage_from_device(masterD.as<float>(), prior ? masterCF.as<float>() : nullptr) ||
+            devs[b]->build_resident(*tbs[b], prior != nullptr, t) != 0) {
+          failed.store(1);
+          break;
+        }
+        parents[(size_t)b * reps + r].assign(t.parent.begin(), t.parent.begin() + (2 * N - 1));
+      }
+    });
+  while (ready.load() < builders) std::this_thread::sleep_for(std::chrono::microseconds(100));
+  const auto t0 = std::chrono::steady_clock::now();
+  go.store(true);
+  for (auto &x : th) x.join();
+  *seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+  (void)device_builder_expect(device, N, 0, false);
+  if (failed.load()) return RL_EHIP;
+  int bad = 0;
+  for (int b = 1; b < builders; b++)
+    for (int r = 0; r < reps; r++) bad += parents[(size_t)b * reps + r] != parents[r];
+  *mismatches = bad;
+  if (first_parents)
+    for (int r = 0; r < reps; r++) memcpy(first_parents + (size_t)r * (2 * N - 1), parents[r].data(), ((size_t)2 * N - 1) * 4);
+  return RL_OK;
 }
 
 void rl_stage_opts_init(rl_stage_opts *o) {

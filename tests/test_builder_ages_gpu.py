@@ -1,4 +1,4 @@
-"""MinMatch::QuickBuild with sample ages (`--sample_ages`) on the GPU (minmatch_gpu.hip, the AGES build) against the
+"""MinMatch::QuickBuild with sample ages (`--sample_ages`) on the GPU (minmatch_build.h, the AGES build) against the
 host builder with sample ages -- the one checked against the reference's MinMatch (tests/test_oracle_ref.py::
 test_builder_with_sample_ages_matches_reference_minmatch) and its files (tests/golden/synth24_ages.npz): the same
 parent and child arrays tree after tree from ONE builder, with the state it carries between builds."""

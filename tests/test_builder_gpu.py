@@ -1,4 +1,4 @@
-"""The tree builder on the GPU (relate_amd/csrc/minmatch_gpu.hip) against the host builder -- which is the one
+"""The tree builder on the GPU (relate_amd/csrc/minmatch_builder.hip, its workers minmatch_worker.hip) against the host builder -- which is the one
 checked against the reference binary (tests/test_oracle_ref.py) and the golden tree sequences: the same parent
 and child arrays, tree after tree, with the state MinMatch carries between builds."""
 import numpy as np

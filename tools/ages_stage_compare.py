@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """tools/ages_stage_compare.py [N] [L]: Paint + BuildTopology of a synthetic chunk with a tenth of the samples ancient
-(`--sample_ages`), once with the host tree builder and once with the device's (the AGES build of minmatch_gpu.hip):
+(`--sample_ages`), once with the host tree builder and once with the device's (the AGES build of minmatch_build.h):
 wall-clock of the stage, trees per builder, and that the files are the same.  -> one JSON line (and
 gpurun_out/ages_stage_compare.json)."""
 import json
