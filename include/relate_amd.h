@@ -364,6 +364,21 @@ int rl_debug_builder_throughput(int N, double theta, int device, int builders, i
  * scripts/RelateParallel/RelateParallel.sh:231-257); 7/8 of the worker slots with whole windows resident, 29/64 of the
  * CUs (times the kernel's workgroups per CU) when the windows are bounded and RePaint runs all through the stage. */
 int rl_debug_stage_worker_goal(int cus, int open_sections, int bounded_windows, int workers_per_cu);
+/* Test hook (host only): how a stage sizes itself against HBM (relate_amd/csrc/stage_plan.h plan_sections), from plain
+ * numbers.  In: the chunk's sizes (S, waves: a posterior row is S * 64 * waves floats); rows_of[num_windows], the
+ * posterior rows of every section's window; the sections of the call; whether a window holds stones of its own (a
+ * stage from paint files, or stones parked in host memory); trees on the device or the host; `room`, 0.9 of the free
+ * HBM, if known; this rank's host threads; the knobs as the stage resolves them (environment, rl_stage_opts,
+ * fallback: window_rows and section_threads with whether they were set at all, window_parts, repaint_lanes).
+ * Out: ints_out[6] = section threads, sections the estimate sees open at once, rows a window keeps (0: all), second
+ * RePaint lane wanted (0 / 1), its strips' bytes, and for `probe_section` the smallest cached block that counts as
+ * room for its window; doubles_out[6] = the largest window's rows, bytes per row, per window next to its rows, per
+ * device builder, per bounded window's kept RePaint states, and of `probe_section`'s open window. */
+int rl_debug_stage_plan(int N, int nloc, int S, int waves, const double *rows_of, int num_windows, int first_section,
+                        int last_section, int stones_per_window, int gpu_build, int room_known, double room,
+                        int host_threads, int window_rows_set, long long window_rows, long long window_parts,
+                        int section_threads_set, long long section_threads, long long repaint_lanes, int probe_section,
+                        long long *ints_out, double *doubles_out);
 
 /* Tree-sequence loop of one section, AncesTreeBuilder::BuildTopology
  * (src/anc_builder.cpp:398-656): first tree from the distance matrix at
@@ -440,7 +455,7 @@ typedef struct rl_stage_opts {
   long long window_rows;    /* posterior rows a window keeps resident; 0: from the HBM that is free; < 0: all      */
   int window_parts;         /* a window keeps at least 1/window_parts of its rows (0: 32)                          */
   int section_threads;      /* sections open at once at most (0: from HBM and the device)                          */
-  int workers;              /* tree-builder workgroups on the device (0: the rule of treeseq.cpp stage_worker_goal -- one per open section, 29/64 of the CUs when the windows are bounded, times the kernel's workgroups per CU) */
+  int workers;              /* tree-builder workgroups on the device (0: the rule of stage.cpp stage_worker_goal -- one per open section, 29/64 of the CUs when the windows are bounded, times the kernel's workgroups per CU) */
   int repaint_lanes;        /* RePaint launches side by side: 1 or 2 (0: 1)                                        */
   int park_stones;          /* fused stage: stepping stones to pinned host memory after Paint (rl_park_stones)     */
   int pin_threads;          /* section threads pinned to L3 groups: 1 / 0 (-1: 1)                                  */

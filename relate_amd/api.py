@@ -710,6 +710,30 @@ def map_mutation(parent, carriers):
     return r
 
 
+STAGE_PLAN_INTS = ("nthreads", "concurrent", "cap_rows", "wants_second_lane", "lane2_bytes", "min_block")
+STAGE_PLAN_DOUBLES = ("max_rows", "row_bytes", "fixed_bytes", "builder_bytes", "bstate_bytes", "window_bytes")
+
+
+def debug_stage_plan(N, nloc, S, waves, rows_of, first_section, last_section, stones_per_window, gpu_build, room_known,
+                     room, host_threads, window_rows_set, window_rows, window_parts, section_threads_set,
+                     section_threads, repaint_lanes, probe):
+    """rl_debug_stage_plan: the stage's sizing (stage_plan.h plan_sections) for plain numbers -> dict of the plan's
+    fields, window_bytes and min_block those of section `probe`"""
+    rows_of = np.ascontiguousarray(rows_of, dtype=np.float64)
+    ints = np.zeros(len(STAGE_PLAN_INTS), np.int64)
+    doubles = np.zeros(len(STAGE_PLAN_DOUBLES), np.float64)
+    f = lib().rl_debug_stage_plan
+    f.restype = C.c_int
+    f.argtypes = ([C.c_int] * 4 + [C.c_void_p] + [C.c_int] * 6 + [C.c_double, C.c_int, C.c_int, C.c_longlong, C.c_longlong,
+                  C.c_int, C.c_longlong, C.c_longlong, C.c_int, C.c_void_p, C.c_void_p])
+    _check(f(N, nloc, S, waves, _p(rows_of), len(rows_of), first_section, last_section, int(stones_per_window),
+             int(gpu_build), int(room_known), float(room), host_threads, int(window_rows_set), window_rows, window_parts,
+             int(section_threads_set), section_threads, repaint_lanes, probe, _p(ints), _p(doubles)))
+    out = {k: int(v) for k, v in zip(STAGE_PLAN_INTS, ints)}
+    out.update({k: float(v) for k, v in zip(STAGE_PLAN_DOUBLES, doubles)})
+    return out
+
+
 def debug_cancel_rowmin(d, carriers, log_ratio):
     """rl_debug_cancel_rowmin: cancel_rowmin_kernel on a copy of the N x N float32 matrix d -> (matrix, row minima)"""
     d = np.array(d, dtype=np.float32, order="C")

@@ -199,7 +199,7 @@ struct rl_ctx {
   // A RePaint launch of one of the context's windows needs the forward strips (d_k2_scratch) and a stream: one at a
   // time on s0 (the windows' other work -- distance matrices -- runs on their own streams, side by side).
   std::mutex repaint_mutex;
-  // A stage may open a SECOND lane (strips, stream, events of its own; RELATE_AMD_REPAINT_LANES=2, treeseq.cpp): a
+  // A stage may open a SECOND lane (strips, stream, events of its own; RELATE_AMD_REPAINT_LANES=2, stage.cpp): a
   // launch is a forward and a backward kernel of one workgroup per target, each as long as its longest target, on
   // the CUs the tree builder's workers leave -- two windows' launches side by side fill each other's tails.
   struct RepaintLane {
@@ -249,7 +249,7 @@ float fast_log_host(float v);
 }  // namespace rl
 
 
-// the caller's rl_stage_opts, whatever its age, onto the defaults (treeseq.cpp); RL_EINVAL for a struct that never
+// the caller's rl_stage_opts, whatever its age, onto the defaults (stage.cpp); RL_EINVAL for a struct that never
 // went through rl_stage_opts_init
 extern "C" int rl_internal_resolve_opts(const rl_stage_opts *in, rl_stage_opts *out);
 

@@ -98,7 +98,7 @@ void *cache_alloc(BlockCache &c, size_t bytes, size_t *got, AllocFn raw_alloc) {
       }
     }
     // (workers leave 50 ms after the last tree: a few seconds cover a caller that follows a build; inside a busy
-    //  stage they never leave, and the stage's admission loop is the one that waits -- treeseq.cpp)
+    //  stage they never leave, and the stage's admission loop is the one that waits -- stage.cpp)
     for (int waited = 0; g_worker_launches.load() > 0 && waited < 50; waited++)
       std::this_thread::sleep_for(std::chrono::milliseconds(100));
     if (g_worker_launches.load() == 0) {

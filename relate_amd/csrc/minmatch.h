@@ -294,7 +294,7 @@ int device_builder_expect(int device, int N, int builders, bool ages = false);
 int device_builder_expect_add(int device, int N, int delta, bool ages = false);
 // workgroups of the worker kernel for trees of N leaves a CU holds (1 or 2)
 int device_builder_workers_per_cu(int N, bool ages = false);
-// the stage's rule for how many resident workers to ask for (treeseq.cpp)
+// the stage's rule for how many resident workers to ask for (stage.cpp)
 int stage_worker_goal(int cus, int open_sections, bool bounded_windows, int per_cu);
 
 }  // namespace rl

@@ -29,14 +29,8 @@
 #include <vector>
 
 #include "common.h"
-
-namespace rl {
-// (treeseq.cpp) a tree-sequence object that borrows the panel instead of copying it
-rl_treeseq *treeseq_borrowing(int N, int L, const uint32_t *bits, int row_words, const double *rpos, const int *bp_pos,
-                              const int *state, double theta);
-int device_builder_reserve_shared(int device, int N);
-int device_builder_expect_add(int device, int N, int delta, bool ages = false);
-}  // namespace rl
+#include "minmatch.h"
+#include "treeseq.h"
 
 using namespace rl;
 

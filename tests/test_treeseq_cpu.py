@@ -116,7 +116,7 @@ def test_device_builder_rng_restatement_matches_the_library(seed):
 
 
 def test_stage_worker_rule():
-    """treeseq.cpp: stage_worker_goal -- the counts the measured configurations ran with"""
+    """stage.cpp: stage_worker_goal -- the counts the measured configurations ran with"""
     from relate_amd import api
     g = api.lib().rl_debug_stage_worker_goal
     assert g(256, 134, 1, 1) == 112   # C3: 134 open sections, bounded windows, one worker per CU: 29/64 of the CUs in whole XCD rounds

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""The stage's worker rule (treeseq.cpp: stage_worker_goal) against other counts: the fused stage of
+"""The stage's worker rule (stage.cpp: stage_worker_goal) against other counts: the fused stage of
 one chunk per tree size -- N = 2000 (a C4 chunk), N = 5000 (the L = 100k cut of C3, 53 windows), N = 10,000
 (L = 20k, 33 windows) -- with the rule's own count and with RELATE_AMD_BUILD_WORKERS = 0.75 / 1.25 / 1.5 x of it.
 
