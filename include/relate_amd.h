@@ -228,6 +228,17 @@ int rl_debug_term_split(int S, int *ks, int *r);
  * (the kernels then redo that lane from its exact entry value); out_table is zeroed.  RL_EINVAL for bad arguments. */
 int rl_debug_walk_table(const int *A4, int p0, int sh, int delta_lo, int delta_hi, int *packable, int *out_table,
                         int *out_reference);
+/* Host only: the exact order's walk over the lanes of one wave (relate_amd/csrc/exact_sum.h walk_enter, walk_leave).
+ * records: [lanes][7] ints {kind, U_0, U_1, U_2, U_3, p0, sh}, 1 <= lanes <= 64.  RL_WALK_TRANSLATION: delta -> delta + U_0
+ * (any int, modulo 2^32).  RL_WALK_TABLE: a head, delta -> (delta >> sh) + U_h, h = (p0 + delta) & 3, every U_h an
+ * int16.  RL_WALK_CONSTANT: a head whose exit offset is U_0 (an int16) whatever came before.  entry_delta: the offset
+ * on entry of lane 0.  *out_literal: the exit offset lane by lane, a table lane in the literal form
+ * (walk_hop_reference); *out_scan: as the kernels compute it, from the inclusive add-scan of the translations and a
+ * walk over the heads.  RL_EINVAL for bad arguments. */
+#define RL_WALK_TRANSLATION 0
+#define RL_WALK_TABLE 1
+#define RL_WALK_CONSTANT 2
+int rl_debug_walk_lanes(const int *records, int lanes, int entry_delta, int *out_literal, int *out_scan);
 
 /* Experiment builds only (kernels compiled with -DRL_STATS and
  * RELATE_AMD_TEST_STATS set): 16 event counters of the last rl_paint. */

@@ -162,6 +162,23 @@ def walk_table(A4, p0, sh, delta_lo, delta_hi):
     return bool(ok.value), tab, ref
 
 
+WALK_TRANSLATION, WALK_TABLE, WALK_CONSTANT = 0, 1, 2
+
+
+def walk_lanes(records, entry_delta=0):
+    """rl_debug_walk_lanes: the exact order's walk over one wave's lanes, records [lanes][7] int32 = (kind, U_0, U_1,
+    U_2, U_3, p0, sh) with kind WALK_TRANSLATION (delta -> delta + U_0), WALK_TABLE (a head with a hop table) or
+    WALK_CONSTANT (a head that exits at U_0) -> (exit offset lane by lane in the literal form, exit offset from the
+    add-scan of the translations and the walk over the heads) (host code, no GPU)"""
+    records = np.ascontiguousarray(records, dtype=np.int32)
+    assert records.ndim == 2 and records.shape[1] == 7
+    lit, scan = C.c_int(), C.c_int()
+    f = lib().rl_debug_walk_lanes
+    f.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]
+    _check(f(_p(records), int(records.shape[0]), int(entry_delta), C.byref(lit), C.byref(scan)))
+    return lit.value, scan.value
+
+
 def paint_segment_range(lo, hi, seg, s):
     """rl_paint_segment_range: -> (first, last): segment s of seg walks [first, last) of the step range [lo, hi)
     (host code, no GPU; the kernels run the same function)"""

@@ -241,3 +241,81 @@ extern "C" int rl_debug_walk_table(const int *A4, int p0, int sh, int delta_lo, 
   }
   return RL_OK;
 }
+
+// host only: the walk over one wave's lanes (exact_sum.h) for per-lane records {kind, U_0, U_1, U_2, U_3, p0, sh} --
+// lane by lane in the literal form, and as the kernels do it: the add-scan of the translations, then the heads
+extern "C" int rl_debug_walk_lanes(const int *records, int lanes, int entry_delta, int *out_literal, int *out_scan) {
+  using namespace rl;
+  if (!records || !out_literal || !out_scan) {
+    set_error("rl_debug_walk_lanes: null argument");
+    return RL_EINVAL;
+  }
+  if (lanes < 1 || lanes > 64) {
+    set_error("rl_debug_walk_lanes: lanes=%d outside 1..64", lanes);
+    return RL_EINVAL;
+  }
+  for (int l = 0; l < lanes; l++) {
+    const int *r = records + 7 * l;
+    if (r[0] < RL_WALK_TRANSLATION || r[0] > RL_WALK_CONSTANT) {
+      set_error("rl_debug_walk_lanes: lane %d: kind=%d outside 0..2", l, r[0]);
+      return RL_EINVAL;
+    }
+    if (r[0] == RL_WALK_TABLE &&
+        (r[5] < 0 || r[5] > 3 || r[6] < 0 || r[6] > 1 || !walk_table_pack_runs(r[1], r[2], r[3], r[4]).ok)) {
+      set_error("rl_debug_walk_lanes: lane %d: p0=%d outside 0..3, sh=%d outside 0..1 or a U_h that is no int16", l,
+                r[5], r[6]);
+      return RL_EINVAL;
+    }
+    if (r[0] == RL_WALK_CONSTANT && (short)r[1] != r[1]) {
+      set_error("rl_debug_walk_lanes: lane %d: the exit offset %d of a constant lane is no int16", l, r[1]);
+      return RL_EINVAL;
+    }
+  }
+  // the literal form: one lane after the other, a table lane as A_h + ((delta - B_h) >> sh), A_h = U_h + (B_h >> sh)
+  int delta = entry_delta;
+  for (int l = 0; l < lanes; l++) {
+    const int *r = records + 7 * l;
+    if (r[0] == RL_WALK_TRANSLATION) {
+      delta = (int)((unsigned)delta + (unsigned)r[1]);
+    } else if (r[0] == RL_WALK_CONSTANT) {
+      delta = r[1];
+    } else {
+      int A[4];
+      for (int h = 0; h < 4; h++) A[h] = r[1 + h] - walk_run_offset(0, h, r[5], r[6]);  // U_h + (B_h >> sh)
+      delta = walk_hop_reference(A[0], A[1], A[2], A[3], r[5], r[6], delta);
+    }
+  }
+  *out_literal = delta;
+  // as sum_exact_fast: T = inclusive scan of (head ? 0 : C); start behind the last constant lane; per head
+  // walk_enter, the hop through the packed table and the meta word (walk_head_hop), walk_leave; the trailing
+  // translations
+  unsigned T[64], run = 0;
+  unsigned long long todo = 0;
+  int qc = -1;
+  for (int l = 0; l < lanes; l++) {
+    const int *r = records + 7 * l;
+    if (r[0] == RL_WALK_TRANSLATION)
+      run += (unsigned)r[1];
+    else
+      todo |= 1ull << l;
+    if (r[0] == RL_WALK_CONSTANT) qc = l;
+    T[l] = run;
+  }
+  int rel = entry_delta;
+  if (qc >= 0) {
+    rel = walk_leave((int)(short)walk_table_pack_runs(records[7 * qc + 1], 0, 0, 0).lo, T[qc]);
+    todo &= ~((2ull << qc) - 1ull);
+  }
+  while (todo) {
+    const int q = __builtin_ctzll(todo);
+    todo &= todo - 1;
+    const int *r = records + 7 * q;
+    const WalkTable t = walk_table_pack_runs(r[1], r[2], r[3], r[4]);
+    const int m = walk_meta(r[5], r[6], false);
+    delta = walk_enter(rel, T[q]);
+    delta = walk_head_hop(t.lo, t.hi, m, delta);
+    rel = walk_leave(delta, T[q]);
+  }
+  *out_scan = walk_enter(rel, T[lanes - 1]);
+  return RL_OK;
+}

@@ -26,16 +26,20 @@
 //       r_3 runs show the same exponent after every term (their high words are
 //       xor-ed and or-accumulated term by term) so does every run in between,
 //       the true one included.
-// In integer offsets delta_l = (s_l - P_l)/ulp a lane without a rounding tie
-// acts as delta -> ((delta + K) >> s) + C (s = binade crossings inside, 0 or 1);
-// such maps compose into maps of the same form, so a segmented wavefront scan
-// composes them all at once.  What remains sequential is a walk over the few
-// lanes (measured ~3.5 per sum at N = 5000) where a tie made the four runs
-// disagree (4-entry table, walk_table_hop below) or where the run jumps two or
-// more binades (a term much larger than the prefix, ~0.9 per sum: that lane
-// redoes its run from its exact entry value).  Anything else irregular (P_l within 16384 ulp of a power
-// of two, ...) falls back to the literal serial sum for that step (measured:
-// < 1e-4 of the steps).
+// In integer offsets delta_l = (s_l - P_l)/ulp a lane without a rounding tie that
+// stays in its binade acts as the translation delta -> delta + C; translations
+// compose by adding, so one plain integer add-scan over the wavefront composes
+// them all at once (wave_scan_u32, walk_enter below).  What remains sequential is
+// a walk over the few other lanes, the heads: where a tie made the four runs
+// disagree or the run crosses one binade (delta -> (delta >> s) + U_h from a
+// 4-entry table, walk_head_hop below; ~2.5 tie lanes per sum at N = 5000 and
+// about as many crossings, DESIGN_NOTES 17), or where the run jumps two or more
+// binades (a term much larger than the prefix, ~0.65 per sum: that lane redoes
+// its run from its exact entry value).  Anything else irregular (P_l within
+// 16384 ulp of a power of two, ...) falls back to the literal serial sum for
+// that step (measured: < 1e-4 of the steps).  (Targets spread over two waves,
+// N > 5120, still compose the crossing lanes in a segmented scan and walk the
+// rest: sum_exact_fast_segmented.)
 // The result is ALWAYS the serial sum, bit for bit.
 #pragma once
 #include "paint_device.h"
@@ -64,6 +68,17 @@ RL_DEV double wave_scan_f64(double v) {
   v += dpp_f64<DPP_ROW_SHR + 8>(v);
   v += dpp_f64<DPP_ROW_BCAST15, 0xa>(v);
   v += dpp_f64<DPP_ROW_BCAST31, 0xc>(v);
+  return v;
+}
+// the same over unsigned integers modulo 2^32: each step is one v_add_u32 with a DPP operand (the zero shifted in,
+// and read by the rows a broadcast step does not select, is the identity: such a row keeps its value)
+RL_DEV unsigned wave_scan_u32(unsigned v) {
+  v += (unsigned)dpp_i32<DPP_ROW_SHR + 1>((int)v);
+  v += (unsigned)dpp_i32<DPP_ROW_SHR + 2>((int)v);
+  v += (unsigned)dpp_i32<DPP_ROW_SHR + 4>((int)v);
+  v += (unsigned)dpp_i32<DPP_ROW_SHR + 8>((int)v);
+  v += (unsigned)dpp_i32<DPP_ROW_BCAST15, 0xa>((int)v);
+  v += (unsigned)dpp_i32<DPP_ROW_BCAST31, 0xc>((int)v);
   return v;
 }
 RL_DEV int hi32(double v) { return (int)(__double_as_longlong(v) >> 32); }
@@ -328,10 +343,11 @@ RL_DEV double sum_exact_fallback_linked(const T &term, const WaveLink<WAVES> &lk
 // B_h = h - p0 (mod 4) for all four starts (G4 is a multiple of 4) and delta = h - p0 (mod 4) by the choice of h, so
 // delta - B_h is a multiple of 4 and for sh in {0, 1} the shift distributes exactly:
 //   A_h + ((delta - B_h) >> sh)  =  (delta >> sh) + U_h,   U_h = A_h - (B_h >> sh).
-// U_h is the `d` of the affine test (a run's increment less Q - P: small), so the four fit signed 16-bit fields of
-// two registers, built by all lanes at once during classification, which needs them anyway; the walk's dependent
-// path per tie lane is then a shift-and-add, a mask, a 64-bit shift, a sign extension, and one shift of delta and an
-// add -- no select of A_h or B_h by h, and every read from the lane comes before it.
+// U_h is a run's increment less Q - P (small; where sh = 0 and all four agree, the lane is a translation by it), so
+// the four fit signed 16-bit fields of two registers, built by all lanes at once during classification, which needs
+// them anyway; the walk's dependent path per head with a table is then a shift, an add, a 64-bit shift, a sign
+// extension, and one shift of delta and an add -- no select of A_h or B_h by h, and every read from the lane comes
+// before it.
 // One function each for the kernels and the host (rl_debug_walk_table); integers only.
 constexpr int WALK_G4 = 16384;  // half-width of the bracket [r_0, r_3] in ulps
 RL_HD inline int walk_hop_reference(int A0, int A1, int A2, int A3, int p0, int sh, int delta) {
@@ -365,6 +381,31 @@ RL_HD inline int walk_table_hop(int lo, int hi, int p16, int sh, int delta) {
   const unsigned long long t = ((unsigned long long)(unsigned)hi << 32) | (unsigned)lo;
   return (delta >> sh) + (int)(short)(unsigned short)(t >> (((delta << 4) + p16) & 48));
 }
+// The head's meta word of the one-wave walk: p0 in bits 4..5, where the field offset wants it, above it the redo flag
+// and sh (sh last: a multi-binade lane's sh spills upwards only, and is read for table lanes alone, where it is 0 or
+// 1).  walk_head_hop is walk_table_hop from that word: the field offset is the low six bits of (delta << 4) + meta,
+// which is all a 64-bit shift reads, so nothing of meta has to be masked out first.
+enum { WALK_META_REDO = 64, WALK_META_SH_BIT = 7 };
+RL_HD inline int walk_meta(int p0, int sh, bool redo) {
+  return (p0 << 4) | (redo ? WALK_META_REDO : 0) | (sh << WALK_META_SH_BIT);
+}
+RL_HD inline int walk_head_hop(int lo, int hi, int meta, int delta) {
+  const unsigned long long t = ((unsigned long long)(unsigned)hi << 32) | (unsigned)lo;
+  return (delta >> ((meta >> WALK_META_SH_BIT) & 1)) + (int)(short)(unsigned short)(t >> (((delta << 4) + meta) & 63));
+}
+
+// ---- the walk between two heads ----------------------------------------------
+// A tie-free lane that stays in its binade (and an exact-entry lane) is a pure translation delta -> delta + C, and
+// translations compose by adding: T = the inclusive scan over the wave of (head ? 0 : C), one register, no segments.
+// Between heads the walk keeps rel = delta - T, which no translation changes: in front of head q the offset is
+// walk_enter(rel, T[q]), behind it rel = walk_leave(delta, T[q]) -- a head adds 0 to the scan, so T[q] = T[q-1], and
+// lane q itself is read, never lane q - 1.  rel starts as the entry offset (T
+// is 0 in front of lane 0), as walk_leave(A0, T[qc]) behind a `constant` lane qc, and the exit offset of the wave is
+// walk_enter(rel, T[63]).
+// Only differences of T are used, so its wrap-around modulo 2^32 is harmless: the arithmetic is unsigned.
+// The same functions for the kernels and the host (rl_debug_walk_lanes); integers only.
+RL_HD inline int walk_enter(int rel, unsigned T) { return (int)((unsigned)rel + T); }
+RL_HD inline int walk_leave(int delta, unsigned T) { return (int)((unsigned)delta - T); }
 
 #ifdef RL_STATS
 #define RL_CLK() __builtin_readcyclecounter()
@@ -376,8 +417,207 @@ RL_HD inline int walk_table_hop(int lo, int hi, int p16, int sh, int delta) {
 
 // L: this lane's serial sum of its terms from +0.0 (the caller accumulates it
 // inside its update loop, where the dependent adds hide behind other work).
+template <int S, typename T>
+RL_DEV double sum_exact_fast(const T &term, double L) {
+  constexpr bool REG_TERM = T::REG;
+  constexpr int G4 = WALK_G4;  // half-width of the bracket [r_0, r_3] in ulps
+
+  const unsigned long long tk0 = RL_CLK();
+  // ---- A. approximate prefix from the lanes' local serial sums
+  double Q = wave_scan_f64(L);                // ~ sum over lanes <= l (of this wave)
+  double P = dpp_f64<DPP_WAVE_SHR1>(Q);       // ~ entry value of this lane (lane 0: +0.0)
+  const long long pb = __double_as_longlong(P);
+  // Lanes whose entry value is known exactly need no bracket: nothing but zeros before the lane (entry
+  // +0.0; lane 0 always), and lane 1, whose entry is lane 0's local sum -- a serial sum
+  // from +0.0, i.e. the true prefix.  Their four runs start AT the entry, so the run is the true one whatever
+  // it crosses (lane 1 is where two-binade jumps are most frequent), and the lane's map is the constant
+  // exit offset.
+  const bool zero_entry = pb == 0 || (threadIdx.x & 63) == 1;
+
+  const unsigned long long tk1 = RL_CLK();
+  // ---- B. four runs from r_h = h (mod 4 ulp), r_0 / r_3 bracketing the true entry
+  const long long base = pb & ~3ll;
+  const int p0 = (int)(pb & 3);
+  double c0 = __longlong_as_double(base - G4);
+  double c1 = __longlong_as_double(base + 1);
+  double c2 = __longlong_as_double(base + 2);
+  double c3 = __longlong_as_double(base + 3 + G4);
+  if (zero_entry) { c0 = P; c1 = P; c2 = P; c3 = P; }
+  const double r0 = c0, r3 = c3;
+  const int e_in = expo_field(r0);
+  const bool entry_ok = zero_entry || (e_in == expo_field(r3) && e_in > 64);
+  int exdiff = 0;  // OR over the terms of (high word of c0) xor (high word of c3)
+  double thB = term.th, nthB = term.nth;
+  term.for_each(thB, nthB, [&](int, double x) {
+    c0 += x;
+    c1 += x;
+    c2 += x;
+    c3 += x;
+    // exponent fields of the two bracketing runs must agree after every term:
+    // exdiff |= hi(c0) ^ hi(c3), one v_bitop3_b32 per term (bits 20..30 count)
+    exdiff = __builtin_amdgcn_bitop3_b32(exdiff, hi32(c0), hi32(c3), 0xF6);
+    // Tie the check to its partial sums: otherwise the scheduler first runs the chains to the end and keeps all
+    // partial sums alive.  A scheduling barrier, not an empty asm statement with the sums as operands: the hazard
+    // recognizer treats an inline asm that names registers a double-precision instruction has just written as a
+    // reader of them and puts a wait state in front -- one s_nop per term, 80 of the ~1000 issue slots of a forward
+    // step (round 4, seen in the ISA).
+    // (The backward pass, whose terms are recomputed here four at a time, keeps the asm statement: with the barrier
+    //  alone its chain block spills 47 register pairs.)
+    if constexpr (REG_TERM)
+      __builtin_amdgcn_sched_barrier(0);
+    else
+      asm volatile("" : "+v"(exdiff), "+v"(c1), "+v"(c2), "+v"(thB), "+v"(nthB));  // (c0, c3: through exdiff)
+  });
+  const unsigned long long tk2 = RL_CLK();
+  const int e_out = expo_field(c0);
+  // exit unit = entry unit of the next lane = ulp of the binade of Q
+  const int e_next = expo_field(Q);
+  // An exit offset (c - Q) / ulp is asked for only where c lies in Q's binade (every other lane is invalid or walked
+  // from its exact entry): there it is the difference of the two bit patterns -- one integer subtraction of the low
+  // words instead of a subtraction, a multiplication and a quarter-rate conversion in double precision, six times
+  // per sum (round 4).
+  const unsigned q_lo = (unsigned)__double_as_longlong(Q);
+  auto exit_offset = [&](double c) -> int { return (int)((unsigned)__double_as_longlong(c) - q_lo); };
+
+  // ---- classification
+  const bool same_seq = (exdiff >> 20) == 0;
+  const int sh = e_out - e_in;
+  bool invalid = !entry_ok || !same_seq;
+  // the exit must sit in the binade the next lane (or the caller) measures in
+  if (!zero_entry && e_out != e_next) invalid = true;
+  if (zero_entry && expo_field(c0) != e_next) invalid = true;
+  // a run that jumps two or more binades (a term much larger than the prefix)
+  // does not fit the mod-4 argument: the walk redoes it from its exact entry
+  const bool jump = !zero_entry && !invalid && sh >= 2;
+  // ... unless the two bracketing runs END on the same value: addition is
+  // monotone in its start, so every run started inside the bracket ends there
+  // too, the true one included -- the exit is known outright and nothing to
+  // the left of this lane matters any more (the usual case: the big term
+  // swamps the 2^15 ulp of the bracket)
+  const bool constant = jump && __double_as_longlong(c0) == __double_as_longlong(c3);
+  const bool special = jump && !constant;
+
+  // offsets are in units of the exit ulp.  Exit offsets of the four runs
+  // (|A_h| < 2^15) and entry offsets B_h = (r_h - P)/ulp_in of their starts:
+  int A0 = 0;
+  if (constant) A0 = exit_offset(c0);
+  // exact entry: the exit is c0 itself; offset 0 wherever the approximate prefix Q is that same sum (lane 0,
+  // all-zero prefixes), a few ulp for lane 1
+  if (zero_entry && __double_as_longlong(c0) != __double_as_longlong(Q)) A0 = exit_offset(c0);
+  // The lane's map is delta -> A_h + ((delta - B_h) >> sh), h = (p0 + delta) & 3, B_h = (r_h - P)/ulp_in the entry
+  // offsets of the four starts; with U_h = A_h - (B_h >> sh) (walk_run_offset) it is (delta >> sh) + U_h.  A lane that
+  // stays in its binade (sh = 0) and whose four U_h agree (no tie) is the translation delta -> delta + U_0.  So is an
+  // exact-entry lane: delta is 0 on entry (nothing but exact lanes before it) and A0 on exit.  Every other valid lane
+  // is a head, which the walk visits: a tie lane, a lane that crosses one binade (sh = 1; with or without a tie, the
+  // hop (delta >> 1) + U_h covers both), a multi-binade run and a `constant` lane.
+  const bool table = !invalid && !jump && !zero_entry;  // sh is 0 or 1
+  int U0 = A0, U1 = 0, U2 = 0, U3 = 0;  // (a `constant` lane: its A0 in the table's low field, where the walk starts)
+  bool translation = zero_entry;
+  if (table) {
+    U0 = walk_run_offset(exit_offset(c0), 0, p0, sh);
+    U1 = walk_run_offset(exit_offset(c1), 1, p0, sh);
+    U2 = walk_run_offset(exit_offset(c2), 2, p0, sh);
+    U3 = walk_run_offset(exit_offset(c3), 3, p0, sh);
+    translation = sh == 0 && U0 == U1 && U1 == U2 && U2 == U3;
+  }
+  // the hop table of a head with one (walk_table_pack); the fields of every other lane are never read, but for the
+  // low field of a `constant` lane
+  const WalkTable wt = walk_table_pack_runs(U0, U1, U2, U3);
+  // A U_h beyond int16 (never seen: |U_h| is bounded by the error of Q - P, (1) above): the lane has no table and is
+  // redone from its exact entry value like a multi-binade run, which is right for every lane that is not invalid.
+  // (the flag is read for heads only: !wt.ok needs no `table && !translation` beside it)
+  const bool redo = special || !wt.ok;
+  const int t01 = wt.lo, t23 = wt.hi;
+  // a register of its own, read for heads only (sh: read for table lanes only, where it is 0 or 1)
+  const int meta = walk_meta(p0, sh, redo);
+
+  // the caller's unit: the total is returned as Q_63 + delta * ulp(Q_63); Q_63
+  // must not be within the bracket width of a power of two
+  const double Qt = rd_lane_f64(Q, 63);
+  {
+    const long long qb = __double_as_longlong(Qt) & ~3ll;
+    const int ea = expo_field(__longlong_as_double(qb - G4)), eb = expo_field(__longlong_as_double(qb + 3 + G4));
+    if (ea != eb || ea <= 64) invalid = true;
+  }
+  // ---- C. compose the translations with one integer add-scan (walk_enter: a head adds nothing and nothing else
+  // rides in the scanned register), then walk the heads
+  const unsigned TS = wave_scan_u32(translation ? (unsigned)U0 : 0u);
+  RL_STAT(0, 1);
+  if (__ballot(invalid) != 0ull) {
+    RL_STAT(1, 1);
+    return sum_exact_fallback<S>(term);  // irregular step: literal serial sum
+  }
+  const unsigned long long tk3 = RL_CLK();
+  unsigned long long todo = __ballot(!translation);
+  RL_STAT(2, __builtin_popcountll(todo));
+  {
+    const unsigned long long sp = __ballot(special || (table && !translation && !wt.ok));
+    (void)sp;
+    RL_STAT(3, __builtin_popcountll(sp));
+  }
+  // the walk's state: the exact offset less the scan value (walk_enter, walk_leave).  Lane 0 enters at exactly 0 (its
+  // local sum is exact, Q_0 == L_0)
+  int rel = 0;
+  {  // start behind the last lane whose exit is known outright
+    const unsigned long long cm = __ballot(constant);
+    if (cm) {
+      const int qc = 63 - __builtin_clzll(cm);
+      rel = walk_leave((int)(short)__builtin_amdgcn_readlane(t01, qc),  // its A0
+                       (unsigned)__builtin_amdgcn_readlane((int)TS, qc));
+      todo &= ~((2ull << qc) - 1ull);
+    }
+  }
+  while (todo) {
+    const int q = __builtin_ctzll(todo);
+    asm("s_bitset0_b64 %0, %1" : "+s"(todo) : "s"(q));  // todo &= ~(1 << q), one instruction instead of three
+    // Everything read from the lanes is independent of the offset and comes first: the head's hop table, its meta
+    // and its scan value; the offset's own path is then one add in front of the hop (walk_enter), the hop
+    // (walk_head_hop) and one subtraction behind it (walk_leave).  Lane 0 enters at exactly +0.0 and is never walked.
+    const int tlo = __builtin_amdgcn_readlane(t01, q), thi = __builtin_amdgcn_readlane(t23, q);
+    const int m = __builtin_amdgcn_readlane(meta, q);
+    const unsigned Tq = (unsigned)__builtin_amdgcn_readlane((int)TS, q);
+    const int din = walk_enter(rel, Tq);
+    // The hop first and for every head, the rerun after it as the exception: with the two as the arms of one branch
+    // the compiler routes both through a flag and three more branches per head.  (What the hop makes of a lane that
+    // is redone is not used.)
+    int dout = walk_head_hop(tlo, thi, m, din);  // a tie or a crossing lane: sh is 0 or 1
+    if (m & WALK_META_REDO) {
+      // multi-binade run: redo it from the exact entry value
+      const double Pq = rd_lane_f64(P, q);
+      const double uq = pow2_field(expo_field(Pq) - 52);
+      double t = Pq + (double)din * uq;  // exact
+      double thC = term.th, nthC = term.nth;
+      term.for_each(thC, nthC, [&](int, double x) {
+        t += x;
+        if constexpr (!REG_TERM) asm volatile("" : "+v"(thC), "+v"(nthC));  // (not t: a wait state per term, see the chain pass)
+      });
+      const double v = rd_lane_f64(t, q);
+      // (the true exit lies between the bracketing runs, which end in Q's binade -- else the lane were invalid)
+      dout = (int)((unsigned)__double_as_longlong(v) - (unsigned)__builtin_amdgcn_readlane((int)q_lo, q));
+    }
+    rel = walk_leave(dout, Tq);
+  }
+  // the translations behind the last head
+  const int delta = walk_enter(rel, (unsigned)__builtin_amdgcn_readlane((int)TS, 63));
+  {
+    const unsigned long long tk4 = RL_CLK();
+    (void)tk0; (void)tk1; (void)tk2; (void)tk3; (void)tk4;
+    RL_STAT(4, tk1 - tk0);  // scan
+    RL_STAT(5, tk2 - tk1);  // four runs
+    RL_STAT(6, tk3 - tk2);  // classification + translation scan
+    RL_STAT(7, tk4 - tk3);  // walk
+  }
+  return Qt + (double)delta * pow2_field(expo_field(Qt) - 52);
+}
+
+// Targets of two waves (N > 5120) keep the sum they had: the tie-free lanes, crossing lanes among them, composed as
+// maps delta -> ((delta + K) >> s) + C by a segmented scan over three registers, the walk over the tie lanes and
+// the multi-binade lanes with the composite of lane q - 1 read in front of each, and the waves meeting in LDS at
+// workgroup barriers.  A run of the whole GPU suite with the one-wave sum above in both places stopped in the test
+// that paints N = 10,000 from two host threads at once; nothing in the sum explains that (DESIGN_NOTES 17), and until
+// something does the two-wave kernels are, instruction for instruction, what they were.
 template <int S, int WAVES, typename T>
-RL_DEV double sum_exact_fast(const T &term, double L, WaveLink<WAVES> &lk) {
+RL_DEV double sum_exact_fast_segmented(const T &term, double L, WaveLink<WAVES> &lk) {
   constexpr bool REG_TERM = T::REG;
   constexpr int G4 = WALK_G4;  // half-width of the bracket [r_0, r_3] in ulps
 
@@ -652,8 +892,10 @@ RL_DEV double wave_sum(const T &term, double L, WaveLink<WAVES> &lk) {
     return lanes_total(L, lk);
   } else {
     lk.phase++;
-    if constexpr (MODE == 1)
-      return sum_exact_fast<S, WAVES>(term, L, lk);
+    if constexpr (MODE == 1 && WAVES == 1)
+      return sum_exact_fast<S>(term, L);
+    else if constexpr (MODE == 1)
+      return sum_exact_fast_segmented<S, WAVES>(term, L, lk);
     else
       return sum_exact_fallback_linked<S, WAVES>(term, lk);
   }

@@ -7,7 +7,7 @@ prints the 16 event counters of exact_sum.h / paint_kernels.hip per sum.
 
 counters 0..7: forward sums, 8..15: backward sums -- number of sums, fallbacks to the literal order, lanes walked,
 lanes re-run from their exact entry (two-binade jumps), cycles in the scan / the four chains / the classification and
-map scan / the walk."""
+the scan of the translations / the walk."""
 import ctypes as C
 import json
 import os
