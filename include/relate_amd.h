@@ -758,6 +758,54 @@ int rl_coalrate_finalize(const float *data, int N, int nepochs, const int *group
                          double *rates);
 int rl_coalrate_finalize_files(const char *bin_path, const char *poplabels_or_null, const char *coal_path);
 
+/* ------------------------------------------------------------------ Frequency and Selection
+ * The two modes of the reference's RelateSelection that DetectSelection.sh runs
+ * (include/evaluate/selection/RelateSelection.cpp): allele frequency through time, and its p-values.
+ *
+ * Frequency.  Node times are those of Tree::GetCoordinates (src/anc.cpp:525-537): t(leaf) = 0, t(m) =
+ * (float)max((double)t(c2) + bl[c2], (double)t(c1) + bl[c1]).  The boundaries are rl_coalrate_epochs' (the reference's
+ * :381-464 yields the same floats).  A SNP on branch b of its tree, b neither -1 nor the root, has a row: with T the
+ * internal nodes of the tree and S those in the subtree of b (b included if internal), for every boundary e, from the
+ * oldest to 0,
+ *   lineages (.lin)  = 0 if t(root) < e, else 1 + |{u in T : t(u) > e}|
+ *   carriers (.freq) = 0 if t(root) < e or t(parent(b)) <= e, else 1 + |{u in S : t(u) > e}|
+ * and, with DAF the leaves below b and h = (DAF + 1) / 2: when_DAF_is_half = -1 if h <= 1, else 1 + |{u in T : t(u) >=
+ * x}| with x the (h-1)-th largest time in S; when_mutation_has_freq2 = -1 if b is a leaf, else 1 + |{u in T : t(u) >=
+ * t(b)}|; TreeFreq = 0.  That closed form equals the reference's walk (:556-788) on trees in which no two internal
+ * nodes have equal float times and none has a time <= 0; on every other tree the rows are those of the walk itself,
+ * restated on the host (relate_amd/csrc/frequency.cpp), whose live asserts are RL_EINVAL naming the tree and the SNP.
+ *   rl_frequency_trees (replaces :510-516, :541-547, :556-788): parents, branch_length [ntrees][2N-1]; nsnps SNPs with
+ *     snp_tree (rising, in [0, ntrees)) and snp_branch (in [-1, 2N-2]); freq [nsnps][E+1]: the carriers per boundary,
+ *     then TreeFreq; lin [nsnps][E+2]: the lineages per boundary, when_DAF_is_half, when_mutation_has_freq2; marks
+ *     [nsnps]: 1 where the row is there, 0 where the branch is -1 or the root (the row is untouched); root_time
+ *     [ntrees]; *host_trees: trees with a marked SNP whose rows came from the host walk.  device >= 0: on that GPU
+ *     (relate_amd/csrc/frequency_kernels.hip; 2 <= N <= 10240, the trees go up in batches of
+ *     rl_frequency_batch_trees(N), trees with tied or non-positive times come back for the host walk; RL_ENODEVICE
+ *     without one); device < 0: the host walk for every tree, one thread, any N >= 2.  2 <= E <= 64.
+ *   rl_frequency_anc (replaces :354-363, :467-814 and AncMutIterators::FirstSNP / NextSNP, src/mutations.cpp:933-1009):
+ *     the trees of a TEXT .anc that have SNPs in the .mut; a SNP is written iff it has exactly one branch, is not
+ *     flipped, age_begin <= t(root) and the branch is neither -1 nor the root (:539-554).  Writes freq_path and
+ *     lin_path as the reference does (`pos rs_id`, every count followed by a space; .freq ends ` TreeFreq DataFreq`
+ *     behind a second space, DataFreq 0).  *rows: rows written; *host_trees as above (either may be NULL).
+ *     RL_EINVAL: sample ages in the header, .gz inputs, a .mut with population-frequency columns, tree indices that
+ *     fall.  (--first_snp / --last_snp of the reference are not offered.)
+ * Selection, on the host (its bytes are libm's):
+ *   rl_selection_logp (replaces log_pvalue, :136-178): log10 of P(at least fN of N lineages carry | fk of k did), in
+ *     the reference's float / double arithmetic; 1 if fk < 2 or k == -1.  The reference's asserts (fN < N, fk < k,
+ *     fN > 0) and an index outside its table of log(k!) are RL_EINVAL.
+ *   rl_selection_files (replaces :190-328): in_prefix.freq + in_prefix.lin (this library's or the reference's) ->
+ *     out_path, the reference's .sele: the .lin's header, then per row `pos rs_id`, a cell per boundary and the two
+ *     trailing cells (fk = (int)((fN + 1) / 2) at when_DAF_is_half, fk = 2 at when_mutation_has_freq2), all `1` for a
+ *     row with fN <= 2; written with the precision of operator<<.  Rows in parallel on RELATE_AMD_THREADS threads. */
+int rl_frequency_batch_trees(int N);
+int rl_frequency_trees(const int *parents, const double *branch_length, int N, int ntrees, const int *snp_tree,
+                       const int *snp_branch, int nsnps, const float *epochs, int nepochs, int device, int *freq, int *lin,
+                       unsigned char *marks, float *root_time, int *host_trees);
+int rl_frequency_anc(const char *anc_path, const char *mut_path, const float *epochs, int nepochs, int device,
+                     const char *freq_path, const char *lin_path, long long *rows, int *host_trees);
+int rl_selection_logp(int k, float fk, int N, float fN, float *logp);
+int rl_selection_files(const char *in_prefix, const char *out_path);
+
 /* ------------------------------------------------------------------ tools */
 /* Synthetic block-coalescent panel (stand-in for MakeChunks input,
  * SURVEY.md 8d).  seq_chars (L*N) and/or bits (L*row_words) may be NULL. */

@@ -85,6 +85,14 @@ def lib():
         L.rl_coalrate_read_bin.argtypes = [C.c_char_p, C.c_void_p, C.POINTER(C.c_int), C.c_void_p, C.POINTER(C.c_int)]
         L.rl_coalrate_finalize.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p]
         L.rl_coalrate_finalize_files.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p]
+        L.rl_frequency_batch_trees.argtypes = [C.c_int]
+        L.rl_frequency_trees.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int,
+                                         C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                         C.POINTER(C.c_int)]
+        L.rl_frequency_anc.argtypes = [C.c_char_p, C.c_char_p, C.c_void_p, C.c_int, C.c_int, C.c_char_p, C.c_char_p,
+                                       C.POINTER(C.c_longlong), C.POINTER(C.c_int)]
+        L.rl_selection_logp.argtypes = [C.c_int, C.c_float, C.c_int, C.c_float, C.POINTER(C.c_float)]
+        L.rl_selection_files.argtypes = [C.c_char_p, C.c_char_p]
         L.rl_window_copying.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
         L.rl_window_copying_host.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
         L.rl_copying_matrix.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.POINTER(C.c_longlong)]
@@ -939,6 +947,58 @@ def coalrate_finalize_files(bin_path, coal_path, poplabels=None):
     """rl_coalrate_finalize_files: out.bin -> out.coal, as FinalizePopulationSize writes it"""
     _check(lib().rl_coalrate_finalize_files(os.fsencode(bin_path), None if poplabels is None else os.fsencode(poplabels),
                                             os.fsencode(coal_path)))
+
+
+def frequency_batch_trees(N):
+    """trees per batch of the device path of frequency_trees / frequency_anc at N leaves"""
+    return lib().rl_frequency_batch_trees(int(N))
+
+
+def frequency_trees(parents, branch_length, snp_tree, snp_branch, epochs, device=None):
+    """rl_frequency_trees: the rows of Frequency for SNPs on the branches snp_branch of the trees snp_tree (rising).
+    parents, branch_length: [trees][2N-1] (or one tree); epochs: [E] floats, epochs[0] = 0, rising; device: None = the
+    host walk, an int = that GPU.
+    -> (freq [snps][E+1] int32: carriers per boundary from the oldest to 0, TreeFreq; lin [snps][E+2] int32: lineages
+    per boundary, when_DAF_is_half, when_mutation_has_freq2; marks [snps] bool: the row is there (the branch is
+    neither -1 nor the root); root_time [trees] float32; host_trees: trees walked on the host)"""
+    pa = np.ascontiguousarray(np.atleast_2d(parents), dtype=np.int32)
+    bl = np.ascontiguousarray(np.atleast_2d(branch_length), dtype=np.float64)
+    st = np.ascontiguousarray(np.atleast_1d(snp_tree), dtype=np.int32)
+    sb = np.ascontiguousarray(np.atleast_1d(snp_branch), dtype=np.int32)
+    ep = np.ascontiguousarray(epochs, dtype=np.float32)
+    if pa.shape[1] % 2 == 0 or bl.shape != pa.shape or st.shape != sb.shape or st.ndim != 1 or ep.ndim != 1:
+        raise RelateError("frequency_trees: parents %s, branch lengths %s, SNP trees %s, SNP branches %s"
+                          % (pa.shape, bl.shape, st.shape, sb.shape))
+    N, E = (pa.shape[1] + 1) // 2, len(ep)
+    freq, lin = np.zeros((len(st), E + 1), np.int32), np.zeros((len(st), E + 2), np.int32)
+    marks, root_time, host_trees = np.zeros(len(st), np.uint8), np.zeros(len(pa), np.float32), C.c_int(0)
+    _check(lib().rl_frequency_trees(_p(pa), _p(bl), N, len(pa), _p(st), _p(sb), len(st), _p(ep), E,
+                                    -1 if device is None else int(device), _p(freq), _p(lin), _p(marks), _p(root_time),
+                                    C.byref(host_trees)))
+    return freq, lin, marks.astype(bool), root_time, host_trees.value
+
+
+def frequency_anc(anc_path, mut_path, epochs, freq_path, lin_path, device=None):
+    """rl_frequency_anc: out.freq and out.lin of `RelateSelection --mode Frequency` from a text .anc and its .mut
+    -> (rows written, trees walked on the host)"""
+    ep = np.ascontiguousarray(epochs, dtype=np.float32)
+    rows, host_trees = C.c_longlong(0), C.c_int(0)
+    _check(lib().rl_frequency_anc(os.fsencode(anc_path), os.fsencode(mut_path), _p(ep), len(ep),
+                                  -1 if device is None else int(device), os.fsencode(freq_path), os.fsencode(lin_path),
+                                  C.byref(rows), C.byref(host_trees)))
+    return rows.value, host_trees.value
+
+
+def selection_logp(k, fk, N, fN):
+    """rl_selection_logp: the reference's log_pvalue(k, fk, N, fN) -> float32"""
+    out = C.c_float(0.0)
+    _check(lib().rl_selection_logp(int(k), float(fk), int(N), float(fN), C.byref(out)))
+    return np.float32(out.value)
+
+
+def selection_files(in_prefix, out_path):
+    """rl_selection_files: in_prefix.freq + in_prefix.lin -> out_path (.sele), as `RelateSelection --mode Selection`"""
+    _check(lib().rl_selection_files(os.fsencode(in_prefix), os.fsencode(out_path)))
 
 
 def stage_find_equivalent_branches(out_dir, chunk_index=0):

@@ -1,0 +1,122 @@
+// anc_text.h -- the text inputs of the modes that read a dated tree sequence (coalrate.cpp: CoalescentRateForSection;
+// frequency.cpp: Frequency): a text file that is refused when compressed, and the text .anc one tree at a time.  `mode`
+// is the name a message starts with.
+#pragma once
+#include <cerrno>
+#include <cstdint>
+#include <cstdio>
+#include <cstdlib>
+#include <fstream>
+#include <sstream>
+#include <string>
+
+#include "common.h"
+
+namespace rl {
+
+inline bool is_gzip(const std::string &fn) {
+  FILE *fp = fopen(fn.c_str(), "rb");
+  if (!fp) return false;
+  unsigned char m[2] = {0, 0};
+  const bool gz = fread(m, 1, 2, fp) == 2 && m[0] == 0x1f && m[1] == 0x8b;
+  fclose(fp);
+  return gz;
+}
+
+// opens a text input of the mode; a missing file whose .gz twin exists, or a gzip file, is refused (RL_EINVAL)
+inline int open_text(const char *mode, const std::string &fn, std::ifstream &is) {
+  is.open(fn);
+  if (is.fail()) {
+    std::ifstream gz(fn + ".gz");
+    if (!gz.fail()) {
+      set_error("%s: %s.gz: compressed inputs are not part of this build, decompress the file", mode, fn.c_str());
+      return RL_EINVAL;
+    }
+    set_error("%s: failed to open file %s", mode, fn.c_str());
+    return RL_EIO;
+  }
+  if (is_gzip(fn)) {
+    set_error("%s: %s is compressed: compressed inputs are not part of this build, decompress the file", mode, fn.c_str());
+    return RL_EINVAL;
+  }
+  return RL_OK;
+}
+
+inline bool parse_int(const std::string &s, int *v) {
+  errno = 0;
+  char *end = nullptr;
+  const long x = strtol(s.c_str(), &end, 10);
+  if (end == s.c_str() || errno || x < INT32_MIN || x > INT32_MAX) return false;
+  *v = (int)x;
+  return true;
+}
+
+// the text .anc (AncMutIterators::OpenFiles, src/mutations.cpp:713-752; Tree::ReadTree, src/anc.cpp:39-80), one tree
+// at a time
+struct AncText {
+  const char *mode;
+  std::string fn;
+  std::ifstream is;
+  int N = 0, trees = 0;
+  bool has_ages = false;
+  std::string line;
+  explicit AncText(const char *m) : mode(m) {}
+  int open(const std::string &path) {
+    fn = path;
+    if (const int rc = open_text(mode, fn, is)) return rc;
+    std::string tag;
+    long long n = 0, t = 0;
+    getline(is, line);
+    std::istringstream h1(line);
+    h1 >> tag >> n;
+    if (h1.fail() || tag != "NUM_HAPLOTYPES") return bad_header();
+    long long ages = 0;
+    for (double a; ages < n && h1 >> a;) ages++;
+    has_ages = n > 0 && ages == n;
+    getline(is, line);
+    std::istringstream h2(line);
+    h2 >> tag >> t;
+    if (h2.fail() || tag != "NUM_TREES") return bad_header();
+    if (n < 2 || n > (1 << 30) || t < 0 || t > INT32_MAX) {
+      set_error("%s: %s: %lld haplotypes, %lld trees: no pair to take", mode, fn.c_str(), n, t);
+      return RL_EINVAL;
+    }
+    N = (int)n, trees = (int)t;
+    return RL_OK;
+  }
+  int bad_header() {
+    set_error("%s: %s does not start with `NUM_HAPLOTYPES N` and `NUM_TREES T`: not a text .anc file", mode, fn.c_str());
+    return RL_EFORMAT;
+  }
+  // `pos: parent:(branch_length num_events snp_begin snp_end) ...`, 2N-1 nodes
+  int next(int index, int *parent, double *bl) {
+    if (!getline(is, line)) {
+      set_error("%s: %s ends before tree %d of %d", mode, fn.c_str(), index, trees);
+      return RL_EFORMAT;
+    }
+    const char *p = line.c_str();
+    char *end = nullptr;
+    (void)strtol(p, &end, 10);
+    bool ok = end != p && *end == ':';
+    p = end + 1;
+    for (int v = 0; ok && v < 2 * N - 1; v++) {
+      const long par = strtol(p, &end, 10);
+      ok = end != p && end[0] == ':' && end[1] == '(' && par >= -1 && par < 2 * (long)N - 1;
+      if (!ok) break;
+      p = end + 2;
+      bl[v] = strtod(p, &end);
+      ok = end != p;
+      parent[v] = (int)par;
+      while (ok && *end && *end != ')') end++;
+      ok = ok && *end == ')';
+      p = end + 1;
+    }
+    if (!ok) {
+      set_error("%s: %s: tree %d is not `pos: parent:(branch_length num_events snp_begin snp_end) ...` for %d nodes", mode, fn.c_str(), index, 2 * N - 1);
+      return RL_EFORMAT;
+    }
+    return RL_OK;
+  }
+};
+
+}  // namespace rl

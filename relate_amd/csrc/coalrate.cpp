@@ -6,7 +6,7 @@
 // uncoalesced in epoch e (the opportunity).  Every element gets at most one float addition per tree, trees in order.
 // As on the device (coalrate_kernels.hip) a row of a tree is a running maximum of g outwards from rank[i]
 // (pairwise.cpp), no walk in the tree.  This file is that on one thread for any N (the CPU suite's implementation,
-// the yardstick of the GPU tests and the `device < 0` path), the epochs, the streaming reader of the text .anc and
+// the yardstick of the GPU tests and the `device < 0` path), the epochs, the loop over the text .anc (anc_text.h) and
 // the .mut with the factors of AncMutIterators::NextTree, the .bin file, the finalize step with the .coal file, and
 // the C entry points.
 #include <cerrno>
@@ -18,6 +18,7 @@
 #include <string>
 #include <vector>
 
+#include "anc_text.h"
 #include "coalrate.h"
 #include "common.h"
 #include "tree_host.h"
@@ -162,47 +163,10 @@ struct MutRow {
   int pos, dist, tree;
 };
 
-bool is_gzip(const std::string &fn) {
-  FILE *fp = fopen(fn.c_str(), "rb");
-  if (!fp) return false;
-  unsigned char m[2] = {0, 0};
-  const bool gz = fread(m, 1, 2, fp) == 2 && m[0] == 0x1f && m[1] == 0x8b;
-  fclose(fp);
-  return gz;
-}
-
-// opens a text input of the mode; a missing file whose .gz twin exists, or a gzip file, is refused (RL_EINVAL)
-int open_text(const std::string &fn, std::ifstream &is) {
-  is.open(fn);
-  if (is.fail()) {
-    std::ifstream gz(fn + ".gz");
-    if (!gz.fail()) {
-      set_error("CoalescentRateForSection: %s.gz: compressed inputs are not part of this build, decompress the file", fn.c_str());
-      return RL_EINVAL;
-    }
-    set_error("CoalescentRateForSection: failed to open file %s", fn.c_str());
-    return RL_EIO;
-  }
-  if (is_gzip(fn)) {
-    set_error("CoalescentRateForSection: %s is compressed: compressed inputs are not part of this build, decompress the file", fn.c_str());
-    return RL_EINVAL;
-  }
-  return RL_OK;
-}
-
-bool parse_int(const std::string &s, int *v) {
-  errno = 0;
-  char *end = nullptr;
-  const long x = strtol(s.c_str(), &end, 10);
-  if (end == s.c_str() || errno || x < INT32_MIN || x > INT32_MAX) return false;
-  *v = (int)x;
-  return true;
-}
-
 // Mutations::Read (src/mutations.cpp:230-318): `;`-separated, the second column pos, the third dist, the fifth tree
 int read_mut(const std::string &fn, std::vector<MutRow> &rows) {
   std::ifstream is;
-  if (const int rc = open_text(fn, is)) return rc;
+  if (const int rc = open_text("CoalescentRateForSection", fn, is)) return rc;
   std::string line, field;
   getline(is, line);  // the header
   long long n = 1;
@@ -256,72 +220,6 @@ struct Persistence {
       tree_in_mut = mut[k].tree;
     }
     return bases;
-  }
-};
-
-// the text .anc (AncMutIterators::OpenFiles, src/mutations.cpp:713-752; Tree::ReadTree, src/anc.cpp:39-80), one tree
-// at a time
-struct AncText {
-  std::string fn;
-  std::ifstream is;
-  int N = 0, trees = 0;
-  bool has_ages = false;
-  std::string line;
-  int open(const std::string &path) {
-    fn = path;
-    if (const int rc = open_text(fn, is)) return rc;
-    std::string tag;
-    long long n = 0, t = 0;
-    getline(is, line);
-    std::istringstream h1(line);
-    h1 >> tag >> n;
-    if (h1.fail() || tag != "NUM_HAPLOTYPES") return bad_header();
-    long long ages = 0;
-    for (double a; ages < n && h1 >> a;) ages++;
-    has_ages = n > 0 && ages == n;
-    getline(is, line);
-    std::istringstream h2(line);
-    h2 >> tag >> t;
-    if (h2.fail() || tag != "NUM_TREES") return bad_header();
-    if (n < 2 || n > (1 << 30) || t < 0 || t > INT32_MAX) {
-      set_error("CoalescentRateForSection: %s: %lld haplotypes, %lld trees: no pair to take", fn.c_str(), n, t);
-      return RL_EINVAL;
-    }
-    N = (int)n, trees = (int)t;
-    return RL_OK;
-  }
-  int bad_header() {
-    set_error("CoalescentRateForSection: %s does not start with `NUM_HAPLOTYPES N` and `NUM_TREES T`: not a text .anc file", fn.c_str());
-    return RL_EFORMAT;
-  }
-  // `pos: parent:(branch_length num_events snp_begin snp_end) ...`, 2N-1 nodes
-  int next(int index, int *parent, double *bl) {
-    if (!getline(is, line)) {
-      set_error("CoalescentRateForSection: %s ends before tree %d of %d", fn.c_str(), index, trees);
-      return RL_EFORMAT;
-    }
-    const char *p = line.c_str();
-    char *end = nullptr;
-    (void)strtol(p, &end, 10);
-    bool ok = end != p && *end == ':';
-    p = end + 1;
-    for (int v = 0; ok && v < 2 * N - 1; v++) {
-      const long par = strtol(p, &end, 10);
-      ok = end != p && end[0] == ':' && end[1] == '(' && par >= -1 && par < 2 * (long)N - 1;
-      if (!ok) break;
-      p = end + 2;
-      bl[v] = strtod(p, &end);
-      ok = end != p;
-      parent[v] = (int)par;
-      while (ok && *end && *end != ')') end++;
-      ok = ok && *end == ')';
-      p = end + 1;
-    }
-    if (!ok) {
-      set_error("CoalescentRateForSection: %s: tree %d is not `pos: parent:(branch_length num_events snp_begin snp_end) ...` for %d nodes", fn.c_str(), index, 2 * N - 1);
-      return RL_EFORMAT;
-    }
-    return RL_OK;
   }
 };
 
@@ -452,7 +350,7 @@ extern "C" int rl_coalrate_anc(const char *anc_path, const char *mut_path, const
                                float *out_or_null, int *N_out) {
   if (!anc_path || !mut_path || !epochs || !N_out) return null_args("rl_coalrate_anc");
   if (const int rc = check_epochs("rl_coalrate_anc", epochs, nepochs)) return rc;
-  AncText anc;
+  AncText anc("CoalescentRateForSection");
   int rc = anc.open(anc_path);
   if (rc) return rc;
   if (anc.has_ages) {

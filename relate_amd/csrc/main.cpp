@@ -23,6 +23,12 @@
 //           and sample ages are refused)
 //   Relate --mode FinalizePopulationSize -o out [--poplabels f]
 //          (RelateCoalescentRate --mode FinalizePopulationSize: out.bin -> out.coal; --poplabels hap is refused)
+//   Relate --mode Frequency -i prefix -o out [--bins lower,upper,step] [--years_per_gen g] [--device d]
+//          (RelateSelection --mode Frequency of the reference: reads prefix.anc (text) and prefix.mut, writes out.freq
+//           and out.lin, the reference's bytes; --device -1: on the host; .gz inputs, sample ages and a .mut with
+//           population-frequency columns are refused; no --first_snp / --last_snp)
+//   Relate --mode Selection -i prefix -o out
+//          (RelateSelection --mode Selection: prefix.freq + prefix.lin -> out.sele, on the host)
 // Same options, files and stderr banners as include/pipeline/Relate.cpp:19-115,
 // Paint.cpp, BuildTopology.cpp of the reference; every other --mode is refused
 // (use the reference binary for them).  Extra options: --device n,
@@ -56,7 +62,7 @@ static void usage_line() {
   std::cerr << "---------------------------------------------------------" << std::endl << std::endl;
 }
 
-static const char *kModes = "MakeChunks|Paint|BuildTopology|PaintBuildTopology|FindEquivalentBranches|OptimizeParameters|CompareTopology|PairwiseCoalescence|CopyingMatrix|CoalescentRateForSection|FinalizePopulationSize";
+static const char *kModes = "MakeChunks|Paint|BuildTopology|PaintBuildTopology|FindEquivalentBranches|OptimizeParameters|CompareTopology|PairwiseCoalescence|CopyingMatrix|CoalescentRateForSection|FinalizePopulationSize|Frequency|Selection";
 
 // `Relate --mode OptimizeParameters` (pipeline/OptimizeParameters.cpp:22-206): MakeChunks, then for every chunk the
 // grid of (theta, recombination factor) through rl_stage_optimize_parameters, the temporary files removed as the
@@ -411,6 +417,57 @@ static int finalize_population_size(std::map<std::string, std::string> &opt) {
   return 0;
 }
 
+// `Relate --mode Frequency -i prefix -o out [--bins l,u,s] [--years_per_gen g] [--device d]`
+// (evaluate/selection/RelateSelection.cpp:330-814: rl_coalrate_epochs, rl_frequency_anc)
+static int frequency(std::map<std::string, std::string> &opt) {
+  if (!opt.count("input") || !opt.count("output")) {
+    std::cout << "Not enough arguments supplied." << std::endl;
+    std::cout << "Needed: input, output. Optional: years_per_gen, bins, device." << std::endl;
+    return 0;  // (exit(0), :335-345)
+  }
+  std::cerr << "---------------------------------------------------------" << std::endl;
+  std::cerr << "Calculating frequency through time for " << opt["input"] << "." << std::endl;
+  float years_per_gen = 28.0f;
+  try {
+    if (opt.count("years_per_gen")) years_per_gen = std::stof(opt["years_per_gen"]);
+  } catch (...) {
+    std::cerr << "Error: --years_per_gen expects a number" << std::endl;
+    return 1;
+  }
+  std::vector<float> epochs(4096);
+  int E = (int)epochs.size(), host_trees = 0;
+  long long rows = 0;
+  const int device = opt.count("device") ? atoi(opt["device"].c_str()) : 0;
+  const std::string anc = opt["input"] + ".anc", mut = opt["input"] + ".mut", freq = opt["output"] + ".freq", lin = opt["output"] + ".lin";
+  if (rl_coalrate_epochs(years_per_gen, opt.count("bins") ? opt["bins"].c_str() : nullptr, epochs.data(), &E) != 0 ||
+      rl_frequency_anc(anc.c_str(), mut.c_str(), epochs.data(), E, device, freq.c_str(), lin.c_str(), &rows, &host_trees) != 0) {
+    std::cerr << "Error: " << rl_last_error() << std::endl;
+    return 1;
+  }
+  if (device >= 0 && host_trees) std::cerr << host_trees << " trees with tied node times were walked on the host." << std::endl;
+  usage_line();
+  return 0;
+}
+
+// `Relate --mode Selection -i prefix -o out` (RelateSelection.cpp:190-328: rl_selection_files)
+static int selection(std::map<std::string, std::string> &opt) {
+  if (!opt.count("input") || !opt.count("output")) {
+    std::cout << "Not enough arguments supplied." << std::endl;
+    std::cout << "Needed: input, output." << std::endl;
+    std::cout << "Calculating pvalue for selection using output of mode Frequency." << std::endl;
+    return 0;  // (exit(0), :195-205)
+  }
+  std::cerr << "---------------------------------------------------------" << std::endl;
+  std::cerr << "Calculating evidence of selection for " << opt["input"] << "." << std::endl;
+  const std::string sele = opt["output"] + ".sele";
+  if (rl_selection_files(opt["input"].c_str(), sele.c_str()) != 0) {
+    std::cerr << "Error: " << rl_last_error() << std::endl;
+    return 1;
+  }
+  usage_line();
+  return 0;
+}
+
 int main(int argc, char **argv) {
   // BuildTopology keeps several tree-builder launches and window kernels in flight from its section threads: more
   // hardware queues than HIP's default four (read when the runtime starts; an explicit setting wins) -- but not more
@@ -430,7 +487,8 @@ int main(int argc, char **argv) {
       {"paint_all_windows", false},  // (PaintBuildTopology of a section range: Paint keeps every window, not the range's)
       {"input", true},  // (OptimizeParameters: the grid, Relate.cpp:43)
       {"metric", true},  // (PairwiseCoalescence: size | time)
-      // (CoalescentRateForSection / FinalizePopulationSize, RelateCoalescentRate.cpp:14-34; mask is named to be refused)
+      // (CoalescentRateForSection / FinalizePopulationSize, RelateCoalescentRate.cpp:14-34; mask is named to be refused;
+      //  Frequency / Selection read input, output, bins and years_per_gen of RelateSelection.cpp:1586-1596)
       {"bins", true}, {"years_per_gen", true}, {"poplabels", true}, {"mask", true},
       // accepted and ignored by these two modes in the reference as well
       {"haps", true}, {"sample", true}, {"map", true}, {"mutation_rate", true}, {"effectiveN", true},
@@ -470,11 +528,15 @@ int main(int argc, char **argv) {
     std::cerr << "  CopyingMatrix: --chunk_index c -o out [--first_section a --last_section b] [--painting theta,rho] [--sum_mode m] [--device d]" << std::endl;
     std::cerr << "  CoalescentRateForSection: -i,--input prefix -o out [--bins lower,upper,step] [--years_per_gen g] [--device d]" << std::endl;
     std::cerr << "  FinalizePopulationSize: -o out [--poplabels f]" << std::endl;
+    std::cerr << "  Frequency: -i,--input prefix -o out [--bins lower,upper,step] [--years_per_gen g] [--device d]" << std::endl;
+    std::cerr << "  Selection: -i,--input prefix -o out" << std::endl;
     return opt.count("help") ? 0 : 1;
   }
   const std::string mode = opt["mode"];
   if (mode == "CoalescentRateForSection") return coalescent_rate_for_section(opt);
   if (mode == "FinalizePopulationSize") return finalize_population_size(opt);
+  if (mode == "Frequency") return frequency(opt);
+  if (mode == "Selection") return selection(opt);
   if (mode == "CompareTopology") return compare_topology(opt);
   if (mode == "PairwiseCoalescence") return pairwise_coalescence(opt);
   if (mode == "OptimizeParameters" && opt.count("output") && opt["output"].find('/') != std::string::npos) {
@@ -597,7 +659,7 @@ int main(int argc, char **argv) {
     if (rc == 1) return 1;  // first_section >= num_windows (BuildTopology.cpp:45)
   } else {
     std::cerr << "Mode " << mode << " is not part of this build: it replaces --mode MakeChunks, Paint, BuildTopology, FindEquivalentBranches, "
-              << "OptimizeParameters, CoalescentRateForSection and FinalizePopulationSize only; run the reference Relate for the other stages." << std::endl;
+              << "OptimizeParameters, CoalescentRateForSection, FinalizePopulationSize, Frequency and Selection only; run the reference Relate for the other stages." << std::endl;
     return 1;
   }
   if (rc != 0) {

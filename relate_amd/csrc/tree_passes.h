@@ -163,6 +163,33 @@ __device__ inline void wave_float_times(const unsigned *K, const double *__restr
   }
 }
 
+// TM[i] = time of internal node i as the reference's Tree::GetCoordinates has it (src/anc.cpp:525-537): a float,
+// rounded at every node, t(m) = (float)max((double)t(c2) + bl[c2], (double)t(c1) + bl[c1]) over both children and
+// t(leaf) = 0.  One wavefront calls it.
+__device__ inline void wave_max_times(const unsigned *K, const double *__restrict__ bl, int N, float *TM, int lane) {
+  const int ni = N - 1;
+  const auto leaf = [](int) { return 0.0f; };
+  const auto table = [&](int j) { return TM[j]; };
+  for (int b = 0; b < ni; b += 64) {
+    const int i = b + lane;
+    const bool act = i < ni;
+    int d1 = -1, d2 = -1;
+    float t1 = 0.0f, t2 = 0.0f;
+    double len1 = 0.0, len2 = 0.0;
+    if (act) {
+      const int c1 = first_child(K, i), c2 = second_child(K, i);
+      len1 = bl[c1];
+      len2 = bl[c2];
+      d1 = child_source(c1, N, b, &t1, leaf, table);
+      d2 = child_source(c2, N, b, &t2, leaf, table);
+    }
+    const float t = wave_pull<2>(act, d1, t1, d2, t2, [len1, len2](float a, float c) {
+      return (float)fmax((double)c + len2, (double)a + len1);
+    });
+    if (act) TM[i] = t;
+  }
+}
+
 // U[i] holds the parent (internal numbering) of internal node i on entry and the left end of its interval on return:
 // the first child starts where its parent does, the second after the first child's leaves.  One wavefront calls it;
 // each lane calls visit(i, left end, is a second child, is the root) for its node once U[i] is written.
