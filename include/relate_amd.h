@@ -806,6 +806,56 @@ int rl_frequency_anc(const char *anc_path, const char *mut_path, const float *ep
 int rl_selection_logp(int k, float fk, int N, float fN, float *logp);
 int rl_selection_files(const char *in_prefix, const char *out_path);
 
+/* ------------------------------------------------------------------ AvgMutationRate
+ * The reference's `RelateMutationRate --mode Avg` (include/evaluate/mutation_rate/AvgMutationRate.cpp), the step of
+ * EstimatePopulationSize.sh whose _avg.rate file is the --mrate input of the next branch-length pass.
+ *
+ * The epoch boundaries are DOUBLES here (:373-456): `log_10` and years_per_gen are floats inside double expressions.
+ * Node times are those of Tree::GetCoordinates (src/anc.cpp:525-537), a float at every node, as for Frequency.
+ *
+ * Branch length of a tree per epoch (GetCoordsAndLineages :19-95, GetBranchLengthsInEpoch :228-291).  With t_1 <= ...
+ * <= t_{N-1} the sorted times of the internal nodes and t_0 = 0, the interval (t_{k-1}, t_k] carries n = N - (k-1)
+ * lineages -- leaves sort before internal nodes at time 0, so this holds with tied times and with internal nodes at
+ * 0; an empty interval adds nothing.  A cursor walks the epochs, from epoch 0, over the intervals (a, b] in order:
+ *   b <  ep[c+1]:  out[c] += (double)((float)n * (b - a))                     a float product of a float difference
+ *   b >= ep[c+1]:  out[c] += (double)n * (ep[c+1] - (double)a); c++;
+ *                  while ep[c+1] < b: out[c] = (double)n * (ep[c+1] - ep[c]); c++   whole epochs, assigned
+ *                  out[c] = (double)n * ((double)b - ep[c])                    (b == ep[c+1] leaves the cursor at c)
+ * and the walk ends for good once c == E-1: what lies above the last boundary is dropped and out[E-1] stays 0 (the
+ * reference shrinks its vector to E-1 entries and its caller reads E).  So a time exactly on a boundary decides
+ * whether the next interval is added as a float product or assigned as a double one; both sides restate that.
+ *
+ * Per SNP with exactly one branch, in the .mut's order, flipped or not (:519-586): the mutation is spread over the
+ * epochs that [age_begin, age_end] spans, in proportion; opportunity[e] += out_of_its_tree[e] * count_bases[s], with
+ * count_bases[s] = 0.5*dist[j-1]/1e9 + 0.5*dist[j]/1e9, j the SNP's index in the position list (0.5*dist[0]/1e9 alone
+ * for j = 0; :458-494).  Both are serial double sums on the host.  rate[e] = (mutation[e] / opportunity[e]) / 1e9.
+ *   rl_mutrate_epochs (replaces :373-456): the default 31 boundaries, or those of --bins lower,upper,step.
+ *     *nepochs: room on entry, the count on return.
+ *   rl_mutrate_trees (replaces :58-95 and :228-291): parents, branch_length [ntrees][2N-1]; out [ntrees][E] doubles,
+ *     entry E-1 equal to 0.  device >= 0: on that GPU (relate_amd/csrc/mutrate_kernels.hip; 2 <= N <= 10240, 2 <= E
+ *     <= 64, the trees go up in batches of rl_mutrate_batch_trees(N); every tree is answered there, none comes back;
+ *     RL_ENODEVICE without one -- there is no fallback); device < 0: the reference's walk restated on one host thread
+ *     (relate_amd/csrc/mutrate.cpp), same limits.  RL_EINVAL names the tree: a parent that is not above its child, a
+ *     branch length that is negative or not finite; epochs[0] must be 0 and the boundaries rise.
+ *   rl_mutrate_anc (replaces :296-590 and AncMutIterators::FirstSNP / NextSNP): the trees of a TEXT .anc that have a
+ *     one-branch SNP in the .mut.  dist_path_or_null: the --dist file (one header line, then `pos dist`; it may hold
+ *     more positions than the .mut); NULL: the .mut's own pos and dist columns.  mutation [E], opportunity [E];
+ *     *mapped_snps (may be NULL): SNPs with one branch.  RL_EINVAL: sample ages in the header, .gz inputs (the dist
+ *     file included), tree indices that fall, a .mut position that the dist file does not hold (the reference reads
+ *     past the end), naming the SNP.
+ *   rl_mutrate_write (replaces :967-991): `epoch rate` per line with the precision of operator<<; the last epoch's
+ *     opportunity is 0 and its rate prints as the division leaves it (`-nan`, or `inf`).
+ * Multi-chromosome inputs (--chr, --first_chr, --last_chr), MutationDensity and the per-category modes are not
+ * offered. */
+int rl_mutrate_batch_trees(int N);
+int rl_mutrate_epochs(float years_per_gen, const char *bins_or_null, double *epochs, int *nepochs);
+int rl_mutrate_trees(const int *parents, const double *branch_length, int N, int ntrees, const double *epochs,
+                     int nepochs, int device, double *out);
+int rl_mutrate_anc(const char *anc_path, const char *mut_path, const char *dist_path_or_null, const double *epochs,
+                   int nepochs, int device, double *mutation, double *opportunity, long long *mapped_snps);
+int rl_mutrate_write(const char *path, const double *epochs, int nepochs, const double *mutation,
+                     const double *opportunity);
+
 /* ------------------------------------------------------------------ tools */
 /* Synthetic block-coalescent panel (stand-in for MakeChunks input,
  * SURVEY.md 8d).  seq_chars (L*N) and/or bits (L*row_words) may be NULL. */

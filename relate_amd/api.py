@@ -91,6 +91,12 @@ def lib():
                                          C.POINTER(C.c_int)]
         L.rl_frequency_anc.argtypes = [C.c_char_p, C.c_char_p, C.c_void_p, C.c_int, C.c_int, C.c_char_p, C.c_char_p,
                                        C.POINTER(C.c_longlong), C.POINTER(C.c_int)]
+        L.rl_mutrate_batch_trees.argtypes = [C.c_int]
+        L.rl_mutrate_epochs.argtypes = [C.c_float, C.c_char_p, C.c_void_p, C.POINTER(C.c_int)]
+        L.rl_mutrate_trees.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p]
+        L.rl_mutrate_anc.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p,
+                                     C.c_void_p, C.POINTER(C.c_longlong)]
+        L.rl_mutrate_write.argtypes = [C.c_char_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
         L.rl_selection_logp.argtypes = [C.c_int, C.c_float, C.c_int, C.c_float, C.POINTER(C.c_float)]
         L.rl_selection_files.argtypes = [C.c_char_p, C.c_char_p]
         L.rl_window_copying.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
@@ -999,6 +1005,56 @@ def selection_logp(k, fk, N, fN):
 def selection_files(in_prefix, out_path):
     """rl_selection_files: in_prefix.freq + in_prefix.lin -> out_path (.sele), as `RelateSelection --mode Selection`"""
     _check(lib().rl_selection_files(os.fsencode(in_prefix), os.fsencode(out_path)))
+
+
+def mutrate_batch_trees(N):
+    """trees per batch of the device path of mutrate_trees / mutrate_anc at N leaves"""
+    return lib().rl_mutrate_batch_trees(int(N))
+
+
+def mutrate_epochs(years_per_gen=28.0, bins=None):
+    """rl_mutrate_epochs: the epoch boundaries of `RelateMutationRate --mode Avg` -> [E] float64 (31 by default;
+    bins: "lower,upper,step" in log10 years)"""
+    ep = np.empty(4096, np.float64)
+    E = C.c_int(len(ep))
+    _check(lib().rl_mutrate_epochs(float(years_per_gen), None if bins is None else bins.encode(), _p(ep), C.byref(E)))
+    return ep[:E.value].copy()
+
+
+def mutrate_trees(parents, branch_length, epochs, device=None):
+    """rl_mutrate_trees: the total branch length of every tree in every epoch.  parents, branch_length: [trees][2N-1]
+    (or one tree); epochs: [E] float64, epochs[0] = 0, rising; device: None = the reference's walk on the host, an
+    int = that GPU.  -> [trees][E] float64, entry E-1 equal to 0"""
+    pa = np.ascontiguousarray(np.atleast_2d(parents), dtype=np.int32)
+    bl = np.ascontiguousarray(np.atleast_2d(branch_length), dtype=np.float64)
+    ep = np.ascontiguousarray(epochs, dtype=np.float64)
+    if pa.shape[1] % 2 == 0 or bl.shape != pa.shape or ep.ndim != 1:
+        raise RelateError("mutrate_trees: parents %s, branch lengths %s, epochs %s" % (pa.shape, bl.shape, ep.shape))
+    out = np.zeros((len(pa), len(ep)), np.float64)
+    _check(lib().rl_mutrate_trees(_p(pa), _p(bl), (pa.shape[1] + 1) // 2, len(pa), _p(ep), len(ep),
+                                  -1 if device is None else int(device), _p(out)))
+    return out
+
+
+def mutrate_anc(anc_path, mut_path, epochs, dist_path=None, device=None):
+    """rl_mutrate_anc: the sums of `RelateMutationRate --mode Avg` over the one-branch SNPs of a text .anc and its
+    .mut (dist_path: the --dist file) -> (mutation [E] float64, opportunity [E] float64, mapped SNPs)"""
+    ep = np.ascontiguousarray(epochs, dtype=np.float64)
+    mutation, opportunity, mapped = np.zeros(len(ep)), np.zeros(len(ep)), C.c_longlong(0)
+    _check(lib().rl_mutrate_anc(os.fsencode(anc_path), os.fsencode(mut_path),
+                                None if dist_path is None else os.fsencode(dist_path), _p(ep), len(ep),
+                                -1 if device is None else int(device), _p(mutation), _p(opportunity), C.byref(mapped)))
+    return mutation, opportunity, mapped.value
+
+
+def mutrate_write(path, epochs, mutation, opportunity):
+    """rl_mutrate_write: the _avg.rate file, `epoch rate` per line with rate = (mutation / opportunity) / 1e9"""
+    ep = np.ascontiguousarray(epochs, dtype=np.float64)
+    m = np.ascontiguousarray(mutation, dtype=np.float64)
+    o = np.ascontiguousarray(opportunity, dtype=np.float64)
+    if not ep.shape == m.shape == o.shape or ep.ndim != 1:
+        raise RelateError("mutrate_write: epochs %s, mutation %s, opportunity %s" % (ep.shape, m.shape, o.shape))
+    _check(lib().rl_mutrate_write(os.fsencode(path), _p(ep), len(ep), _p(m), _p(o)))
 
 
 def stage_find_equivalent_branches(out_dir, chunk_index=0):

@@ -29,6 +29,10 @@
 //           population-frequency columns are refused; no --first_snp / --last_snp)
 //   Relate --mode Selection -i prefix -o out
 //          (RelateSelection --mode Selection: prefix.freq + prefix.lin -> out.sele, on the host)
+//   Relate --mode AvgMutationRate -i prefix -o out [--dist file] [--bins lower,upper,step] [--years_per_gen g] [--device d]
+//          (RelateMutationRate --mode Avg of the reference: reads prefix.anc (text) and prefix.mut, writes
+//           out_avg.rate, the reference's bytes; --device -1: on the host; .gz inputs, sample ages and --chr /
+//           --first_chr / --last_chr are refused)
 // Same options, files and stderr banners as include/pipeline/Relate.cpp:19-115,
 // Paint.cpp, BuildTopology.cpp of the reference; every other --mode is refused
 // (use the reference binary for them).  Extra options: --device n,
@@ -62,7 +66,7 @@ static void usage_line() {
   std::cerr << "---------------------------------------------------------" << std::endl << std::endl;
 }
 
-static const char *kModes = "MakeChunks|Paint|BuildTopology|PaintBuildTopology|FindEquivalentBranches|OptimizeParameters|CompareTopology|PairwiseCoalescence|CopyingMatrix|CoalescentRateForSection|FinalizePopulationSize|Frequency|Selection";
+static const char *kModes = "MakeChunks|Paint|BuildTopology|PaintBuildTopology|FindEquivalentBranches|OptimizeParameters|CompareTopology|PairwiseCoalescence|CopyingMatrix|CoalescentRateForSection|FinalizePopulationSize|Frequency|Selection|AvgMutationRate";
 
 // `Relate --mode OptimizeParameters` (pipeline/OptimizeParameters.cpp:22-206): MakeChunks, then for every chunk the
 // grid of (theta, recombination factor) through rl_stage_optimize_parameters, the temporary files removed as the
@@ -468,6 +472,54 @@ static int selection(std::map<std::string, std::string> &opt) {
   return 0;
 }
 
+// `Relate --mode AvgMutationRate -i prefix -o out [--dist file] [--bins l,u,s] [--years_per_gen g] [--device d]`
+// (evaluate/mutation_rate/AvgMutationRate.cpp:830-1013, RelateMutationRate --mode Avg: rl_mutrate_epochs,
+// rl_mutrate_anc, rl_mutrate_write; a summary on stdout in place of the reference's terminal plot)
+static int avg_mutation_rate(std::map<std::string, std::string> &opt) {
+  if (!opt.count("input") || !opt.count("output")) {
+    std::cout << "Not enough arguments supplied." << std::endl;
+    std::cout << "Needed: input, output. Optional: dist, years_per_gen, bins, device." << std::endl;
+    std::cout << "Calculate avg mutation rate through time." << std::endl;
+    return 0;  // (exit(0), :833-842)
+  }
+  for (const char *o : {"chr", "first_chr", "last_chr"})
+    if (opt.count(o)) {
+      std::cerr << "Error: --" << o << " is not part of this build's AvgMutationRate: one chromosome per run; run the reference's RelateMutationRate for it." << std::endl;
+      return 1;
+    }
+  std::cerr << "---------------------------------------------------------" << std::endl;
+  std::cerr << "Calculating average mutation rate for " << opt["input"] << " ..." << std::endl;
+  float years_per_gen = 28.0f;
+  try {
+    if (opt.count("years_per_gen")) years_per_gen = std::stof(opt["years_per_gen"]);
+  } catch (...) {
+    std::cerr << "Error: --years_per_gen expects a number" << std::endl;
+    return 1;
+  }
+  std::vector<double> epochs(4096);
+  int E = (int)epochs.size();
+  long long mapped = 0;
+  const int device = opt.count("device") ? atoi(opt["device"].c_str()) : 0;
+  const std::string anc = opt["input"] + ".anc", mut = opt["input"] + ".mut", rate = opt["output"] + "_avg.rate";
+  if (rl_mutrate_epochs(years_per_gen, opt.count("bins") ? opt["bins"].c_str() : nullptr, epochs.data(), &E) != 0) {
+    std::cerr << "Error: " << rl_last_error() << std::endl;
+    return 1;
+  }
+  std::vector<double> mutation(E), opportunity(E);
+  if (rl_mutrate_anc(anc.c_str(), mut.c_str(), opt.count("dist") ? opt["dist"].c_str() : nullptr, epochs.data(), E, device,
+                     mutation.data(), opportunity.data(), &mapped) != 0 ||
+      rl_mutrate_write(rate.c_str(), epochs.data(), E, mutation.data(), opportunity.data()) != 0) {
+    std::cerr << "Error: " << rl_last_error() << std::endl;
+    return 1;
+  }
+  double mutations = 0.0, chances = 0.0;
+  for (int e = 0; e < E; e++) mutations += mutation[e], chances += opportunity[e];
+  std::cout << mapped << " mapped SNPs, " << E << " epochs, average rate " << (chances > 0.0 ? mutations / chances / 1e9 : 0.0)
+            << " per base per generation; " << rate << " written." << std::endl;
+  usage_line();
+  return 0;
+}
+
 int main(int argc, char **argv) {
   // BuildTopology keeps several tree-builder launches and window kernels in flight from its section threads: more
   // hardware queues than HIP's default four (read when the runtime starts; an explicit setting wins) -- but not more
@@ -490,6 +542,9 @@ int main(int argc, char **argv) {
       // (CoalescentRateForSection / FinalizePopulationSize, RelateCoalescentRate.cpp:14-34; mask is named to be refused;
       //  Frequency / Selection read input, output, bins and years_per_gen of RelateSelection.cpp:1586-1596)
       {"bins", true}, {"years_per_gen", true}, {"poplabels", true}, {"mask", true},
+      // (AvgMutationRate reads input, output, dist, bins and years_per_gen of RelateMutationRate.cpp; the three that
+      //  name several chromosomes are named to be refused)
+      {"chr", true}, {"first_chr", true}, {"last_chr", true},
       // accepted and ignored by these two modes in the reference as well
       {"haps", true}, {"sample", true}, {"map", true}, {"mutation_rate", true}, {"effectiveN", true},
       {"memory", true}, {"dist", true}, {"annot", true}, {"coal", true}, {"transversion", false}};
@@ -530,6 +585,7 @@ int main(int argc, char **argv) {
     std::cerr << "  FinalizePopulationSize: -o out [--poplabels f]" << std::endl;
     std::cerr << "  Frequency: -i,--input prefix -o out [--bins lower,upper,step] [--years_per_gen g] [--device d]" << std::endl;
     std::cerr << "  Selection: -i,--input prefix -o out" << std::endl;
+    std::cerr << "  AvgMutationRate: -i,--input prefix -o out [--dist file] [--bins lower,upper,step] [--years_per_gen g] [--device d]" << std::endl;
     return opt.count("help") ? 0 : 1;
   }
   const std::string mode = opt["mode"];
@@ -537,6 +593,7 @@ int main(int argc, char **argv) {
   if (mode == "FinalizePopulationSize") return finalize_population_size(opt);
   if (mode == "Frequency") return frequency(opt);
   if (mode == "Selection") return selection(opt);
+  if (mode == "AvgMutationRate") return avg_mutation_rate(opt);
   if (mode == "CompareTopology") return compare_topology(opt);
   if (mode == "PairwiseCoalescence") return pairwise_coalescence(opt);
   if (mode == "OptimizeParameters" && opt.count("output") && opt["output"].find('/') != std::string::npos) {
@@ -659,7 +716,7 @@ int main(int argc, char **argv) {
     if (rc == 1) return 1;  // first_section >= num_windows (BuildTopology.cpp:45)
   } else {
     std::cerr << "Mode " << mode << " is not part of this build: it replaces --mode MakeChunks, Paint, BuildTopology, FindEquivalentBranches, "
-              << "OptimizeParameters, CoalescentRateForSection, FinalizePopulationSize, Frequency and Selection only; run the reference Relate for the other stages." << std::endl;
+              << "OptimizeParameters, CoalescentRateForSection, FinalizePopulationSize, Frequency, Selection and AvgMutationRate only; run the reference Relate for the other stages." << std::endl;
     return 1;
   }
   if (rc != 0) {

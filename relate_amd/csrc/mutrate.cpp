@@ -1,0 +1,460 @@
+// mutrate.cpp -- AvgMutationRate, host side (include/relate_amd.h has the definition; the reference:
+// include/evaluate/mutation_rate/AvgMutationRate.cpp).
+//
+// The per-tree quantity is the total branch length in every epoch.  HostLengths restates the reference's two functions
+// operation by operation -- the std::sort of all 2N-1 node times by (time, label), the count of lineages per group of
+// equal times, the serial walk with its epoch cursor and its float and double products -- and is the `device < 0`
+// path and the authority the device (mutrate_kernels.hip) is held to, bit for bit.  This file also holds the readers
+// of the .mut and of the --dist file, count_bases, the loop over the SNPs (two serial double sums, in the .mut's
+// order), the writer of _avg.rate and the C entry points.
+#include <algorithm>
+#include <cfloat>
+#include <chrono>
+#include <cmath>
+#include <cstring>
+#include <fstream>
+#include <numeric>
+#include <sstream>
+#include <string>
+#include <vector>
+
+#include "anc_text.h"
+#include "common.h"
+#include "mutrate.h"
+#include "tree_host.h"
+
+namespace rl {
+
+namespace {
+
+const char *const kMode = "AvgMutationRate";
+
+// one tree's branch length per epoch as the reference computes it
+struct HostLengths : TreeTables {
+  std::vector<float> coords;    // coordinates_tree
+  std::vector<int> order, lin;  // sorted_indices, num_lineages
+  std::vector<int> lin_tmp;
+  explicit HostLengths(int n) : TreeTables(n), coords(nodes), order(nodes), lin(nodes, 0), lin_tmp(nodes) {}
+
+  // parent must have passed first_bad_node, bl first_bad_length.  out: E doubles, out[E-1] = 0
+  void run(const int *parent, const double *bl, const double *epoch, int E, double *out) {
+    fill(parent);
+    // Tree::GetCoordinates (src/anc.cpp:525-537): the maximum over both children in double, a float at every node
+    for (int v = 0; v < N; v++) coords[v] = 0.0f;
+    for (int n = N; n < nodes; n++)
+      coords[n] = (float)std::max((double)coords[second[n]] + bl[second[n]], (double)coords[first[n]] + bl[first[n]]);
+    // GetCoordsAndLineages (:58-95)
+    std::iota(order.begin(), order.end(), 0);
+    std::sort(order.begin(), order.end(),
+              [this](int a, int b) { return coords[a] == coords[b] ? a < b : coords[a] < coords[b]; });
+    int num_lins = 0, start = 0;
+    double age = coords[order[0]];
+    for (int i = 0; i < nodes; i++) {
+      if (coords[order[i]] > age) {
+        for (; start != i; start++) lin[order[start]] = num_lins;
+        age = coords[order[start]];
+      }
+      if (order[i] < N) num_lins++;
+      else num_lins--;
+    }
+    // (the group of the root keeps what an earlier tree left: no interval starts there)
+    lin_tmp = lin;
+    for (int i = 0; i < nodes; i++) lin[i] = lin_tmp[order[i]];
+    std::sort(coords.begin(), coords.end());
+    // GetBranchLengthsInEpoch (:228-291); the caller reads E entries of a vector shrunk to E - 1
+    std::fill(out, out + E, 0.0);
+    int ep = 0;
+    for (ep = 0; ep < E; ep++)
+      if (coords[0] < epoch[ep]) break;
+    ep--;
+    out[ep] = 0;
+    for (int i = 1; i < nodes; i++) {
+      if (coords[i] > coords[i - 1]) {
+        if (coords[i] < epoch[ep + 1]) {
+          if (coords[i - 1] >= epoch[ep]) out[ep] += lin[i - 1] * (coords[i] - coords[i - 1]);
+          else out[ep] = lin[i - 1] * (coords[i] - epoch[ep]);
+        } else {
+          if (coords[i - 1] >= epoch[ep]) out[ep] += lin[i - 1] * (epoch[ep + 1] - coords[i - 1]);
+          else out[ep] = lin[i - 1] * (epoch[ep + 1] - epoch[ep]);  // (the reference asserts it never gets here)
+          ep++;
+          if (ep == E - 1) break;
+          while (ep < E - 1 && epoch[ep + 1] < coords[i]) {  // (the reference tests ep second, reading epoch[E])
+            out[ep] = lin[i - 1] * (epoch[ep + 1] - epoch[ep]);
+            ep++;
+          }
+          if (ep < E - 1) out[ep] = lin[i - 1] * (coords[i] - epoch[ep]);
+          else break;
+        }
+      }
+    }
+  }
+};
+
+int check_epochs(const char *who, const double *ep, int E) {
+  if (E < 2 || E > kMutrateMaxEpochs) {
+    set_error("%s: 2 <= epochs <= %d (%d given)", who, kMutrateMaxEpochs, E);
+    return RL_EINVAL;
+  }
+  if (ep[0] != 0.0) {
+    set_error("%s: the first epoch boundary is %g, not 0", who, ep[0]);
+    return RL_EINVAL;
+  }
+  for (int e = 1; e < E; e++)
+    if (!(ep[e] > ep[e - 1] && ep[e] <= DBL_MAX)) {
+      set_error("%s: epoch boundary %d (%g) is not finite and above boundary %d (%g)", who, e, ep[e], e - 1, ep[e - 1]);
+      return RL_EINVAL;
+    }
+  return RL_OK;
+}
+
+// 0, or the first node whose branch length is negative or not finite + 1 (the root's is not read)
+int first_bad_length(const double *bl, int N) {
+  for (int v = 0; v < 2 * N - 2; v++)
+    if (!(bl[v] >= 0.0 && bl[v] <= DBL_MAX)) return v + 1;
+  return 0;
+}
+
+// out [ntrees][E].  `where` names the trees' origin in a message; tree_id (or null: the index) what a tree is called
+int mutrate_rows(const int *parents, const double *bl, int N, int ntrees, const double *ep, int E, int device, double *out,
+                 const char *where, const int *tree_id) {
+  if (N < 2 || N > kMutrateMaxN) {
+    set_error("%s: trees of 2 <= N <= %d leaves (N=%d)", where, kMutrateMaxN, N);
+    return RL_EINVAL;
+  }
+  const size_t nodes = (size_t)2 * N - 1;
+  const auto tree_name = [&](int t) { return std::string(where) + ": tree " + std::to_string(tree_id ? tree_id[t] : t); };
+  std::vector<int> flags((size_t)ntrees, kMutrateTreeRefused);
+  if (device >= 0) {
+    if (const int rc = mutrate_device(parents, bl, N, ntrees, ep, E, device, out, flags.data())) return rc;
+    if (std::count(flags.begin(), flags.end(), (int)kMutrateTreeDone) == ntrees) return RL_OK;
+  }
+  HostLengths host(N);
+  std::vector<unsigned char> kids;
+  for (int t = 0; t < ntrees; t++) {
+    if (flags[t] == kMutrateTreeDone) continue;
+    const int *parent = parents + t * nodes;
+    const double *b = bl + t * nodes;
+    if (first_bad_node(parent, N, kids)) return refuse_tree(tree_name(t).c_str(), parent, N);
+    if (const int v = first_bad_length(b, N)) {
+      set_error("%s: branch length %g of node %d is negative or not finite", tree_name(t).c_str(), b[v - 1], v - 1);
+      return RL_EINVAL;
+    }
+    if (device >= 0) return refuse_tree(tree_name(t).c_str(), parent, N);  // (refused by the device and not by the host)
+    host.run(parent, b, ep, E, out + (size_t)t * E);
+  }
+  return RL_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ the file layer
+
+// what AvgMutationRate reads of a SNP (Mutations::Read, src/mutations.cpp:229-430)
+struct MutSnp {
+  int pos = 0, dist = 0, tree = 0, branches = 0;
+  float age_begin = 0.0f, age_end = 0.0f;
+};
+
+// `snp;pos;dist;rs_id;tree;branches;is_not_mapping;is_flipped;age_begin;age_end;...`
+int read_mut(const std::string &fn, std::vector<MutSnp> &snps) {
+  std::ifstream is;
+  if (const int rc = open_text(kMode, fn, is)) return rc;
+  std::string line;
+  getline(is, line);  // the header
+  long long n = 1;
+  std::vector<std::string> col;
+  while (getline(is, line)) {
+    n++;
+    if (line.empty()) continue;
+    col.assign(1, std::string());
+    for (char c : line) {
+      if (c == ';') col.emplace_back();
+      else col.back() += c;
+    }
+    MutSnp m;
+    bool ok = col.size() >= 10 && parse_int(col[1], &m.pos) && parse_int(col[2], &m.dist) && parse_int(col[4], &m.tree);
+    if (ok) {
+      char *end = nullptr;
+      m.age_begin = (float)strtod(col[8].c_str(), &end);  // (std::stod into a float)
+      ok = end != col[8].c_str();
+      m.age_end = (float)strtod(col[9].c_str(), &end);
+      ok = ok && end != col[9].c_str();
+      std::istringstream br(col[5]);
+      for (std::string b; ok && br >> b;) {
+        int v = 0;
+        ok = parse_int(b, &v);
+        m.branches++;
+      }
+    }
+    if (!ok) {
+      set_error("%s: %s: line %lld is not `snp;pos;dist;rs_id;tree;branches;is_not_mapping;is_flipped;age_begin;age_end;...`", kMode, fn.c_str(), n);
+      return RL_EFORMAT;
+    }
+    if (!snps.empty() && m.tree < snps.back().tree) {
+      set_error("%s: %s: line %lld: tree index %d after %d: the tree indices must not fall", kMode, fn.c_str(), n, m.tree, snps.back().tree);
+      return RL_EINVAL;
+    }
+    snps.push_back(m);
+  }
+  if (snps.empty()) {
+    set_error("%s: %s holds no SNP", kMode, fn.c_str());
+    return RL_EFORMAT;
+  }
+  return RL_OK;
+}
+
+// the --dist file (:326-357): one header line, then `pos dist` per line (sscanf "%d %d")
+int read_dist(const std::string &fn, std::vector<int> &pos, std::vector<int> &dist) {
+  std::ifstream is;
+  if (const int rc = open_text(kMode, fn, is)) return rc;
+  std::string line;
+  getline(is, line);
+  long long n = 1;
+  while (getline(is, line)) {
+    n++;
+    int p = 0, d = 0;
+    if (sscanf(line.c_str(), "%d %d", &p, &d) != 2) {
+      set_error("%s: %s: line %lld is not `pos dist`", kMode, fn.c_str(), n);
+      return RL_EFORMAT;
+    }
+    pos.push_back(p);
+    dist.push_back(d);
+  }
+  if (pos.empty()) {
+    set_error("%s: %s holds no position", kMode, fn.c_str());
+    return RL_EFORMAT;
+  }
+  return RL_OK;
+}
+
+// :458-494: the scan of the position list for the .mut's positions, in order
+int count_bases_of(const std::vector<MutSnp> &mut, const std::vector<int> &pos, const std::vector<int> &dist,
+                   const char *list_name, std::vector<double> &count_bases) {
+  const double total_num_bases = 1e9;
+  const size_t L = mut.size(), M = pos.size();
+  count_bases.assign(L, 0.0);
+  size_t s = 0, j = 0;
+  if (mut[0].pos == pos[0]) {
+    count_bases[0] = 0.5 * dist[0] / total_num_bases;
+    s++;
+  }
+  for (j = 1; s < L; j++) {
+    if (j >= M) {
+      set_error("%s: SNP %zu of the .mut (position %d) is not in %s: the reference reads past the end of its list", kMode, s,
+                mut[s].pos, list_name);
+      return RL_EINVAL;
+    }
+    if (mut[s].pos == pos[j]) {
+      count_bases[s] = 0.5 * dist[j - 1] / total_num_bases;
+      count_bases[s] += 0.5 * dist[j] / total_num_bases;
+      s++;
+    }
+  }
+  return RL_OK;
+}
+
+int null_args(const char *who) {
+  set_error("%s: bad arguments (no null pointers)", who);
+  return RL_EINVAL;
+}
+
+}  // namespace
+}  // namespace rl
+
+using namespace rl;
+
+extern "C" int rl_mutrate_batch_trees(int N) { return N < 2 ? 0 : mutrate_batch_trees(N); }
+
+extern "C" int rl_mutrate_epochs(float years_per_gen, const char *bins_or_null, double *epochs, int *nepochs) {
+  if (!epochs || !nepochs) return null_args("rl_mutrate_epochs");
+  if (!(years_per_gen > 0.0f && years_per_gen <= FLT_MAX)) {
+    set_error("rl_mutrate_epochs: years_per_gen %g is not positive and finite", (double)years_per_gen);
+    return RL_EINVAL;
+  }
+  const int cap = *nepochs;
+  std::vector<double> ep;
+  const float log_10 = std::log(10);
+  if (bins_or_null) {  // :382-443
+    double v[3];
+    const char *p = bins_or_null;
+    for (int k = 0; k < 3; k++) {
+      char *end = nullptr;
+      v[k] = strtof(p, &end);  // (std::stof)
+      if (end == p || (k < 2 && *end != ',') || (k == 2 && *end != '\0' && *end != ',')) {
+        set_error("rl_mutrate_epochs: bins `%s`: epochs format is wrong. Specify x,y,stepsize.", bins_or_null);
+        return RL_EINVAL;
+      }
+      p = end + 1;
+    }
+    const double lower = v[0], upper = v[1], step = v[2];
+    if (!(step > 0.0) || !(std::fabs(lower) <= 1e30) || !(std::fabs(upper) <= 1e30) || (upper - lower) / step > 1e6) {
+      set_error("rl_mutrate_epochs: bins `%s`: the step must be positive and the range finite", bins_or_null);
+      return RL_EINVAL;
+    }
+    ep.push_back(0.0);
+    for (double boundary = lower; boundary < upper; boundary += step) ep.push_back(std::exp(log_10 * boundary) / years_per_gen);
+    ep.push_back(std::exp(log_10 * upper) / years_per_gen);
+    ep.push_back(std::max(1e8, 10.0 * ep[ep.size() - 1]) / years_per_gen);
+  } else {  // :447-454
+    const int E = 31;
+    ep.resize(E);
+    ep[0] = 0.0;
+    ep[1] = 1e3 / years_per_gen;
+    for (int e = 2; e < E - 1; e++) ep[e] = std::exp(log_10 * (3.0 + 4.0 * (e - 1.0) / (E - 3.0))) / years_per_gen;
+    ep[E - 1] = 1e8 / years_per_gen;
+  }
+  *nepochs = (int)ep.size();
+  if ((int)ep.size() > cap) {
+    set_error("rl_mutrate_epochs: %zu epoch boundaries, room for %d", ep.size(), cap);
+    return RL_EINVAL;
+  }
+  memcpy(epochs, ep.data(), ep.size() * sizeof(double));
+  return RL_OK;
+}
+
+extern "C" int rl_mutrate_trees(const int *parents, const double *branch_length, int N, int ntrees, const double *epochs,
+                                int nepochs, int device, double *out) {
+  if (!parents || !branch_length || !epochs || !out || ntrees < 0) {
+    set_error("rl_mutrate_trees: bad arguments (ntrees=%d; no null pointers)", ntrees);
+    return RL_EINVAL;
+  }
+  if (const int rc = check_epochs("rl_mutrate_trees", epochs, nepochs)) return rc;
+  return mutrate_rows(parents, branch_length, N, ntrees, epochs, nepochs, device, out, "rl_mutrate_trees", nullptr);
+}
+
+extern "C" int rl_mutrate_anc(const char *anc_path, const char *mut_path, const char *dist_path_or_null,
+                              const double *epochs, int nepochs, int device, double *mutation, double *opportunity,
+                              long long *mapped_snps) {
+  if (!anc_path || !mut_path || !epochs || !mutation || !opportunity) return null_args("rl_mutrate_anc");
+  if (const int rc = check_epochs("rl_mutrate_anc", epochs, nepochs)) return rc;
+  const int E = nepochs;
+  AncText anc(kMode);
+  int rc = anc.open(anc_path);
+  if (rc) return rc;
+  if (anc.has_ages) {
+    set_error("%s: %s has sample ages: the coordinates with sample ages are not part of this build", kMode, anc_path);
+    return RL_EINVAL;
+  }
+  const int N = anc.N;
+  if (N > kMutrateMaxN) {
+    set_error("%s: %s: trees of 2 <= N <= %d leaves (N=%d)", kMode, anc_path, kMutrateMaxN, N);
+    return RL_EINVAL;
+  }
+  std::vector<MutSnp> mut;
+  if ((rc = read_mut(mut_path, mut))) return rc;
+  if (mut.back().tree >= anc.trees || mut.front().tree < 0) {
+    set_error("%s: %s names tree %d, %s holds %d", kMode, mut_path, mut.front().tree < 0 ? mut.front().tree : mut.back().tree, anc_path, anc.trees);
+    return RL_EINVAL;
+  }
+  std::vector<int> pos, dist;
+  if (dist_path_or_null) {
+    if ((rc = read_dist(dist_path_or_null, pos, dist))) return rc;
+  } else {
+    for (const MutSnp &m : mut) pos.push_back(m.pos), dist.push_back(m.dist);
+  }
+  std::vector<double> count_bases;
+  if ((rc = count_bases_of(mut, pos, dist, dist_path_or_null ? dist_path_or_null : "its own columns", count_bases))) return rc;
+
+  // the trees with a one-branch SNP go up batch by batch; their E doubles come back and the SNPs of the batch are
+  // added in the .mut's order (:519-586)
+  const size_t nodes = (size_t)2 * N - 1;
+  const int batch = mutrate_batch_trees(N);
+  std::vector<int> parents((size_t)batch * nodes), tree_id, scratch_parent(nodes);
+  std::vector<double> bl((size_t)batch * nodes), scratch_bl(nodes), lengths;
+  std::vector<size_t> snp_id;  // the mapped SNPs of the batch
+  std::vector<int> snp_tree;   // ... and the tree of each, within the batch
+  std::fill(mutation, mutation + E, 0.0);
+  std::fill(opportunity, opportunity + E, 0.0);
+  long long mapped = 0;
+  // RELATE_AMD_TIMING=1: where the wall-clock of the mode goes (reading the text, the trees' lengths, the SNP loop)
+  typedef std::chrono::steady_clock Clock;
+  const auto since = [](Clock::time_point t0) { return std::chrono::duration<double>(Clock::now() - t0).count(); };
+  const Clock::time_point begun = Clock::now();
+  double trees_seconds = 0.0, snps_seconds = 0.0;
+  int trees_done = 0;
+  const auto flush = [&]() -> int {
+    const int held = (int)tree_id.size();
+    if (!held) return RL_OK;
+    lengths.assign((size_t)held * E, 0.0);
+    Clock::time_point t0 = Clock::now();
+    if (const int r = mutrate_rows(parents.data(), bl.data(), N, held, epochs, E, device, lengths.data(), anc_path, tree_id.data()))
+      return r;
+    trees_seconds += since(t0);
+    trees_done += held;
+    t0 = Clock::now();
+    for (size_t i = 0; i < snp_id.size(); i++) {
+      const MutSnp &m = mut[snp_id[i]];
+      const double *in_epoch = &lengths[(size_t)snp_tree[i] * E];
+      int ep = 0;
+      while (epochs[ep] <= m.age_begin) {
+        ep++;
+        if (ep == E) break;
+      }
+      ep--;
+      if (ep < 0) {
+        set_error("%s: %s: SNP %zu has age_begin %g below 0: the reference aborts on this input", kMode, mut_path, snp_id[i], (double)m.age_begin);
+        return RL_EINVAL;
+      }
+      mapped++;
+      const float age_end = m.age_end;
+      const double branch_length = age_end - m.age_begin;  // (a float difference)
+      if (ep < E - 1) {
+        if (age_end <= epochs[ep + 1]) {
+          mutation[ep] += 1.0;
+        } else {
+          mutation[ep] += (epochs[ep + 1] - m.age_begin) / branch_length;
+          ep++;
+          while (ep < E - 1 && epochs[ep + 1] <= age_end) {
+            mutation[ep] += (epochs[ep + 1] - epochs[ep]) / branch_length;
+            ep++;
+          }
+          if (ep + 1 != E) mutation[ep] += (age_end - epochs[ep]) / branch_length;
+        }
+      }
+      for (int e = 0; e < E; e++) opportunity[e] += in_epoch[e] * count_bases[snp_id[i]];
+    }
+    snps_seconds += since(t0);
+    tree_id.clear(), snp_id.clear(), snp_tree.clear();
+    return RL_OK;
+  };
+  size_t k = 0;
+  for (int t = 0; t < anc.trees && k < mut.size(); t++) {
+    bool wanted = false;
+    const size_t k0 = k;
+    for (; k < mut.size() && mut[k].tree == t; k++) wanted |= mut[k].branches == 1;
+    int *parent = wanted ? &parents[tree_id.size() * nodes] : scratch_parent.data();
+    double *b = wanted ? &bl[tree_id.size() * nodes] : scratch_bl.data();
+    if ((rc = anc.next(t, parent, b))) return rc;
+    if (!wanted) continue;
+    for (size_t s = k0; s < k; s++)
+      if (mut[s].branches == 1) snp_id.push_back(s), snp_tree.push_back((int)tree_id.size());
+    tree_id.push_back(t);
+    if ((int)tree_id.size() == batch && (rc = flush())) return rc;
+  }
+  if ((rc = flush())) return rc;
+  if (timing_level() >= 1)
+    fprintf(stderr, "[mutrate] %d trees of N=%d on %s: %.6f s; SNP loop (%lld mapped): %.6f s; reading the text and the rest: %.6f s\n",
+            trees_done, N, device >= 0 ? "the device" : "the host", trees_seconds, mapped, snps_seconds,
+            since(begun) - trees_seconds - snps_seconds);
+  if (mapped_snps) *mapped_snps = mapped;
+  return RL_OK;
+}
+
+extern "C" int rl_mutrate_write(const char *path, const double *epochs, int nepochs, const double *mutation,
+                                const double *opportunity) {
+  if (!path || !epochs || !mutation || !opportunity || nepochs < 0) return null_args("rl_mutrate_write");
+  std::ofstream os(path);
+  if (os.fail()) {
+    set_error("%s: error while opening file %s", kMode, path);
+    return RL_EIO;
+  }
+  const double total_num_bases = 1e9;
+  for (int e = 0; e < nepochs; e++) {
+    const double rate = (mutation[e] / opportunity[e]) / total_num_bases;
+    os << epochs[e] << " " << rate << "\n";
+  }
+  os.close();
+  if (os.fail()) {
+    set_error("%s: writing %s failed", kMode, path);
+    return RL_EIO;
+  }
+  return RL_OK;
+}
