@@ -856,6 +856,54 @@ int rl_mutrate_anc(const char *anc_path, const char *mut_path, const char *dist_
 int rl_mutrate_write(const char *path, const double *epochs, int nepochs, const double *mutation,
                      const double *opportunity);
 
+/* ------------------------------------------------------------------ CoalRateForTree
+ * The reference's `RelateCoalescentRate --mode CoalRateForTree` (CoalescenceRateForTree, include/evaluate/
+ * coalescent_rate/CoalescentRateForSection.cpp:605-858, and coal_tree::populate / coal_tree::Dump(const std::string&),
+ * coal_tree.cpp), the step EstimatePopulationSize.sh runs in every iteration: dated trees in, the .coal file of the
+ * next branch-length pass out.  The boundaries are the doubles of rl_mutrate_epochs (:630-713 is the text of
+ * AvgMutationRate.cpp:373-456).  Node times are those of Tree::GetCoordinates, a float at every node.
+ *
+ * Per tree with `bases` the float of AncMutIterators::NextTree widened to double (coal_tree.cpp:98-199): all 2N-1
+ * node times are sorted by (time, label); num_lins[r] is the lineage count after the group of equal times that holds
+ * rank r.  Ranks 1 .. 2N-2 are walked with an epoch cursor c and lower = ep[0]:
+ *   while coords[r] <= ep[c] (a float against a double):
+ *     an internal node:  num[c-1] += bases / 1e9
+ *     denom[c-1] += bases * n * (n-1) / 2.0 * (coords[r] - lower) / 1e9, n = num_lins[r-1];  lower = coords[r]
+ *   otherwise: denom[c-1] += bases * n * (n-1) / 2.0 * (ep[c] - lower) / 1e9;  lower = ep[c];  c++
+ * every operation in double, left to right; the walk ends at the root or with the boundaries, and entry E-1 of both
+ * vectors stays 0.  The terms go straight onto the accumulators of the current block of block_size trees (1000 in
+ * the reference): one serial sum per block and epoch through the block's trees in order, not a sum per tree.  There
+ * are (int)(ntrees / (double)block_size + 1) blocks; the last may stay empty.
+ * On the device (relate_amd/csrc/coaltree_kernels.hip) the terms come from the sorted times S of the internal nodes
+ * alone -- node k lies in epoch j with ep[j] < S[k] <= ep[j+1], n = N - k, lower = max(S[k-1], ep[j]) -- in one
+ * kernel, and a second adds them in the walk's order; the host twin (coaltree.cpp) is the walk itself.
+ *   rl_coaltree_batch_trees: trees per upload of the device path at N leaves.
+ *   rl_coaltree_num_blocks: the block count of a sequence (coal_tree.cpp:78); 0 for bad arguments.
+ *   rl_coaltree_trees (replaces coal_tree.cpp:98-199): parents, branch_length [ntrees][2N-1], factors [ntrees] (the
+ *     bases, finite and >= 0); num, denom [blocks][E] doubles.  *num_blocks: room in blocks on entry, the count on
+ *     return.  block_size >= 1.  device >= 0: on that GPU (2 <= N <= 10240, 2 <= E <= 64; RL_ENODEVICE without
+ *     one -- there is no fallback); device < 0: the walk on one host thread, same limits.  RL_EINVAL names the tree:
+ *     a parent that is not above its child, a branch length or a factor that is negative or not finite; epochs[0]
+ *     must be 0 and the boundaries rise.
+ *   rl_coaltree_anc (replaces CoalescentRateForSection.cpp:748-770 and coal_tree.cpp:242-297): the trees of a TEXT
+ *     .anc with the factors its .mut gives them as for rl_coalrate_anc, in blocks of 1000, until a factor is
+ *     negative; num, denom [E]: the blocks added in order.  *ntrees (may be NULL): the trees taken.  RL_EINVAL:
+ *     sample ages in the header, .gz inputs.
+ *   rl_coaltree_rates (replaces coal_tree.cpp:309-319): rates[i] = num[i] / denom[i] where denom[i] != 0, otherwise
+ *     the rate before it, or 0 at i = 0.
+ *   rl_coaltree_write (replaces coal_tree.cpp:299-343): `0 `, the boundaries, `0 0 ` and the rates, three lines with
+ *     the precision of operator<<.
+ * Several chromosomes (--chr), --dist and the dead --coal input (is_coal_fail = true, :799) are not offered. */
+int rl_coaltree_batch_trees(int N);
+int rl_coaltree_num_blocks(long long ntrees, int block_size);
+int rl_coaltree_trees(const int *parents, const double *branch_length, const float *factors, int N, int ntrees,
+                      const double *epochs, int nepochs, int block_size, int device, double *num, double *denom,
+                      int *num_blocks);
+int rl_coaltree_anc(const char *anc_path, const char *mut_path, const double *epochs, int nepochs, int device,
+                    double *num, double *denom, int *ntrees);
+int rl_coaltree_rates(const double *num, const double *denom, int nepochs, double *rates);
+int rl_coaltree_write(const char *path, const double *epochs, int nepochs, const double *rates);
+
 /* ------------------------------------------------------------------ tools */
 /* Synthetic block-coalescent panel (stand-in for MakeChunks input,
  * SURVEY.md 8d).  seq_chars (L*N) and/or bits (L*row_words) may be NULL. */

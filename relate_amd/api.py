@@ -97,6 +97,14 @@ def lib():
         L.rl_mutrate_anc.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p,
                                      C.c_void_p, C.POINTER(C.c_longlong)]
         L.rl_mutrate_write.argtypes = [C.c_char_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+        L.rl_coaltree_batch_trees.argtypes = [C.c_int]
+        L.rl_coaltree_num_blocks.argtypes = [C.c_longlong, C.c_int]
+        L.rl_coaltree_trees.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int,
+                                        C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_int)]
+        L.rl_coaltree_anc.argtypes = [C.c_char_p, C.c_char_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                      C.POINTER(C.c_int)]
+        L.rl_coaltree_rates.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+        L.rl_coaltree_write.argtypes = [C.c_char_p, C.c_void_p, C.c_int, C.c_void_p]
         L.rl_selection_logp.argtypes = [C.c_int, C.c_float, C.c_int, C.c_float, C.POINTER(C.c_float)]
         L.rl_selection_files.argtypes = [C.c_char_p, C.c_char_p]
         L.rl_window_copying.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
@@ -1055,6 +1063,69 @@ def mutrate_write(path, epochs, mutation, opportunity):
     if not ep.shape == m.shape == o.shape or ep.ndim != 1:
         raise RelateError("mutrate_write: epochs %s, mutation %s, opportunity %s" % (ep.shape, m.shape, o.shape))
     _check(lib().rl_mutrate_write(os.fsencode(path), _p(ep), len(ep), _p(m), _p(o)))
+
+
+COALTREE_BLOCK_SIZE = 1000  # trees per block in the reference's CoalRateForTree
+
+
+def coaltree_batch_trees(N):
+    """trees per batch of the device path of coaltree_trees / coaltree_anc at N leaves"""
+    return lib().rl_coaltree_batch_trees(int(N))
+
+
+def coaltree_num_blocks(ntrees, block_size=COALTREE_BLOCK_SIZE):
+    """rl_coaltree_num_blocks: (int)(ntrees / block_size + 1), the blocks of a sequence of ntrees trees"""
+    return lib().rl_coaltree_num_blocks(int(ntrees), int(block_size))
+
+
+def coaltree_trees(parents, branch_length, factors, epochs, block_size=COALTREE_BLOCK_SIZE, device=None):
+    """rl_coaltree_trees: the coalescence counts and the pair opportunity of `RelateCoalescentRate --mode
+    CoalRateForTree` per block of block_size trees and epoch.  parents, branch_length: [trees][2N-1] (or one tree);
+    factors: [trees] float32, the bases every tree persists for; epochs: [E] float64, epochs[0] = 0, rising; device:
+    None = the reference's walk on the host, an int = that GPU.  -> (num, denom), each [blocks][E] float64"""
+    pa = np.ascontiguousarray(np.atleast_2d(parents), dtype=np.int32)
+    bl = np.ascontiguousarray(np.atleast_2d(branch_length), dtype=np.float64)
+    f = np.ascontiguousarray(np.atleast_1d(factors), dtype=np.float32)
+    ep = np.ascontiguousarray(epochs, dtype=np.float64)
+    if pa.shape[1] % 2 == 0 or bl.shape != pa.shape or f.shape != (len(pa),) or ep.ndim != 1 or int(block_size) < 1:
+        raise RelateError("coaltree_trees: parents %s, branch lengths %s, factors %s, epochs %s, block size %s"
+                          % (pa.shape, bl.shape, f.shape, ep.shape, block_size))
+    blocks = C.c_int(coaltree_num_blocks(len(pa), block_size))
+    num, denom = np.zeros((blocks.value, len(ep)), np.float64), np.zeros((blocks.value, len(ep)), np.float64)
+    _check(lib().rl_coaltree_trees(_p(pa), _p(bl), _p(f), (pa.shape[1] + 1) // 2, len(pa), _p(ep), len(ep),
+                                   int(block_size), -1 if device is None else int(device), _p(num), _p(denom),
+                                   C.byref(blocks)))
+    return num, denom
+
+
+def coaltree_anc(anc_path, mut_path, epochs, device=None):
+    """rl_coaltree_anc: the trees of a text .anc with the factors of its .mut, in the reference's blocks of 1000,
+    the blocks added in order -> (num [E] float64, denom [E] float64, trees taken)"""
+    ep = np.ascontiguousarray(epochs, dtype=np.float64)
+    num, denom, ntrees = np.zeros(len(ep)), np.zeros(len(ep)), C.c_int(0)
+    _check(lib().rl_coaltree_anc(os.fsencode(anc_path), os.fsencode(mut_path), _p(ep), len(ep),
+                                 -1 if device is None else int(device), _p(num), _p(denom), C.byref(ntrees)))
+    return num, denom, ntrees.value
+
+
+def coaltree_rates(num, denom):
+    """rl_coaltree_rates: num / denom where denom != 0, otherwise the rate before it (0 at the start) -> [E] float64"""
+    n = np.ascontiguousarray(num, dtype=np.float64)
+    d = np.ascontiguousarray(denom, dtype=np.float64)
+    if n.shape != d.shape or n.ndim != 1:
+        raise RelateError("coaltree_rates: num %s, denom %s" % (n.shape, d.shape))
+    rates = np.zeros(len(n), np.float64)
+    _check(lib().rl_coaltree_rates(_p(n), _p(d), len(n), _p(rates)))
+    return rates
+
+
+def coaltree_write(path, epochs, rates):
+    """rl_coaltree_write: the .coal file of CoalRateForTree: `0 `, the boundaries, `0 0 ` and the rates"""
+    ep = np.ascontiguousarray(epochs, dtype=np.float64)
+    r = np.ascontiguousarray(rates, dtype=np.float64)
+    if ep.shape != r.shape or ep.ndim != 1:
+        raise RelateError("coaltree_write: epochs %s, rates %s" % (ep.shape, r.shape))
+    _check(lib().rl_coaltree_write(os.fsencode(path), _p(ep), len(ep), _p(r)))
 
 
 def stage_find_equivalent_branches(out_dir, chunk_index=0):

@@ -25,6 +25,42 @@
 
 namespace rl {
 
+// Mutations::Read (src/mutations.cpp:230-318): `;`-separated, the second column pos, the third dist, the fifth tree
+int read_mut_rows(const char *mode, const std::string &fn, std::vector<MutRow> &rows) {
+  std::ifstream is;
+  if (const int rc = open_text(mode, fn, is)) return rc;
+  std::string line, field;
+  getline(is, line);  // the header
+  long long n = 1;
+  while (getline(is, line)) {
+    n++;
+    if (line.empty()) continue;
+    std::istringstream ls(line);
+    MutRow r{0, 0, 0};
+    bool ok = true;
+    for (int c = 0; c < 5 && ok; c++) {
+      ok = (bool)getline(ls, field, ';');
+      if (ok && c == 1) ok = parse_int(field, &r.pos);
+      if (ok && c == 2) ok = parse_int(field, &r.dist);
+      if (ok && c == 4) ok = parse_int(field, &r.tree);
+    }
+    if (!ok) {
+      set_error("%s: %s: line %lld is not `snp;pos;dist;rs_id;tree;...`", mode, fn.c_str(), n);
+      return RL_EFORMAT;
+    }
+    if (!rows.empty() && r.tree < rows.back().tree) {
+      set_error("%s: %s: line %lld: tree index %d after %d: the tree indices must not fall", mode, fn.c_str(), n, r.tree, rows.back().tree);
+      return RL_EINVAL;
+    }
+    rows.push_back(r);
+  }
+  if (rows.empty()) {
+    set_error("%s: %s holds no SNP", mode, fn.c_str());
+    return RL_EFORMAT;
+  }
+  return RL_OK;
+}
+
 namespace {
 
 // the product is rounded, then the sum: no fused multiply-add (coalrate_kernels.hip does the same)
@@ -158,70 +194,6 @@ struct Coalrate {
 };
 
 // ------------------------------------------------------------------------------------------------ the file layer
-
-struct MutRow {
-  int pos, dist, tree;
-};
-
-// Mutations::Read (src/mutations.cpp:230-318): `;`-separated, the second column pos, the third dist, the fifth tree
-int read_mut(const std::string &fn, std::vector<MutRow> &rows) {
-  std::ifstream is;
-  if (const int rc = open_text("CoalescentRateForSection", fn, is)) return rc;
-  std::string line, field;
-  getline(is, line);  // the header
-  long long n = 1;
-  while (getline(is, line)) {
-    n++;
-    if (line.empty()) continue;
-    std::istringstream ls(line);
-    MutRow r{0, 0, 0};
-    bool ok = true;
-    for (int c = 0; c < 5 && ok; c++) {
-      ok = (bool)getline(ls, field, ';');
-      if (ok && c == 1) ok = parse_int(field, &r.pos);
-      if (ok && c == 2) ok = parse_int(field, &r.dist);
-      if (ok && c == 4) ok = parse_int(field, &r.tree);
-    }
-    if (!ok) {
-      set_error("CoalescentRateForSection: %s: line %lld is not `snp;pos;dist;rs_id;tree;...`", fn.c_str(), n);
-      return RL_EFORMAT;
-    }
-    if (!rows.empty() && r.tree < rows.back().tree) {
-      set_error("CoalescentRateForSection: %s: line %lld: tree index %d after %d: the tree indices must not fall", fn.c_str(), n, r.tree, rows.back().tree);
-      return RL_EINVAL;
-    }
-    rows.push_back(r);
-  }
-  if (rows.empty()) {
-    set_error("CoalescentRateForSection: %s holds no SNP", fn.c_str());
-    return RL_EFORMAT;
-  }
-  return RL_OK;
-}
-
-// AncMutIterators::NextTree, mode 0 (src/mutations.cpp:854-912), with pos and dist the .mut's own (no --dist): the
-// bases tree `tree` persists for -- half the dist before its first SNP, its SNPs' dists, minus half the last --
-// or 0 for a tree without SNPs
-struct Persistence {
-  const std::vector<MutRow> &mut;
-  size_t k = 0;
-  int tree_in_mut;
-  explicit Persistence(const std::vector<MutRow> &m) : mut(m), tree_in_mut(m[0].tree) {}
-  double next(int tree) {
-    if (tree != tree_in_mut) return 0.0;
-    double bases = k != 0 ? mut[k - 1].dist / 2.0 : 0.0;
-    while (tree_in_mut == mut[k].tree) {
-      bases += mut[k].dist;
-      k++;
-      if (k == mut.size()) break;
-    }
-    if (k != mut.size()) {
-      bases -= mut[k - 1].dist / 2.0;
-      tree_in_mut = mut[k].tree;
-    }
-    return bases;
-  }
-};
 
 // Sample::Read (src/sample.cpp:4-110): the group names sorted, and the group of every haplotype -- two haplotypes per
 // line, one if any line's fourth column is `1`
@@ -365,7 +337,7 @@ extern "C" int rl_coalrate_anc(const char *anc_path, const char *mut_path, const
   *N_out = N;
   if (!out_or_null) return RL_OK;
   std::vector<MutRow> mut;
-  if ((rc = read_mut(mut_path, mut))) return rc;
+  if ((rc = read_mut_rows("CoalescentRateForSection", mut_path, mut))) return rc;
   Coalrate cr;
   if ((rc = cr.begin(N, epochs, nepochs, device, out_or_null))) return rc;
   // the loop of CoalescentRateForSection.cpp:441-480: every tree with the bases it persists for -- and, NextTree

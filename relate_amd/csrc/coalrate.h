@@ -1,6 +1,8 @@
 // coalrate.h -- CoalescentRateForSection: what coalrate.cpp (host, files, C ABI) asks of coalrate_kernels.hip (device).
 #pragma once
 #include <cstddef>
+#include <string>
+#include <vector>
 
 namespace rl {
 
@@ -16,6 +18,40 @@ inline int coalrate_batch_trees(int N) {
   const size_t b = kCoalrateBatchBytes / per_tree;
   return b < 1 ? 1 : (b > (1u << 20) ? 1 << 20 : (int)b);
 }
+
+// ---- the .mut as the modes that weigh a tree by the bases it persists for read it (coalrate.cpp; coaltree.cpp:
+// CoalRateForTree)
+struct MutRow {
+  int pos, dist, tree;
+};
+
+// Mutations::Read (src/mutations.cpp:230-318): `;`-separated, the second column pos, the third dist, the fifth tree.
+// `mode` is the name a message starts with (defined in coalrate.cpp)
+int read_mut_rows(const char *mode, const std::string &fn, std::vector<MutRow> &rows);
+
+// AncMutIterators::NextTree, mode 0 (src/mutations.cpp:854-912), with pos and dist the .mut's own (no --dist): the
+// bases tree `tree` persists for -- half the dist before its first SNP, its SNPs' dists, minus half the last --
+// or 0 for a tree without SNPs
+struct Persistence {
+  const std::vector<MutRow> &mut;
+  size_t k = 0;
+  int tree_in_mut;
+  explicit Persistence(const std::vector<MutRow> &m) : mut(m), tree_in_mut(m[0].tree) {}
+  double next(int tree) {
+    if (tree != tree_in_mut) return 0.0;
+    double bases = k != 0 ? mut[k - 1].dist / 2.0 : 0.0;
+    while (tree_in_mut == mut[k].tree) {
+      bases += mut[k].dist;
+      k++;
+      if (k == mut.size()) break;
+    }
+    if (k != mut.size()) {
+      bases -= mut[k - 1].dist / 2.0;
+      tree_in_mut = mut[k].tree;
+    }
+    return bases;
+  }
+};
 
 struct CoalrateDevice;  // D on the device and the staging room of one batch of trees
 

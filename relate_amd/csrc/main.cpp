@@ -30,6 +30,7 @@
 //   Relate --mode Selection -i prefix -o out
 //          (RelateSelection --mode Selection: prefix.freq + prefix.lin -> out.sele, on the host)
 //   Relate --mode AvgMutationRate -i prefix -o out [--dist file] [--bins lower,upper,step] [--years_per_gen g] [--device d]
+//   Relate --mode CoalRateForTree -i prefix -o out [--bins lower,upper,step] [--years_per_gen g] [--device d]
 //          (RelateMutationRate --mode Avg of the reference: reads prefix.anc (text) and prefix.mut, writes
 //           out_avg.rate, the reference's bytes; --device -1: on the host; .gz inputs, sample ages and --chr /
 //           --first_chr / --last_chr are refused)
@@ -66,7 +67,7 @@ static void usage_line() {
   std::cerr << "---------------------------------------------------------" << std::endl << std::endl;
 }
 
-static const char *kModes = "MakeChunks|Paint|BuildTopology|PaintBuildTopology|FindEquivalentBranches|OptimizeParameters|CompareTopology|PairwiseCoalescence|CopyingMatrix|CoalescentRateForSection|FinalizePopulationSize|Frequency|Selection|AvgMutationRate";
+static const char *kModes = "MakeChunks|Paint|BuildTopology|PaintBuildTopology|FindEquivalentBranches|OptimizeParameters|CompareTopology|PairwiseCoalescence|CopyingMatrix|CoalescentRateForSection|FinalizePopulationSize|Frequency|Selection|AvgMutationRate|CoalRateForTree";
 
 // `Relate --mode OptimizeParameters` (pipeline/OptimizeParameters.cpp:22-206): MakeChunks, then for every chunk the
 // grid of (theta, recombination factor) through rl_stage_optimize_parameters, the temporary files removed as the
@@ -520,6 +521,54 @@ static int avg_mutation_rate(std::map<std::string, std::string> &opt) {
   return 0;
 }
 
+// `Relate --mode CoalRateForTree -i prefix -o out [--bins l,u,s] [--years_per_gen g] [--device d]`
+// (CoalescenceRateForTree, evaluate/coalescent_rate/CoalescentRateForSection.cpp:605-858, RelateCoalescentRate --mode
+// CoalRateForTree: rl_mutrate_epochs -- :630-713 is the text of AvgMutationRate.cpp:373-456 --, rl_coaltree_anc,
+// rl_coaltree_rates, rl_coaltree_write; a summary on stdout)
+static int coal_rate_for_tree(std::map<std::string, std::string> &opt) {
+  if (!opt.count("input") || !opt.count("output")) {
+    std::cout << "Not enough arguments supplied." << std::endl;
+    std::cout << "Needed: input, output. Optional: years_per_gen, bins, device." << std::endl;
+    std::cout << "Calculate coalescence rates for sample." << std::endl;
+    return 0;  // (exit(0), :611-620)
+  }
+  for (const char *o : {"dist", "chr"})
+    if (opt.count(o)) {
+      std::cerr << "Error: --" << o << " is not part of this build's CoalRateForTree: one chromosome per run with the .mut's own distances; run the reference's RelateCoalescentRate for it." << std::endl;
+      return 1;
+    }
+  std::cerr << "---------------------------------------------------------" << std::endl;
+  std::cerr << "Calculating coalescence rates for " << opt["input"] << "..." << std::endl;
+  float years_per_gen = 28.0f;
+  try {
+    if (opt.count("years_per_gen")) years_per_gen = std::stof(opt["years_per_gen"]);
+  } catch (...) {
+    std::cerr << "Error: --years_per_gen expects a number" << std::endl;
+    return 1;
+  }
+  std::vector<double> epochs(4096);
+  int E = (int)epochs.size(), ntrees = 0;
+  const int device = opt.count("device") ? atoi(opt["device"].c_str()) : 0;
+  const std::string anc = opt["input"] + ".anc", mut = opt["input"] + ".mut", coal = opt["output"] + ".coal";
+  if (rl_mutrate_epochs(years_per_gen, opt.count("bins") ? opt["bins"].c_str() : nullptr, epochs.data(), &E) != 0) {
+    std::cerr << "Error: " << rl_last_error() << std::endl;
+    return 1;
+  }
+  std::vector<double> num(E), denom(E), rates(E);
+  if (rl_coaltree_anc(anc.c_str(), mut.c_str(), epochs.data(), E, device, num.data(), denom.data(), &ntrees) != 0 ||
+      rl_coaltree_rates(num.data(), denom.data(), E, rates.data()) != 0 ||
+      rl_coaltree_write(coal.c_str(), epochs.data(), E, rates.data()) != 0) {
+    std::cerr << "Error: " << rl_last_error() << std::endl;
+    return 1;
+  }
+  int with_rate = 0;
+  for (int e = 0; e < E; e++) with_rate += denom[e] != 0;
+  std::cout << ntrees << " trees in " << rl_coaltree_num_blocks(ntrees, 1000) << " blocks of 1000, " << with_rate << " of " << E
+            << " epochs with a rate of their own; " << coal << " written." << std::endl;
+  usage_line();
+  return 0;
+}
+
 int main(int argc, char **argv) {
   // BuildTopology keeps several tree-builder launches and window kernels in flight from its section threads: more
   // hardware queues than HIP's default four (read when the runtime starts; an explicit setting wins) -- but not more
@@ -543,7 +592,8 @@ int main(int argc, char **argv) {
       //  Frequency / Selection read input, output, bins and years_per_gen of RelateSelection.cpp:1586-1596)
       {"bins", true}, {"years_per_gen", true}, {"poplabels", true}, {"mask", true},
       // (AvgMutationRate reads input, output, dist, bins and years_per_gen of RelateMutationRate.cpp; the three that
-      //  name several chromosomes are named to be refused)
+      //  name several chromosomes are named to be refused; CoalRateForTree reads input, output, bins and years_per_gen
+      //  of RelateCoalescentRate.cpp and refuses dist and chr)
       {"chr", true}, {"first_chr", true}, {"last_chr", true},
       // accepted and ignored by these two modes in the reference as well
       {"haps", true}, {"sample", true}, {"map", true}, {"mutation_rate", true}, {"effectiveN", true},
@@ -586,6 +636,7 @@ int main(int argc, char **argv) {
     std::cerr << "  Frequency: -i,--input prefix -o out [--bins lower,upper,step] [--years_per_gen g] [--device d]" << std::endl;
     std::cerr << "  Selection: -i,--input prefix -o out" << std::endl;
     std::cerr << "  AvgMutationRate: -i,--input prefix -o out [--dist file] [--bins lower,upper,step] [--years_per_gen g] [--device d]" << std::endl;
+    std::cerr << "  CoalRateForTree: -i,--input prefix -o out [--bins lower,upper,step] [--years_per_gen g] [--device d]" << std::endl;
     return opt.count("help") ? 0 : 1;
   }
   const std::string mode = opt["mode"];
@@ -594,6 +645,7 @@ int main(int argc, char **argv) {
   if (mode == "Frequency") return frequency(opt);
   if (mode == "Selection") return selection(opt);
   if (mode == "AvgMutationRate") return avg_mutation_rate(opt);
+  if (mode == "CoalRateForTree") return coal_rate_for_tree(opt);
   if (mode == "CompareTopology") return compare_topology(opt);
   if (mode == "PairwiseCoalescence") return pairwise_coalescence(opt);
   if (mode == "OptimizeParameters" && opt.count("output") && opt["output"].find('/') != std::string::npos) {
@@ -716,7 +768,7 @@ int main(int argc, char **argv) {
     if (rc == 1) return 1;  // first_section >= num_windows (BuildTopology.cpp:45)
   } else {
     std::cerr << "Mode " << mode << " is not part of this build: it replaces --mode MakeChunks, Paint, BuildTopology, FindEquivalentBranches, "
-              << "OptimizeParameters, CoalescentRateForSection, FinalizePopulationSize, Frequency, Selection and AvgMutationRate only; run the reference Relate for the other stages." << std::endl;
+              << "OptimizeParameters, CoalescentRateForSection, FinalizePopulationSize, Frequency, Selection, AvgMutationRate and CoalRateForTree only; run the reference Relate for the other stages." << std::endl;
     return 1;
   }
   if (rc != 0) {

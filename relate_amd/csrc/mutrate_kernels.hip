@@ -5,10 +5,8 @@
 // mutrate_kernel, one workgroup per tree of a batch:
 //   1. the passes of tree_passes.h: kids with the validity checks, the branch-length sanity check, then wavefront 0
 //      takes the times of Tree::GetCoordinates (wave_max_times);
-//   2. the N-1 internal times sorted ascending IN PLACE: a bitonic network whose comparators all point the same way
-//      (the first step of a merge of width k pairs i with i ^ (k-1), the others i with i ^ j), so the slots from N-1
-//      to the next power of two stand for +infinity without existing -- a comparator that reaches one is skipped.
-//      Only values move: no labels, no ranks;
+//   2. the N-1 internal times sorted ascending IN PLACE by a bitonic network that moves values only: no labels, no
+//      ranks (1 and 2 are sorted_max_times of tree_passes.h, which coaltree_kernels.hip begins with too);
 //   3. one lane of wavefront 0 per epoch e.  With S the sorted times and S[-1] = 0, interval k is (S[k-1], S[k]] and
 //      carries N - k lineages; an empty interval adds +0.  The lane finds by binary search the first k1 with S[k1] >
 //      ep[e] and the first k2 with S[k2] >= ep[e+1], forms the term of interval k1 -- assigned as a double product
@@ -45,44 +43,16 @@ __global__ void __launch_bounds__(T) mutrate_kernel(const int *__restrict__ PAR,
   const int t = blockIdx.x;
   if (t >= ntrees) return;
   const int nodes = 2 * N - 1, ni = N - 1, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  int P = 1;
-  while (P < ni) P <<= 1;
   const int *par = PAR + (size_t)t * nodes;
   const double *bl = BL + (size_t)t * nodes;
   unsigned *K = reinterpret_cast<unsigned *>(lds);              // [ni] kids
   float *S = reinterpret_cast<float *>(lds + (size_t)4 * ni);   // [ni] times, sorted ascending after step 2
 
   if (tid < E) ep[tid] = EP[tid];
-  if (!build_kids<T>(par, N, K, nullptr, &bad)) {
+  if (!sorted_max_times<T>(par, bl, N, K, S, &bad)) {  // steps 1 and 2
     if (tid == 0) FLAG[t] = kMutrateTreeRefused;
     return;
   }
-  __syncthreads();  // (every thread has read build_kids' verdict)
-  for (int v = tid; v < nodes - 1; v += T)
-    if (!(bl[v] >= 0.0 && bl[v] <= DBL_MAX)) bad = 1;  // negative, infinite or NaN: the times would not rise
-  __syncthreads();
-  if (bad) {
-    if (tid == 0) FLAG[t] = kMutrateTreeRefused;
-    return;
-  }
-  if (wave == 0) wave_max_times(K, bl, N, S, lane);
-  __syncthreads();
-
-  for (int k = 2; k <= P; k <<= 1)
-    for (int j = k >> 1; j > 0; j >>= 1) {
-      const int flip = j == (k >> 1) ? k - 1 : j;
-      for (int i = tid; i < P; i += T) {
-        const int l = i ^ flip;
-        if (l > i && l < ni) {  // (l >= ni: +infinity, in its place already)
-          const float a = S[i], b = S[l];
-          if (a > b) {
-            S[i] = b;
-            S[l] = a;
-          }
-        }
-      }
-      __syncthreads();
-    }
   if (wave != 0 || lane >= E) return;
 
   // ---- one lane per epoch

@@ -6,13 +6,17 @@
 //   wave_pull       one wavefront: the scan every pass below and in the kernels is an instance of;
 //   wave_clade_sizes   one wavefront: leaves below every internal node, label order;
 //   wave_float_times   one wavefront: the float time of every internal node, rounded at every node, label order;
-//   wave_left_ends     one wavefront: left end of every internal node's interval of depth-first ranks, falling order.
+//   wave_left_ends     one wavefront: left end of every internal node's interval of depth-first ranks, falling order;
+//   wave_max_times     one wavefront: the float time of every internal node as Tree::GetCoordinates has it;
+//   sorted_max_times   all threads: the checks, wave_max_times and the in-place sort of those times.
 // The wave passes take the internal nodes 64 at a time; a lane PULLS what it depends on -- from LDS for a node of
 // another 64, by lane shuffle for a node of its own 64 once that lane is done.  A round costs a ballot and a shuffle
 // per dependency and value word, no LDS traffic: a caterpillar, whose every node waits for the one before it, takes
 // N-1 such rounds per pass, O(N) in all -- there is no walk from a leaf to the root anywhere.
 #pragma once
 #include <hip/hip_runtime.h>
+
+#include <cfloat>
 
 namespace rl {
 
@@ -188,6 +192,48 @@ __device__ inline void wave_max_times(const unsigned *K, const double *__restric
     });
     if (act) TM[i] = t;
   }
+}
+
+// The prologue of the kernels that consume a tree as its sorted node times (mutrate_kernels.hip: AvgMutationRate;
+// coaltree_kernels.hip: CoalRateForTree).  All threads of the workgroup call it; K and S are ni words of LDS each.
+//   1. build_kids with its checks, then the branch-length check (negative, infinite or NaN: the times would not rise);
+//   2. wavefront 0 takes the times of Tree::GetCoordinates (wave_max_times);
+//   3. the N-1 internal times sorted ascending IN PLACE: a bitonic network whose comparators all point the same way
+//      (the first step of a merge of width k pairs i with i ^ (k-1), the others i with i ^ j), so the slots from N-1
+//      to the next power of two stand for +infinity without existing -- a comparator that reaches one is skipped.
+//      Only values move: no labels, no ranks.
+// Returns false to all threads for a refused tree; otherwise it ends at the __syncthreads() after the sort, with S
+// the sorted times: interval k, (S[k-1], S[k]] with S[-1] = 0, carries N - k lineages.
+template <int T>
+__device__ bool sorted_max_times(const int *__restrict__ par, const double *__restrict__ bl, int N, unsigned *K,
+                                 float *S, int *bad) {
+  const int nodes = 2 * N - 1, ni = N - 1, tid = threadIdx.x;
+  int P = 1;
+  while (P < ni) P <<= 1;
+  if (!build_kids<T>(par, N, K, nullptr, bad)) return false;
+  __syncthreads();  // (every thread has read build_kids' verdict)
+  for (int v = tid; v < nodes - 1; v += T)
+    if (!(bl[v] >= 0.0 && bl[v] <= DBL_MAX)) *bad = 1;
+  __syncthreads();
+  if (*bad) return false;
+  if ((tid >> 6) == 0) wave_max_times(K, bl, N, S, tid & 63);
+  __syncthreads();
+  for (int k = 2; k <= P; k <<= 1)
+    for (int j = k >> 1; j > 0; j >>= 1) {
+      const int flip = j == (k >> 1) ? k - 1 : j;
+      for (int i = tid; i < P; i += T) {
+        const int l = i ^ flip;
+        if (l > i && l < ni) {  // (l >= ni: +infinity, in its place already)
+          const float a = S[i], b = S[l];
+          if (a > b) {
+            S[i] = b;
+            S[l] = a;
+          }
+        }
+      }
+      __syncthreads();
+    }
+  return true;
 }
 
 // U[i] holds the parent (internal numbering) of internal node i on entry and the left end of its interval on return:
