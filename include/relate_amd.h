@@ -904,6 +904,62 @@ int rl_coaltree_anc(const char *anc_path, const char *mut_path, const double *ep
 int rl_coaltree_rates(const double *num, const double *denom, int nepochs, double *rates);
 int rl_coaltree_write(const char *path, const double *epochs, int nepochs, const double *rates);
 
+/* ------------------------------------------------------------------ SubTreesForSubpopulation
+ * The reference's `RelateExtract --mode SubTreesForSubpopulation` (include/extract/
+ * CreateAncesTreeFileForSubpopulation.cpp), the step that opens EstimatePopulationSize.sh under --pop_of_interest: a
+ * dated tree sequence in, the sequence of its subtrees for the haplotypes of some groups out, as a text .anc / .mut
+ * and a .poplabels that the other modes read.
+ *
+ * Per tree (Tree::GetSubTree, src/anc.cpp:655-738) with the subset's M leaves in rising label order:
+ * number_in_subpop[v] is the number of subset leaves below v.  Subset leaf k becomes node k; the internal nodes are
+ * taken in rising label order: one both of whose children have subset leaves below them is KEPT, takes the next free
+ * label M, M+1, ... and its own branch length; one with exactly one such child is contracted -- it converts to what
+ * that child converts to, and its branch length is added (a double addition) onto that subtree node; any other node
+ * converts to -1.  The ancestors above the topmost kept node end in the subtree root's branch length.  M = N is the
+ * identity.  The times are those of Tree::GetCoordinates (:525-565) ON THE SUBTREE, a float at every node:
+ * t(m) = (float)max((double)t(c2) + bl[c2], (double)t(c1) + bl[c1]), t(leaf) = 0.
+ * On the device (relate_amd/csrc/subtrees_kernels.hip) a workgroup takes a tree: the counts are one pull scan, the
+ * new labels an exclusive scan of the keep flags, and every subset leaf and kept node walks its own chain of
+ * contracted ancestors; the host twin (subtrees.cpp) is the reference's loop.
+ *   rl_subtrees_batch_trees: trees per upload of the device path at N leaves.
+ *   rl_subtrees_trees (replaces src/anc.cpp:655-738 and :525-565): parents, branch_length [ntrees][2N-1]; subset [M]
+ *     leaf labels, rising; out: sub_parent, sub_bl, sub_time [ntrees][2M-1], convert_index, number_in_subpop
+ *     [ntrees][2N-1].  device >= 0: on that GPU (RL_ENODEVICE without one -- there is no fallback); device < 0: the
+ *     reference's loop on one host thread.  2 <= N <= 10240, 2 <= M <= N on both.  RL_EINVAL names the tree: a
+ *     parent that is not above its child, a branch length (the root's included) that is negative or not finite; a
+ *     subset label out of range or not above the one before it.
+ *   rl_subtrees_poplabels (replaces Sample::Read and Sample::AssignPopOfInterest, src/sample.cpp:4-171): the group of
+ *     every haplotype (a diploid file counts every line twice, one with ploidy 1 once, a mix is RL_EINVAL), the group
+ *     names sorted and joined with '\n', and, if pops is not NULL, a flag per group: named in pops (comma separated,
+ *     duplicates ignored, `All`; an unknown name is RL_EINVAL).  *num_haplotypes, *num_groups, *names_bytes: room on
+ *     entry, the counts on return; an array without room (or NULL) is not filled.
+ *   rl_subtrees_files (replaces CreateAncesTreeFileForSubpopulation.cpp:17-401): a TEXT .anc and its .mut, a
+ *     .poplabels and the groups of interest in; <out>.anc, <out>.mut and <out>.poplabels out, the reference's bytes:
+ *     the SNPs with one branch that converts to a subtree node other than the root are kept (after the filter on
+ *     the groups' frequency columns, if the .mut has them), a tree without a kept SNP is dropped, neighbouring
+ *     subtrees are associated (FindEquivalentBranches at N = M) and num_events, SNP_begin and SNP_end carried along.
+ *     RL_EINVAL: sample ages in the header, .gz inputs, a .poplabels whose haplotypes are not the .anc's, M < 2, a
+ *     .mut whose tree indices fall, a tree without SNPs before the .mut's last tree (an assert of the reference).
+ *   rl_subtrees_rewrite: a text .anc and .mut read with every column and written again (the readers and writers
+ *     of the above; a file the reference wrote comes back byte for byte). */
+typedef struct rl_subtrees_summary {
+  int trees_read;  /* trees of the .anc the walk visited */
+  int trees_kept;
+  int snps_read;   /* lines of the .mut */
+  int snps_kept;
+  int M, N;
+  int has_freq;    /* the .mut's first line carries frequency columns */
+} rl_subtrees_summary;
+int rl_subtrees_batch_trees(int N);
+int rl_subtrees_trees(const int *parents, const double *branch_length, int N, int ntrees, const int *subset, int M,
+                      int device, int *sub_parent, double *sub_bl, float *sub_time, int *convert_index,
+                      int *number_in_subpop);
+int rl_subtrees_poplabels(const char *poplabels_path, const char *pops_or_null, int *group_of_haplotype,
+                          int *num_haplotypes, int *of_interest, int *num_groups, char *names, int *names_bytes);
+int rl_subtrees_files(const char *anc_path, const char *mut_path, const char *poplabels_path, const char *pops,
+                      const char *out_prefix, int device, rl_subtrees_summary *summary);
+int rl_subtrees_rewrite(const char *anc_in, const char *mut_in, const char *anc_out, const char *mut_out);
+
 /* ------------------------------------------------------------------ tools */
 /* Synthetic block-coalescent panel (stand-in for MakeChunks input,
  * SURVEY.md 8d).  seq_chars (L*N) and/or bits (L*row_words) may be NULL. */

@@ -105,6 +105,13 @@ def lib():
                                       C.POINTER(C.c_int)]
         L.rl_coaltree_rates.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
         L.rl_coaltree_write.argtypes = [C.c_char_p, C.c_void_p, C.c_int, C.c_void_p]
+        L.rl_subtrees_batch_trees.argtypes = [C.c_int]
+        L.rl_subtrees_trees.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p,
+                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.rl_subtrees_poplabels.argtypes = [C.c_char_p, C.c_char_p, C.c_void_p, C.POINTER(C.c_int), C.c_void_p,
+                                            C.POINTER(C.c_int), C.c_char_p, C.POINTER(C.c_int)]
+        L.rl_subtrees_files.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_int, C.c_void_p]
+        L.rl_subtrees_rewrite.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p]
         L.rl_selection_logp.argtypes = [C.c_int, C.c_float, C.c_int, C.c_float, C.POINTER(C.c_float)]
         L.rl_selection_files.argtypes = [C.c_char_p, C.c_char_p]
         L.rl_window_copying.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
@@ -1126,6 +1133,65 @@ def coaltree_write(path, epochs, rates):
     if ep.shape != r.shape or ep.ndim != 1:
         raise RelateError("coaltree_write: epochs %s, rates %s" % (ep.shape, r.shape))
     _check(lib().rl_coaltree_write(os.fsencode(path), _p(ep), len(ep), _p(r)))
+
+
+def subtrees_batch_trees(N):
+    """trees per batch of the device path of subtrees_trees / subtrees_files at N leaves"""
+    return lib().rl_subtrees_batch_trees(int(N))
+
+
+def subtrees_trees(parents, branch_length, subset, device=None):
+    """rl_subtrees_trees: the subtrees of `RelateExtract --mode SubTreesForSubpopulation` for the leaves in `subset`
+    (labels, rising).  parents, branch_length: [trees][2N-1] (or one tree); device: None = the reference's loop on the
+    host, an int = that GPU.  -> dict(sub_parent [trees][2M-1] int32, sub_bl float64, sub_time float32, convert_index
+    [trees][2N-1] int32, number_in_subpop int32)"""
+    pa = np.ascontiguousarray(np.atleast_2d(parents), dtype=np.int32)
+    bl = np.ascontiguousarray(np.atleast_2d(branch_length), dtype=np.float64)
+    su = np.ascontiguousarray(subset, dtype=np.int32)
+    if pa.shape[1] % 2 == 0 or bl.shape != pa.shape or su.ndim != 1:
+        raise RelateError("subtrees_trees: parents %s, branch lengths %s, subset %s" % (pa.shape, bl.shape, su.shape))
+    T, nodes, M = len(pa), pa.shape[1], len(su)
+    sub = max(2 * M - 1, 1)
+    out = {"sub_parent": np.zeros((T, sub), np.int32), "sub_bl": np.zeros((T, sub), np.float64),
+           "sub_time": np.zeros((T, sub), np.float32), "convert_index": np.zeros((T, nodes), np.int32),
+           "number_in_subpop": np.zeros((T, nodes), np.int32)}
+    _check(lib().rl_subtrees_trees(_p(pa), _p(bl), (nodes + 1) // 2, T, _p(su), M, -1 if device is None else int(device),
+                                   _p(out["sub_parent"]), _p(out["sub_bl"]), _p(out["sub_time"]), _p(out["convert_index"]),
+                                   _p(out["number_in_subpop"])))
+    return out
+
+
+def read_poplabels(path, pop_of_interest=None):
+    """rl_subtrees_poplabels: a .poplabels file as Sample::Read takes it -> (groups: the names sorted,
+    group_of_haplotype [haplotypes] int32, of_interest: the sorted indices of the groups named in pop_of_interest
+    ("A,B", duplicates ignored, "All"), or None without one)"""
+    pops = None if pop_of_interest is None else pop_of_interest.encode()
+    nh, ng, nb = C.c_int(0), C.c_int(0), C.c_int(0)
+    _check(lib().rl_subtrees_poplabels(os.fsencode(path), pops, None, C.byref(nh), None, C.byref(ng), None, C.byref(nb)))
+    goh, flags, names = np.zeros(nh.value, np.int32), np.zeros(ng.value, np.int32), C.create_string_buffer(nb.value + 1)
+    _check(lib().rl_subtrees_poplabels(os.fsencode(path), pops, _p(goh), C.byref(nh), _p(flags), C.byref(ng), names, C.byref(nb)))
+    groups = names.raw[:nb.value].decode().split("\n")[:-1]
+    return groups, goh, (None if pops is None else [g for g in range(ng.value) if flags[g]])
+
+
+class _SubtreesSummary(C.Structure):
+    _fields_ = [(n, C.c_int) for n in ("trees_read", "trees_kept", "snps_read", "snps_kept", "M", "N", "has_freq")]
+
+
+def subtrees_files(anc_path, mut_path, poplabels_path, pop_of_interest, out_prefix, device=None):
+    """rl_subtrees_files: `RelateExtract --mode SubTreesForSubpopulation`: out_prefix.anc (text), .mut and .poplabels
+    for the haplotypes of the groups in pop_of_interest ("A,B" or "All") -> dict(trees_read, trees_kept, snps_read,
+    snps_kept, M, N, has_freq)"""
+    s = _SubtreesSummary()
+    _check(lib().rl_subtrees_files(os.fsencode(anc_path), os.fsencode(mut_path), os.fsencode(poplabels_path),
+                                   pop_of_interest.encode(), os.fsencode(out_prefix), -1 if device is None else int(device),
+                                   C.byref(s)))
+    return {n: getattr(s, n) for n, _ in s._fields_}
+
+
+def subtrees_rewrite(anc_in, mut_in, anc_out, mut_out):
+    """rl_subtrees_rewrite: a text .anc and .mut read with every column and written again with the mode's writers"""
+    _check(lib().rl_subtrees_rewrite(os.fsencode(anc_in), os.fsencode(mut_in), os.fsencode(anc_out), os.fsencode(mut_out)))
 
 
 def stage_find_equivalent_branches(out_dir, chunk_index=0):

@@ -29,6 +29,10 @@ int write_anc(const std::string &fn, const AncFile &a);
 // the SNPs a file covers: [*first, *last], from its first tree's position to the largest SNP_end of its last tree (a
 // tree covers from its position to the next tree's); RL_EFORMAT for a file without trees or with positions not rising
 int anc_coverage(const AncFile &a, const char *fn, int *first, int *last);
+// FindEquivalentBranches on a sequence in memory (equivalent.cpp): BranchAssociation of every pair of neighbours at
+// N leaves, then AssociateTrees -- num_events and SNP_begin carried forward along equivalent branches, num_events and
+// SNP_end back.  The trees carry child_left / child_right as the reference's trees would
+void associate_sequence(std::vector<AncTree> &trees, int N);
 // the header alone: haplotypes, trees, whether sample ages follow
 int read_anc_header(const std::string &fn, unsigned *N, unsigned *trees, bool *has_ages);
 

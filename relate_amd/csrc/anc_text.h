@@ -1,6 +1,7 @@
 // anc_text.h -- the text inputs of the modes that read a dated tree sequence (coalrate.cpp: CoalescentRateForSection;
-// frequency.cpp: Frequency): a text file that is refused when compressed, and the text .anc one tree at a time.  `mode`
-// is the name a message starts with.
+// frequency.cpp: Frequency): a text file that is refused when compressed, and the text .anc one tree at a time; and
+// the writer of the text .anc for the modes that write one (subtrees.cpp: SubTreesForSubpopulation).  `mode` is the
+// name a message starts with.
 #pragma once
 #include <cerrno>
 #include <cstdint>
@@ -9,7 +10,9 @@
 #include <fstream>
 #include <sstream>
 #include <string>
+#include <vector>
 
+#include "anc_file.h"
 #include "common.h"
 
 namespace rl {
@@ -88,16 +91,20 @@ struct AncText {
     set_error("%s: %s does not start with `NUM_HAPLOTYPES N` and `NUM_TREES T`: not a text .anc file", mode, fn.c_str());
     return RL_EFORMAT;
   }
-  // `pos: parent:(branch_length num_events snp_begin snp_end) ...`, 2N-1 nodes
-  int next(int index, int *parent, double *bl) {
+  // `pos: parent:(branch_length num_events snp_begin snp_end) ...`, 2N-1 nodes.  The last four (each may be null):
+  // the tree's position and, per node, the other three fields as Tree::ReadTree's `%f %d %d` takes them
+  int next(int index, int *parent, double *bl, int *pos = nullptr, float *num_events = nullptr, int *snp_begin = nullptr,
+           int *snp_end = nullptr) {
     if (!getline(is, line)) {
       set_error("%s: %s ends before tree %d of %d", mode, fn.c_str(), index, trees);
       return RL_EFORMAT;
     }
+    const bool all = num_events || snp_begin || snp_end;
     const char *p = line.c_str();
     char *end = nullptr;
-    (void)strtol(p, &end, 10);
+    const long position = strtol(p, &end, 10);
     bool ok = end != p && *end == ':';
+    if (pos) *pos = (int)position;
     p = end + 1;
     for (int v = 0; ok && v < 2 * N - 1; v++) {
       const long par = strtol(p, &end, 10);
@@ -107,6 +114,20 @@ struct AncText {
       bl[v] = strtod(p, &end);
       ok = end != p;
       parent[v] = (int)par;
+      if (ok && all) {
+        p = end;
+        const float ne = strtof(p, &end);
+        ok = end != p;
+        p = end;
+        const long sb = ok ? strtol(p, &end, 10) : 0;
+        ok = ok && end != p;
+        p = end;
+        const long se = ok ? strtol(p, &end, 10) : 0;
+        ok = ok && end != p;
+        if (num_events) num_events[v] = ne;
+        if (snp_begin) snp_begin[v] = (int)sb;
+        if (snp_end) snp_end[v] = (int)se;
+      }
       while (ok && *end && *end != ')') end++;
       ok = ok && *end == ')';
       p = end + 1;
@@ -118,5 +139,31 @@ struct AncText {
     return RL_OK;
   }
 };
+
+// the text .anc without sample ages as AncesTree::Dump(const std::string&) writes it (src/anc.cpp:1050-1073 and
+// :991-1013): `NUM_HAPLOTYPES N ` with its trailing blank, `NUM_TREES T`, then per tree `pos: ` and per node
+// `parent:(%.5f %.3f %d %d) `
+inline int write_anc_text(const char *mode, const std::string &fn, int N, const std::vector<AncTree> &trees) {
+  FILE *fp = fopen(fn.c_str(), "w");
+  if (!fp) {
+    set_error("%s: error while writing to %s", mode, fn.c_str());
+    return RL_EIO;
+  }
+  fprintf(fp, "NUM_HAPLOTYPES %ld ", (long)N);
+  fprintf(fp, "\n");
+  fprintf(fp, "NUM_TREES %ld\n", (long)trees.size());
+  for (const AncTree &t : trees) {
+    fprintf(fp, "%d: ", t.pos);
+    for (size_t v = 0; v < t.parent.size(); v++)
+      fprintf(fp, "%d:(%.5f %.3f %d %d) ", t.parent[v], t.branch_length[v], (double)t.num_events[v], t.snp_begin[v], t.snp_end[v]);
+    fprintf(fp, "\n");
+  }
+  const bool failed = ferror(fp) != 0;
+  if (fclose(fp) != 0 || failed) {
+    set_error("%s: writing %s failed", mode, fn.c_str());
+    return RL_EIO;
+  }
+  return RL_OK;
+}
 
 }  // namespace rl

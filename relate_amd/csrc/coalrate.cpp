@@ -61,6 +61,54 @@ int read_mut_rows(const char *mode, const std::string &fn, std::vector<MutRow> &
   return RL_OK;
 }
 
+// Sample::Read (src/sample.cpp:4-110): the group names sorted, and the group of every haplotype -- two haplotypes per
+// line, one if any line's fourth column is `1`.  `mode` is the name a message starts with (FinalizePopulationSize; subtrees.cpp:
+// SubTreesForSubpopulation)
+int read_poplabels(const char *mode, const std::string &fn, std::vector<std::string> &groups, std::vector<int> &group_of_haplotype) {
+  std::ifstream is(fn);
+  if (is.fail()) {
+    set_error("%s: failed to open file %s", mode, fn.c_str());
+    return RL_EIO;
+  }
+  if (is_gzip(fn)) {
+    set_error("%s: %s is compressed: compressed inputs are not part of this build, decompress the file", mode, fn.c_str());
+    return RL_EINVAL;
+  }
+  std::string line;
+  std::vector<std::string> group_of_line;
+  bool diploid = true;
+  getline(is, line);  // the header
+  while (getline(is, line)) {
+    if (line.empty()) continue;
+    std::vector<std::string> col(1);
+    for (char c : line) {
+      if (c == ' ' || c == '\t') col.emplace_back();
+      else col.back() += c;
+    }
+    if (col.size() < 2) {
+      set_error("%s: %s: `%s` has no second column (the group)", mode, fn.c_str(), line.c_str());
+      return RL_EFORMAT;
+    }
+    const std::string ploidy = col.size() > 3 ? col[3] : std::string();
+    if (ploidy != "NA") {
+      if (ploidy == "1") diploid = false;
+      else if (!diploid) {
+        set_error("%s: %s: Detected both haploid and diploid samples.", mode, fn.c_str());
+        return RL_EINVAL;
+      }
+    }
+    group_of_line.push_back(col[1]);
+    if (std::find(groups.begin(), groups.end(), col[1]) == groups.end()) groups.push_back(col[1]);
+  }
+  std::sort(groups.begin(), groups.end());
+  for (const std::string &gname : group_of_line) {
+    const int ind = (int)(std::find(groups.begin(), groups.end(), gname) - groups.begin());
+    group_of_haplotype.push_back(ind);
+    if (diploid) group_of_haplotype.push_back(ind);
+  }
+  return RL_OK;
+}
+
 namespace {
 
 // the product is rounded, then the sum: no fused multiply-add (coalrate_kernels.hip does the same)
@@ -194,53 +242,6 @@ struct Coalrate {
 };
 
 // ------------------------------------------------------------------------------------------------ the file layer
-
-// Sample::Read (src/sample.cpp:4-110): the group names sorted, and the group of every haplotype -- two haplotypes per
-// line, one if any line's fourth column is `1`
-int read_poplabels(const std::string &fn, std::vector<std::string> &groups, std::vector<int> &group_of_haplotype) {
-  std::ifstream is(fn);
-  if (is.fail()) {
-    set_error("FinalizePopulationSize: failed to open file %s", fn.c_str());
-    return RL_EIO;
-  }
-  if (is_gzip(fn)) {
-    set_error("FinalizePopulationSize: %s is compressed: compressed inputs are not part of this build, decompress the file", fn.c_str());
-    return RL_EINVAL;
-  }
-  std::string line;
-  std::vector<std::string> group_of_line;
-  bool diploid = true;
-  getline(is, line);  // the header
-  while (getline(is, line)) {
-    if (line.empty()) continue;
-    std::vector<std::string> col(1);
-    for (char c : line) {
-      if (c == ' ' || c == '\t') col.emplace_back();
-      else col.back() += c;
-    }
-    if (col.size() < 2) {
-      set_error("FinalizePopulationSize: %s: `%s` has no second column (the group)", fn.c_str(), line.c_str());
-      return RL_EFORMAT;
-    }
-    const std::string ploidy = col.size() > 3 ? col[3] : std::string();
-    if (ploidy != "NA") {
-      if (ploidy == "1") diploid = false;
-      else if (!diploid) {
-        set_error("FinalizePopulationSize: %s: Detected both haploid and diploid samples.", fn.c_str());
-        return RL_EINVAL;
-      }
-    }
-    group_of_line.push_back(col[1]);
-    if (std::find(groups.begin(), groups.end(), col[1]) == groups.end()) groups.push_back(col[1]);
-  }
-  std::sort(groups.begin(), groups.end());
-  for (const std::string &gname : group_of_line) {
-    const int ind = (int)(std::find(groups.begin(), groups.end(), gname) - groups.begin());
-    group_of_haplotype.push_back(ind);
-    if (diploid) group_of_haplotype.push_back(ind);
-  }
-  return RL_OK;
-}
 
 int null_args(const char *who) {
   set_error("%s: bad arguments (no null pointers)", who);
@@ -482,7 +483,7 @@ extern "C" int rl_coalrate_finalize_files(const char *bin_path, const char *popl
   std::vector<std::string> groups;
   std::vector<int> group_of_haplotype;
   if (poplabels_or_null)
-    if (const int rc = read_poplabels(poplabels_or_null, groups, group_of_haplotype)) return rc;
+    if (const int rc = read_poplabels("FinalizePopulationSize", poplabels_or_null, groups, group_of_haplotype)) return rc;
   int E = 0, N = 0;
   int rc = rl_coalrate_read_bin(bin_path, nullptr, &E, nullptr, &N);
   if (rc) return rc;

@@ -53,6 +53,11 @@ struct Persistence {
   }
 };
 
+// ---- the .poplabels as FinalizePopulationSize and SubTreesForSubpopulation (subtrees.cpp) read it
+// Sample::Read (src/sample.cpp:4-103): the group names sorted, and the group of every haplotype -- two haplotypes per
+// line, one if any line's fourth column is `1`; a file that mixes the two is refused (defined in coalrate.cpp)
+int read_poplabels(const char *mode, const std::string &fn, std::vector<std::string> &groups, std::vector<int> &group_of_haplotype);
+
 struct CoalrateDevice;  // D on the device and the staging room of one batch of trees
 
 // epochs [E] have passed the host's checks (2 <= E <= kCoalrateMaxEpochs, ep[0] = 0, rising)

@@ -311,6 +311,25 @@ void propagate(const std::vector<AncTree *> &seq, const std::vector<std::vector<
 // reading them back, and writing them again.
 namespace rl {
 
+// a sequence of trees in memory (subtrees.cpp: the subtrees of SubTreesForSubpopulation): neighbours associated on
+// the host's threads, then events and SNP ranges carried forward and back
+void associate_sequence(std::vector<AncTree> &trees, int N) {
+  std::vector<AncTree *> seq;
+  for (AncTree &t : trees) seq.push_back(&t);
+  const size_t M = seq.size();
+  if (M < 2) return;
+  const BranchMatcher bm(N);
+  std::vector<std::vector<int>> eq(M);  // eq[m]: branches of tree m -> branches of tree m-1
+  const int T = std::min<int>(host_threads(), (int)M - 1);
+  std::vector<std::thread> th;
+  for (int t = 0; t < T; t++)
+    th.emplace_back([&, t]() {
+      for (size_t m = 1 + t; m < M; m += T) bm.associate(*seq[m - 1], *seq[m], eq[m]);
+    });
+  for (auto &x : th) x.join();
+  propagate(seq, eq, N);
+}
+
 struct FebJob {
   int N = 0, W = 0;
   std::vector<AncFile> ancs;

@@ -34,6 +34,10 @@
 //          (RelateMutationRate --mode Avg of the reference: reads prefix.anc (text) and prefix.mut, writes
 //           out_avg.rate, the reference's bytes; --device -1: on the host; .gz inputs, sample ages and --chr /
 //           --first_chr / --last_chr are refused)
+//   Relate --mode SubTreesForSubpopulation --anc a.anc --mut a.mut --poplabels f --pop_of_interest A,B -o out [--device d]
+//          (RelateExtract --mode SubTreesForSubpopulation of the reference: the subtrees of the groups' haplotypes as
+//           out.anc (text), out.mut and out.poplabels, the reference's bytes; --device -1: on the host; .gz inputs and
+//           sample ages are refused)
 // Same options, files and stderr banners as include/pipeline/Relate.cpp:19-115,
 // Paint.cpp, BuildTopology.cpp of the reference; every other --mode is refused
 // (use the reference binary for them).  Extra options: --device n,
@@ -67,7 +71,7 @@ static void usage_line() {
   std::cerr << "---------------------------------------------------------" << std::endl << std::endl;
 }
 
-static const char *kModes = "MakeChunks|Paint|BuildTopology|PaintBuildTopology|FindEquivalentBranches|OptimizeParameters|CompareTopology|PairwiseCoalescence|CopyingMatrix|CoalescentRateForSection|FinalizePopulationSize|Frequency|Selection|AvgMutationRate|CoalRateForTree";
+static const char *kModes = "MakeChunks|Paint|BuildTopology|PaintBuildTopology|FindEquivalentBranches|OptimizeParameters|CompareTopology|PairwiseCoalescence|CopyingMatrix|CoalescentRateForSection|FinalizePopulationSize|Frequency|Selection|AvgMutationRate|CoalRateForTree|SubTreesForSubpopulation";
 
 // `Relate --mode OptimizeParameters` (pipeline/OptimizeParameters.cpp:22-206): MakeChunks, then for every chunk the
 // grid of (theta, recombination factor) through rl_stage_optimize_parameters, the temporary files removed as the
@@ -569,6 +573,57 @@ static int coal_rate_for_tree(std::map<std::string, std::string> &opt) {
   return 0;
 }
 
+// `Relate --mode SubTreesForSubpopulation --anc a.anc --mut a.mut --poplabels f --pop_of_interest A,B -o out [--device d]`
+// (CreateAncesTreeFileForSubpopulation, extract/CreateAncesTreeFileForSubpopulation.cpp:284-401, RelateExtract --mode
+// SubTreesForSubpopulation: rl_subtrees_poplabels for the banner, rl_subtrees_files; a summary on stdout)
+static int sub_trees_for_subpopulation(std::map<std::string, std::string> &opt) {
+  if (!opt.count("pop_of_interest") || !opt.count("poplabels") || !opt.count("anc") || !opt.count("mut") || !opt.count("output")) {
+    std::cout << "Not enough arguments supplied." << std::endl;
+    std::cout << "Needed: pop_of_interest, poplabels, anc, mut, output." << std::endl;
+    std::cout << "Estimate population size using coalescent rate." << std::endl;
+    return 0;  // (exit(0), :290-300)
+  }
+  {  // (:306-309; the frequency columns follow the thirteen of the standard header)
+    std::ifstream is(opt["mut"]);
+    std::string line;
+    if (getline(is, line) && getline(is, line) && std::count(line.begin(), line.end(), ';') <= 13)
+      std::cerr << "We recommend to first add population annotation to .mut using RelateFileFormats --mode GenerateSNPAnnotations" << std::endl;
+  }
+  std::cerr << "---------------------------------------------------------" << std::endl;
+  std::cerr << "Calculating anc file for " << opt["anc"] << " and subpopulation(s) ";
+  int haplotypes = 0, num_groups = 0, names_bytes = 0;
+  if (rl_subtrees_poplabels(opt["poplabels"].c_str(), opt["pop_of_interest"].c_str(), nullptr, &haplotypes, nullptr, &num_groups, nullptr, &names_bytes) != 0) {
+    std::cerr << std::endl << "Error: " << rl_last_error() << std::endl;
+    return 1;
+  }
+  std::vector<int> of_interest(num_groups);
+  std::string names(names_bytes, ' ');
+  if (rl_subtrees_poplabels(opt["poplabels"].c_str(), opt["pop_of_interest"].c_str(), nullptr, &haplotypes, of_interest.data(), &num_groups, &names[0], &names_bytes) != 0) {
+    std::cerr << std::endl << "Error: " << rl_last_error() << std::endl;
+    return 1;
+  }
+  if (opt["pop_of_interest"] != "All") {
+    std::istringstream ns(names);
+    std::string group;
+    for (int g = 0; g < num_groups && getline(ns, group); g++)
+      if (of_interest[g]) std::cerr << group << " ";
+    std::cerr << std::endl;
+  } else {
+    std::cerr << "All" << std::endl;
+  }
+  const int device = opt.count("device") ? atoi(opt["device"].c_str()) : 0;
+  rl_subtrees_summary sum;
+  if (rl_subtrees_files(opt["anc"].c_str(), opt["mut"].c_str(), opt["poplabels"].c_str(), opt["pop_of_interest"].c_str(),
+                        opt["output"].c_str(), device, &sum) != 0) {
+    std::cerr << "Error: " << rl_last_error() << std::endl;
+    return 1;
+  }
+  std::cout << sum.M << " of " << sum.N << " haplotypes; " << sum.trees_kept << " of " << sum.trees_read << " trees and " << sum.snps_kept
+            << " of " << sum.snps_read << " SNPs kept; " << opt["output"] << ".anc, .mut and .poplabels written." << std::endl;
+  usage_line();
+  return 0;
+}
+
 int main(int argc, char **argv) {
   // BuildTopology keeps several tree-builder launches and window kernels in flight from its section threads: more
   // hardware queues than HIP's default four (read when the runtime starts; an explicit setting wins) -- but not more
@@ -595,6 +650,8 @@ int main(int argc, char **argv) {
       //  name several chromosomes are named to be refused; CoalRateForTree reads input, output, bins and years_per_gen
       //  of RelateCoalescentRate.cpp and refuses dist and chr)
       {"chr", true}, {"first_chr", true}, {"last_chr", true},
+      // (SubTreesForSubpopulation reads anc, mut, poplabels, pop_of_interest and output of RelateExtract.cpp)
+      {"anc", true}, {"mut", true}, {"pop_of_interest", true},
       // accepted and ignored by these two modes in the reference as well
       {"haps", true}, {"sample", true}, {"map", true}, {"mutation_rate", true}, {"effectiveN", true},
       {"memory", true}, {"dist", true}, {"annot", true}, {"coal", true}, {"transversion", false}};
@@ -637,6 +694,7 @@ int main(int argc, char **argv) {
     std::cerr << "  Selection: -i,--input prefix -o out" << std::endl;
     std::cerr << "  AvgMutationRate: -i,--input prefix -o out [--dist file] [--bins lower,upper,step] [--years_per_gen g] [--device d]" << std::endl;
     std::cerr << "  CoalRateForTree: -i,--input prefix -o out [--bins lower,upper,step] [--years_per_gen g] [--device d]" << std::endl;
+    std::cerr << "  SubTreesForSubpopulation: --anc a.anc --mut a.mut --poplabels f --pop_of_interest A,B -o out [--device d]" << std::endl;
     return opt.count("help") ? 0 : 1;
   }
   const std::string mode = opt["mode"];
@@ -646,6 +704,7 @@ int main(int argc, char **argv) {
   if (mode == "Selection") return selection(opt);
   if (mode == "AvgMutationRate") return avg_mutation_rate(opt);
   if (mode == "CoalRateForTree") return coal_rate_for_tree(opt);
+  if (mode == "SubTreesForSubpopulation") return sub_trees_for_subpopulation(opt);
   if (mode == "CompareTopology") return compare_topology(opt);
   if (mode == "PairwiseCoalescence") return pairwise_coalescence(opt);
   if (mode == "OptimizeParameters" && opt.count("output") && opt["output"].find('/') != std::string::npos) {
@@ -768,7 +827,7 @@ int main(int argc, char **argv) {
     if (rc == 1) return 1;  // first_section >= num_windows (BuildTopology.cpp:45)
   } else {
     std::cerr << "Mode " << mode << " is not part of this build: it replaces --mode MakeChunks, Paint, BuildTopology, FindEquivalentBranches, "
-              << "OptimizeParameters, CoalescentRateForSection, FinalizePopulationSize, Frequency, Selection, AvgMutationRate and CoalRateForTree only; run the reference Relate for the other stages." << std::endl;
+              << "OptimizeParameters, CoalescentRateForSection, FinalizePopulationSize, Frequency, Selection, AvgMutationRate, CoalRateForTree and SubTreesForSubpopulation only; run the reference Relate for the other stages." << std::endl;
     return 1;
   }
   if (rc != 0) {
