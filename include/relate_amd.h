@@ -856,6 +856,70 @@ int rl_mutrate_anc(const char *anc_path, const char *mut_path, const char *dist_
 int rl_mutrate_write(const char *path, const double *epochs, int nepochs, const double *mutation,
                      const double *opportunity);
 
+/* ------------------------------------------------------------------ MutationRateWithContext / FinalizeMutationRate
+ * The reference's `RelateMutationRate --mode WithContextForChromosome` and `--mode Finalize` (include/evaluate/
+ * mutation_rate/RelateMutationRate.cpp): the mutation rate through time of the 96 trinucleotide categories.  The
+ * epochs are those of rl_mutrate_epochs (:661-744 is the text of AvgMutationRate.cpp:373-456; its `age` is 0), the
+ * branch length of a tree per epoch that of rl_mutrate_trees.
+ *
+ * Categories (:746-794): 192 keys `upstream downstream ancestral derived` over ACGT map onto 96 indices, 6 * (4 * up +
+ * down) + {C>A, C>G, C>T, A>T, A>G, A>C}, a key and its reverse complement onto the same index.
+ *
+ * Bases per SNP and category (CountBasesByType, :40-260): the ancestor FASTA (first line skipped, case kept) and the
+ * mask FASTA (upper-cased) are padded with N to the longer one; one pass moves a base p along them with a count d of
+ * non-P mask characters in a window around p.  p starts at min(1001, position of the first SNP) with the window [0,
+ * 1000 + p]; while the window's right end is inside (main phase, threshold 2000) both ends move, afterwards (tail
+ * phase, threshold 1000) only the left one.  Base p counts for the current SNP s -- +1 on the three categories
+ * (flanks, ancestral -> each other base) -- when it lies between the midpoints to the neighbours of the current
+ * position pos[j] of the position list (the midpoint in front of pos[0] is 0.5 * pos[0]), its mask is P, d is within
+ * the threshold, SNP s has exactly one branch and the three ancestor bases are nucleotides in either case.  s advances
+ * when p reaches the midpoint behind pos[j], j while pos[j] is below SNP s's position.  Both phases end at the LAST
+ * SNP, whose row stays zero.
+ *
+ * Per SNP in the .mut's order (:829-908).  It qualifies with exactly one branch, both flanks not `NA`, alleles `X/Y`
+ * of three characters with X != Y both in ACGT; ind = table[upstream + downstream + X + Y], 0 for a key the table
+ * lacks.  age_end = min(age_end, the float time of its tree's root); the SNP is spread over the epochs [age_begin,
+ * age_end] spans as for AvgMutationRate, onto mutation[e][ind]; and for every epoch e and category c
+ *     opportunity[e][c] += length_of_its_tree[e] * (double)count[s][c]      a double product, then a double sum,
+ * one serial chain per cell through the qualifying SNPs.
+ *   rl_mutctx_category_names (replaces :397-410): the 96 names, '\n' after each, in index order; *bytes: room on
+ *     entry, the bytes needed (with the final 0) on return.  rl_mutctx_category: the index of a 4-letter key, -1 for
+ *     one the table lacks.
+ *   rl_mutctx_count_bases (replaces :40-260): pos [npos] the position list, snp_pos and one_branch [nsnps] the .mut's;
+ *     counts [nsnps][96] uint32.  RL_EINVAL names the SNP where the reference reads outside its sequences (a mask
+ *     that ends inside the first window, a counted base 0) or past the end of its position list.
+ *   rl_mutctx_trees (replaces :888-893 over :821-838): parents, branch_length [ntrees][2N-1]; the qualifying SNPs as
+ *     snp_tree [nsnps] (not falling) and snp_counts [nsnps][96]; opportunity [E][96]; root_time_or_null [ntrees];
+ *     seconds_or_null [3]: on the device, the seconds of the tree arrays and the per-tree kernel | of the SNP copies |
+ *     of the chains kernel.  device >= 0: relate_amd/csrc/mutctx_kernels.hip, in batches of rl_mutrate_batch_trees(N)
+ *     trees, 2 <= N <= 10240, 2 <= E <= 64, RL_ENODEVICE without one; device < 0: the reference's loop on one host
+ *     thread, the same bits.  RL_EINVAL names a tree as rl_mutrate_trees does; nothing of its batch is added.
+ *   rl_mutctx_anc (replaces :578-908): a TEXT .anc and its .mut, the mask, the ancestor, the --dist file or NULL;
+ *     mutation, opportunity [E][96]; snps3 (may be NULL): SNPs read, with one branch, qualifying.  RL_EINVAL: sample
+ *     ages, .gz inputs, an age_end that is not below the last boundary (the reference's assert :869).
+ *   rl_mutctx_write / rl_mutctx_read (replace :916-932, :365-382): prefix_mut.bin (int E, E doubles, u64 E, u64 96,
+ *     E*96 doubles) and prefix_opp.bin (the matrix alone).  *nepochs: room on entry, the count on return.
+ *   rl_mutctx_sum (replaces :445-576): prefix_chr<c>_{mut,opp}.bin of the chromosomes ('\n' separated) added in order
+ *     into out_prefix_{mut,opp}.bin; the per-chromosome files stay (the reference removes them).
+ *   rl_mutctx_finalize (replaces :385-425): in_prefix_{mut,opp}.bin -> the .rate text: the 96 names, then per epoch but
+ *     the last its start and mutation / opportunity per category as operator<< prints a double (0/0: `-nan`).
+ * The ForCategory, ForPattern, XY and MutationDensity modes are not offered. */
+int rl_mutctx_category_names(char *names, int *bytes);
+int rl_mutctx_category(const char *key);
+int rl_mutctx_count_bases(const char *ancestor_path, const char *mask_path, const int *pos, long long npos,
+                          const int *snp_pos, const unsigned char *one_branch, long long nsnps, uint32_t *counts);
+int rl_mutctx_trees(const int *parents, const double *branch_length, int N, int ntrees, const int *snp_tree,
+                    const uint32_t *snp_counts, long long nsnps, const double *epochs, int nepochs, int device,
+                    double *opportunity, float *root_time_or_null, double *seconds_or_null);
+int rl_mutctx_anc(const char *anc_path, const char *mut_path, const char *mask_path, const char *ancestor_path,
+                  const char *dist_path_or_null, const double *epochs, int nepochs, int device, double *mutation,
+                  double *opportunity, long long *snps3);
+int rl_mutctx_write(const char *prefix, const double *epochs, int nepochs, const double *mutation,
+                    const double *opportunity);
+int rl_mutctx_read(const char *prefix, double *epochs, int *nepochs, double *mutation, double *opportunity);
+int rl_mutctx_sum(const char *prefix, const char *chromosomes, const char *out_prefix);
+int rl_mutctx_finalize(const char *in_prefix, const char *rate_path);
+
 /* ------------------------------------------------------------------ CoalRateForTree
  * The reference's `RelateCoalescentRate --mode CoalRateForTree` (CoalescenceRateForTree, include/evaluate/
  * coalescent_rate/CoalescentRateForSection.cpp:605-858, and coal_tree::populate / coal_tree::Dump(const std::string&),

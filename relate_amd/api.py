@@ -97,6 +97,18 @@ def lib():
         L.rl_mutrate_anc.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p,
                                      C.c_void_p, C.POINTER(C.c_longlong)]
         L.rl_mutrate_write.argtypes = [C.c_char_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+        L.rl_mutctx_category_names.argtypes = [C.c_char_p, C.POINTER(C.c_int)]
+        L.rl_mutctx_category.argtypes = [C.c_char_p]
+        L.rl_mutctx_count_bases.argtypes = [C.c_char_p, C.c_char_p, C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p,
+                                            C.c_longlong, C.c_void_p]
+        L.rl_mutctx_trees.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_longlong,
+                                      C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.rl_mutctx_anc.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_void_p, C.c_int,
+                                    C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.rl_mutctx_write.argtypes = [C.c_char_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+        L.rl_mutctx_read.argtypes = [C.c_char_p, C.c_void_p, C.POINTER(C.c_int), C.c_void_p, C.c_void_p]
+        L.rl_mutctx_sum.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p]
+        L.rl_mutctx_finalize.argtypes = [C.c_char_p, C.c_char_p]
         L.rl_coaltree_batch_trees.argtypes = [C.c_int]
         L.rl_coaltree_num_blocks.argtypes = [C.c_longlong, C.c_int]
         L.rl_coaltree_trees.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int,
@@ -1070,6 +1082,99 @@ def mutrate_write(path, epochs, mutation, opportunity):
     if not ep.shape == m.shape == o.shape or ep.ndim != 1:
         raise RelateError("mutrate_write: epochs %s, mutation %s, opportunity %s" % (ep.shape, m.shape, o.shape))
     _check(lib().rl_mutrate_write(os.fsencode(path), _p(ep), len(ep), _p(m), _p(o)))
+
+
+MUTCTX_CATEGORIES = 96  # the trinucleotide categories of MutationRateWithContext
+MUTCTX_DEPTH = 16       # kMutctxDepth: SNPs whose operands a lane of the chains kernel holds at a time
+MUTCTX_SNP_CHUNK = 1 << 15  # kMutctxSnpChunk: qualifying SNPs per launch of the chains kernel
+
+
+def mutctx_category_names():
+    """rl_mutctx_category_names: the 96 category names (`AC/AT`: upstream, ancestral/derived, downstream) in index order"""
+    buf = C.create_string_buffer(1024)
+    n = C.c_int(len(buf))
+    _check(lib().rl_mutctx_category_names(buf, C.byref(n)))
+    return buf.value.decode().split("\n")[:-1]
+
+
+def mutctx_category(key):
+    """rl_mutctx_category: the index of `upstream downstream ancestral derived` (4 letters), -1 for a key the table lacks"""
+    return lib().rl_mutctx_category(key.encode())
+
+
+def mutctx_count_bases(ancestor_path, mask_path, pos, snp_pos, one_branch):
+    """rl_mutctx_count_bases: the bases counted for every SNP and category.  pos: the position list (the --dist file's
+    or the .mut's); snp_pos, one_branch: [L] of the .mut -> [L][96] uint32"""
+    p = np.ascontiguousarray(pos, dtype=np.int32)
+    sp = np.ascontiguousarray(snp_pos, dtype=np.int32)
+    ob = np.ascontiguousarray(one_branch, dtype=np.uint8)
+    if p.ndim != 1 or sp.ndim != 1 or ob.shape != sp.shape:
+        raise RelateError("mutctx_count_bases: pos %s, snp_pos %s, one_branch %s" % (p.shape, sp.shape, ob.shape))
+    out = np.zeros((len(sp), MUTCTX_CATEGORIES), np.uint32)
+    _check(lib().rl_mutctx_count_bases(os.fsencode(ancestor_path), os.fsencode(mask_path), _p(p), len(p), _p(sp), _p(ob),
+                                       len(sp), _p(out)))
+    return out
+
+
+def mutctx_trees(parents, branch_length, snp_tree, snp_counts, epochs, device=None, details=False):
+    """rl_mutctx_trees: the opportunity of every epoch and category.  parents, branch_length: [trees][2N-1]; snp_tree
+    [S] (not falling) and snp_counts [S][96] uint32: the qualifying SNPs in the .mut's order; device: None = the
+    reference's loop on the host, an int = that GPU.  -> [E][96] float64; details: (that, root times [trees] float32,
+    seconds [3]: trees | SNP copies | chains kernel, zeros on the host)"""
+    pa = np.ascontiguousarray(np.atleast_2d(parents), dtype=np.int32)
+    bl = np.ascontiguousarray(np.atleast_2d(branch_length), dtype=np.float64)
+    ep = np.ascontiguousarray(epochs, dtype=np.float64)
+    st = np.ascontiguousarray(snp_tree, dtype=np.int32)
+    sc = np.ascontiguousarray(snp_counts, dtype=np.uint32).reshape(-1, MUTCTX_CATEGORIES)
+    if pa.shape[1] % 2 == 0 or bl.shape != pa.shape or ep.ndim != 1 or st.ndim != 1 or len(sc) != len(st):
+        raise RelateError("mutctx_trees: parents %s, branch lengths %s, epochs %s, SNP trees %s, counts %s"
+                          % (pa.shape, bl.shape, ep.shape, st.shape, sc.shape))
+    out = np.zeros((len(ep), MUTCTX_CATEGORIES), np.float64)
+    roots, seconds = np.zeros(len(pa), np.float32), np.zeros(3, np.float64)
+    _check(lib().rl_mutctx_trees(_p(pa), _p(bl), (pa.shape[1] + 1) // 2, len(pa), _p(st), _p(sc), len(st), _p(ep), len(ep),
+                                 -1 if device is None else int(device), _p(out), _p(roots), _p(seconds)))
+    return (out, roots, seconds) if details else out
+
+
+def mutctx_anc(anc_path, mut_path, mask_path, ancestor_path, epochs, dist_path=None, device=None):
+    """rl_mutctx_anc: `RelateMutationRate --mode WithContextForChromosome` on a text .anc and its .mut -> (mutation
+    [E][96], opportunity [E][96], (SNPs read, with one branch, qualifying))"""
+    ep = np.ascontiguousarray(epochs, dtype=np.float64)
+    mutation, opportunity = np.zeros((len(ep), MUTCTX_CATEGORIES)), np.zeros((len(ep), MUTCTX_CATEGORIES))
+    snps = np.zeros(3, np.int64)
+    _check(lib().rl_mutctx_anc(os.fsencode(anc_path), os.fsencode(mut_path), os.fsencode(mask_path), os.fsencode(ancestor_path),
+                               None if dist_path is None else os.fsencode(dist_path), _p(ep), len(ep),
+                               -1 if device is None else int(device), _p(mutation), _p(opportunity), _p(snps)))
+    return mutation, opportunity, tuple(int(x) for x in snps)
+
+
+def mutctx_write(prefix, epochs, mutation, opportunity):
+    """rl_mutctx_write: prefix_mut.bin and prefix_opp.bin, the reference's bytes"""
+    ep = np.ascontiguousarray(epochs, dtype=np.float64)
+    m = np.ascontiguousarray(mutation, dtype=np.float64)
+    o = np.ascontiguousarray(opportunity, dtype=np.float64)
+    if ep.ndim != 1 or m.shape != (len(ep), MUTCTX_CATEGORIES) or o.shape != m.shape:
+        raise RelateError("mutctx_write: epochs %s, mutation %s, opportunity %s" % (ep.shape, m.shape, o.shape))
+    _check(lib().rl_mutctx_write(os.fsencode(prefix), _p(ep), len(ep), _p(m), _p(o)))
+
+
+def mutctx_read(prefix):
+    """rl_mutctx_read: prefix_mut.bin and prefix_opp.bin -> (epochs [E], mutation [E][96], opportunity [E][96])"""
+    ep = np.zeros(64, np.float64)
+    m, o = np.zeros((64, MUTCTX_CATEGORIES)), np.zeros((64, MUTCTX_CATEGORIES))
+    E = C.c_int(64)
+    _check(lib().rl_mutctx_read(os.fsencode(prefix), _p(ep), C.byref(E), _p(m), _p(o)))
+    return ep[:E.value].copy(), m[:E.value].copy(), o[:E.value].copy()
+
+
+def mutctx_sum(prefix, chromosomes, out_prefix):
+    """rl_mutctx_sum: prefix_chr<c>_{mut,opp}.bin of every chromosome name, added in order -> out_prefix_{mut,opp}.bin"""
+    _check(lib().rl_mutctx_sum(os.fsencode(prefix), "".join(str(c) + "\n" for c in chromosomes).encode(), os.fsencode(out_prefix)))
+
+
+def mutctx_finalize(in_prefix, rate_path):
+    """rl_mutctx_finalize: in_prefix_{mut,opp}.bin -> the .rate text of `RelateMutationRate --mode Finalize`"""
+    _check(lib().rl_mutctx_finalize(os.fsencode(in_prefix), os.fsencode(rate_path)))
 
 
 COALTREE_BLOCK_SIZE = 1000  # trees per block in the reference's CoalRateForTree

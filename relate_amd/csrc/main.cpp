@@ -38,6 +38,14 @@
 //          (RelateExtract --mode SubTreesForSubpopulation of the reference: the subtrees of the groups' haplotypes as
 //           out.anc (text), out.mut and out.poplabels, the reference's bytes; --device -1: on the host; .gz inputs and
 //           sample ages are refused)
+//   Relate --mode MutationRateWithContext -i prefix -o out --mask m.fa --ancestor a.fa [--dist file]
+//          [--bins lower,upper,step] [--years_per_gen g] [--device d]
+//          (RelateMutationRate --mode WithContextForChromosome of the reference: reads prefix.anc (text) and
+//           prefix.mut, writes out_mut.bin and out_opp.bin, the reference's bytes; --device -1: on the host; .gz inputs
+//           and sample ages are refused)
+//   Relate --mode FinalizeMutationRate -i prefix -o out [--first_chr a --last_chr b | --chr file]
+//          (RelateMutationRate --mode Finalize: prefix_mut.bin + prefix_opp.bin -> out.rate; with chromosomes first
+//           out_chr<c>_{mut,opp}.bin summed into out_{mut,opp}.bin, the per-chromosome files kept; on the host)
 // Same options, files and stderr banners as include/pipeline/Relate.cpp:19-115,
 // Paint.cpp, BuildTopology.cpp of the reference; every other --mode is refused
 // (use the reference binary for them).  Extra options: --device n,
@@ -71,7 +79,7 @@ static void usage_line() {
   std::cerr << "---------------------------------------------------------" << std::endl << std::endl;
 }
 
-static const char *kModes = "MakeChunks|Paint|BuildTopology|PaintBuildTopology|FindEquivalentBranches|OptimizeParameters|CompareTopology|PairwiseCoalescence|CopyingMatrix|CoalescentRateForSection|FinalizePopulationSize|Frequency|Selection|AvgMutationRate|CoalRateForTree|SubTreesForSubpopulation";
+static const char *kModes = "MakeChunks|Paint|BuildTopology|PaintBuildTopology|FindEquivalentBranches|OptimizeParameters|CompareTopology|PairwiseCoalescence|CopyingMatrix|CoalescentRateForSection|FinalizePopulationSize|Frequency|Selection|AvgMutationRate|CoalRateForTree|SubTreesForSubpopulation|MutationRateWithContext|FinalizeMutationRate";
 
 // `Relate --mode OptimizeParameters` (pipeline/OptimizeParameters.cpp:22-206): MakeChunks, then for every chunk the
 // grid of (theta, recombination factor) through rl_stage_optimize_parameters, the temporary files removed as the
@@ -525,6 +533,101 @@ static int avg_mutation_rate(std::map<std::string, std::string> &opt) {
   return 0;
 }
 
+// `Relate --mode MutationRateWithContext -i prefix -o out --mask m.fa --ancestor a.fa [--dist file] [--bins l,u,s]
+// [--years_per_gen g] [--device d]` (MutationRateWithContext, evaluate/mutation_rate/RelateMutationRate.cpp:578-949,
+// RelateMutationRate --mode WithContextForChromosome: rl_mutrate_epochs, rl_mutctx_anc, rl_mutctx_write; a summary on
+// stdout)
+static int mutation_rate_with_context(std::map<std::string, std::string> &opt) {
+  if (!opt.count("mask") || !opt.count("ancestor") || !opt.count("input") || !opt.count("output")) {
+    std::cout << "Not enough arguments supplied." << std::endl;
+    std::cout << "Needed: mask, ancestor, input, output. Optional: years_per_gen, bins, dist, device." << std::endl;
+    std::cout << "Calculate mutation rate for 96 categories (Do not apply after using RemoveTreesWithFewMutations).." << std::endl;
+    return 0;  // (exit(0), :580-590)
+  }
+  for (const char *o : {"chr", "first_chr", "last_chr"})
+    if (opt.count(o)) {
+      std::cerr << "Error: --" << o << " is not part of this build's MutationRateWithContext: one chromosome per run (-i prefix_chr<c> -o out_chr<c>), then FinalizeMutationRate with --" << o << "." << std::endl;
+      return 1;
+    }
+  std::cerr << "------------------------------------------------------" << std::endl;
+  std::cerr << "Calculating mutation rate for 96 categories " << opt["input"] << " ..." << std::endl;
+  float years_per_gen = 28.0f;
+  try {
+    if (opt.count("years_per_gen")) years_per_gen = std::stof(opt["years_per_gen"]);
+  } catch (...) {
+    std::cerr << "Error: --years_per_gen expects a number" << std::endl;
+    return 1;
+  }
+  std::vector<double> epochs(4096);
+  int E = (int)epochs.size();
+  const int device = opt.count("device") ? atoi(opt["device"].c_str()) : 0;
+  const std::string anc = opt["input"] + ".anc", mut = opt["input"] + ".mut";
+  if (rl_mutrate_epochs(years_per_gen, opt.count("bins") ? opt["bins"].c_str() : nullptr, epochs.data(), &E) != 0) {
+    std::cerr << "Error: " << rl_last_error() << std::endl;
+    return 1;
+  }
+  std::vector<double> mutation((size_t)E * 96), opportunity((size_t)E * 96);
+  long long snps[3] = {0, 0, 0};
+  if (rl_mutctx_anc(anc.c_str(), mut.c_str(), opt["mask"].c_str(), opt["ancestor"].c_str(),
+                    opt.count("dist") ? opt["dist"].c_str() : nullptr, epochs.data(), E, device, mutation.data(),
+                    opportunity.data(), snps) != 0 ||
+      rl_mutctx_write(opt["output"].c_str(), epochs.data(), E, mutation.data(), opportunity.data()) != 0) {
+    std::cerr << "Error: " << rl_last_error() << std::endl;
+    return 1;
+  }
+  std::cout << snps[0] << " SNPs, " << snps[2] << " qualifying SNPs of " << snps[1] << " with one branch, " << E << " epochs; "
+            << opt["output"] << "_mut.bin and " << opt["output"] << "_opp.bin written." << std::endl;
+  usage_line();
+  return 0;
+}
+
+// `Relate --mode FinalizeMutationRate -i prefix -o out [--first_chr a --last_chr b | --chr file]` (RelateMutationRate
+// --mode Finalize, RelateMutationRate.cpp:3568-3579: with chromosomes SummarizeWholeGenome :445-576, which reads
+// OUT_chr<c>_{mut,opp}.bin and writes OUT_{mut,opp}.bin -- rl_mutctx_sum; the per-chromosome files are not removed --,
+// then FinalizeMutationRate :344-443, which reads IN_{mut,opp}.bin and writes OUT.rate -- rl_mutctx_finalize)
+static int finalize_mutation_rate(std::map<std::string, std::string> &opt) {
+  if (!opt.count("input") || !opt.count("output")) {
+    std::cout << "Not enough arguments supplied." << std::endl;
+    std::cout << "Needed: input, output. Optional: chr, first_chr, last_chr." << std::endl;
+    std::cout << "Extract mutation rate of 96 categories from .bin file." << std::endl;
+    return 0;  // (exit(0), :350-360)
+  }
+  std::string chromosomes;
+  if (opt.count("chr")) {
+    std::ifstream is(opt["chr"]);
+    if (is.fail()) {
+      std::cerr << "Error while opening file " << opt["chr"] << std::endl;
+      return 1;
+    }
+    for (std::string line; getline(is, line);) chromosomes += line + "\n";
+  } else if (opt.count("first_chr") && opt.count("last_chr")) {
+    const int first = atoi(opt["first_chr"].c_str()), last = atoi(opt["last_chr"].c_str());
+    if (first < 0 || last < 0) {
+      std::cerr << "Do not use negative chr indices." << std::endl;
+      return 1;
+    }
+    for (int chr = first; chr <= last; chr++) chromosomes += std::to_string(chr) + "\n";
+  }
+  if (opt.count("chr") || (opt.count("first_chr") && opt.count("last_chr"))) {
+    std::cerr << "------------------------------------------------------" << std::endl;
+    std::cerr << "Summarizing mutation rates..." << std::endl;
+    if (rl_mutctx_sum(opt["output"].c_str(), chromosomes.c_str(), opt["output"].c_str()) != 0) {
+      std::cerr << "Error: " << rl_last_error() << std::endl;
+      return 1;
+    }
+  }
+  std::cerr << "------------------------------------------------------" << std::endl;
+  std::cerr << "Finalizing mutation rate..." << std::endl;
+  const std::string rate = opt["output"] + ".rate";
+  if (rl_mutctx_finalize(opt["input"].c_str(), rate.c_str()) != 0) {
+    std::cerr << "Error: " << rl_last_error() << std::endl;
+    return 1;
+  }
+  std::cout << rate << " written." << std::endl;
+  usage_line();
+  return 0;
+}
+
 // `Relate --mode CoalRateForTree -i prefix -o out [--bins l,u,s] [--years_per_gen g] [--device d]`
 // (CoalescenceRateForTree, evaluate/coalescent_rate/CoalescentRateForSection.cpp:605-858, RelateCoalescentRate --mode
 // CoalRateForTree: rl_mutrate_epochs -- :630-713 is the text of AvgMutationRate.cpp:373-456 --, rl_coaltree_anc,
@@ -652,6 +755,9 @@ int main(int argc, char **argv) {
       {"chr", true}, {"first_chr", true}, {"last_chr", true},
       // (SubTreesForSubpopulation reads anc, mut, poplabels, pop_of_interest and output of RelateExtract.cpp)
       {"anc", true}, {"mut", true}, {"pop_of_interest", true},
+      // (MutationRateWithContext reads mask, ancestor, input, output, dist, bins and years_per_gen of
+      //  RelateMutationRate.cpp; FinalizeMutationRate input, output, chr, first_chr and last_chr)
+      {"ancestor", true},
       // accepted and ignored by these two modes in the reference as well
       {"haps", true}, {"sample", true}, {"map", true}, {"mutation_rate", true}, {"effectiveN", true},
       {"memory", true}, {"dist", true}, {"annot", true}, {"coal", true}, {"transversion", false}};
@@ -695,6 +801,8 @@ int main(int argc, char **argv) {
     std::cerr << "  AvgMutationRate: -i,--input prefix -o out [--dist file] [--bins lower,upper,step] [--years_per_gen g] [--device d]" << std::endl;
     std::cerr << "  CoalRateForTree: -i,--input prefix -o out [--bins lower,upper,step] [--years_per_gen g] [--device d]" << std::endl;
     std::cerr << "  SubTreesForSubpopulation: --anc a.anc --mut a.mut --poplabels f --pop_of_interest A,B -o out [--device d]" << std::endl;
+    std::cerr << "  MutationRateWithContext: -i,--input prefix -o out --mask m.fa --ancestor a.fa [--dist file] [--bins lower,upper,step] [--years_per_gen g] [--device d]" << std::endl;
+    std::cerr << "  FinalizeMutationRate: -i,--input prefix -o out [--first_chr a --last_chr b | --chr file]" << std::endl;
     return opt.count("help") ? 0 : 1;
   }
   const std::string mode = opt["mode"];
@@ -704,6 +812,14 @@ int main(int argc, char **argv) {
   if (mode == "Selection") return selection(opt);
   if (mode == "AvgMutationRate") return avg_mutation_rate(opt);
   if (mode == "CoalRateForTree") return coal_rate_for_tree(opt);
+  if (mode == "MutationRateWithContext") return mutation_rate_with_context(opt);
+  if (mode == "FinalizeMutationRate") return finalize_mutation_rate(opt);
+  for (const char *m : {"MutationRateForCategory", "ForCategoryForChromosome", "ForCategoryForPopForChromosome", "MutationRateForPattern",
+                        "ForPatternForChromosome", "FinalizeForCategory", "FinalizeForPattern", "XY", "MutationDensity"})
+    if (mode == m) {
+      std::cerr << "Error: mode " << mode << " of RelateMutationRate is not part of this build: of the per-category analyses it offers MutationRateWithContext and FinalizeMutationRate; run the reference's RelateMutationRate for this one." << std::endl;
+      return 1;
+    }
   if (mode == "SubTreesForSubpopulation") return sub_trees_for_subpopulation(opt);
   if (mode == "CompareTopology") return compare_topology(opt);
   if (mode == "PairwiseCoalescence") return pairwise_coalescence(opt);
@@ -827,7 +943,7 @@ int main(int argc, char **argv) {
     if (rc == 1) return 1;  // first_section >= num_windows (BuildTopology.cpp:45)
   } else {
     std::cerr << "Mode " << mode << " is not part of this build: it replaces --mode MakeChunks, Paint, BuildTopology, FindEquivalentBranches, "
-              << "OptimizeParameters, CoalescentRateForSection, FinalizePopulationSize, Frequency, Selection, AvgMutationRate, CoalRateForTree and SubTreesForSubpopulation only; run the reference Relate for the other stages." << std::endl;
+              << "OptimizeParameters, CoalescentRateForSection, FinalizePopulationSize, Frequency, Selection, AvgMutationRate, CoalRateForTree, SubTreesForSubpopulation, MutationRateWithContext and FinalizeMutationRate only; run the reference Relate for the other stages." << std::endl;
     return 1;
   }
   if (rc != 0) {

@@ -34,6 +34,7 @@ struct HostLengths : TreeTables {
   std::vector<float> coords;    // coordinates_tree
   std::vector<int> order, lin;  // sorted_indices, num_lineages
   std::vector<int> lin_tmp;
+  float root = 0.0f;  // coordinates_tree[root] after run: the last of the sorted float coordinates
   explicit HostLengths(int n) : TreeTables(n), coords(nodes), order(nodes), lin(nodes, 0), lin_tmp(nodes) {}
 
   // parent must have passed first_bad_node, bl first_bad_length.  out: E doubles, out[E-1] = 0
@@ -61,6 +62,7 @@ struct HostLengths : TreeTables {
     lin_tmp = lin;
     for (int i = 0; i < nodes; i++) lin[i] = lin_tmp[order[i]];
     std::sort(coords.begin(), coords.end());
+    root = coords[nodes - 1];
     // GetBranchLengthsInEpoch (:228-291); the caller reads E entries of a vector shrunk to E - 1
     std::fill(out, out + E, 0.0);
     int ep = 0;
@@ -114,20 +116,12 @@ int first_bad_length(const double *bl, int N) {
   return 0;
 }
 
-// out [ntrees][E].  `where` names the trees' origin in a message; tree_id (or null: the index) what a tree is called
-int mutrate_rows(const int *parents, const double *bl, int N, int ntrees, const double *ep, int E, int device, double *out,
-                 const char *where, const int *tree_id) {
-  if (N < 2 || N > kMutrateMaxN) {
-    set_error("%s: trees of 2 <= N <= %d leaves (N=%d)", where, kMutrateMaxN, N);
-    return RL_EINVAL;
-  }
+// the trees whose flag is not kMutrateTreeDone, on the host: checked, then -- unless the device has refused them --
+// walked.  roots: null, or [ntrees]
+int host_rows(const int *parents, const double *bl, int N, int ntrees, const double *ep, int E, double *out, float *roots,
+              const char *where, const int *tree_id, const int *flags, bool refused_by_device) {
   const size_t nodes = (size_t)2 * N - 1;
   const auto tree_name = [&](int t) { return std::string(where) + ": tree " + std::to_string(tree_id ? tree_id[t] : t); };
-  std::vector<int> flags((size_t)ntrees, kMutrateTreeRefused);
-  if (device >= 0) {
-    if (const int rc = mutrate_device(parents, bl, N, ntrees, ep, E, device, out, flags.data())) return rc;
-    if (std::count(flags.begin(), flags.end(), (int)kMutrateTreeDone) == ntrees) return RL_OK;
-  }
   HostLengths host(N);
   std::vector<unsigned char> kids;
   for (int t = 0; t < ntrees; t++) {
@@ -139,10 +133,26 @@ int mutrate_rows(const int *parents, const double *bl, int N, int ntrees, const 
       set_error("%s: branch length %g of node %d is negative or not finite", tree_name(t).c_str(), b[v - 1], v - 1);
       return RL_EINVAL;
     }
-    if (device >= 0) return refuse_tree(tree_name(t).c_str(), parent, N);  // (refused by the device and not by the host)
+    if (refused_by_device) return refuse_tree(tree_name(t).c_str(), parent, N);  // (refused by the device and not by the host)
     host.run(parent, b, ep, E, out + (size_t)t * E);
+    if (roots) roots[t] = host.root;
   }
   return RL_OK;
+}
+
+// out [ntrees][E].  `where` names the trees' origin in a message; tree_id (or null: the index) what a tree is called
+int mutrate_rows(const int *parents, const double *bl, int N, int ntrees, const double *ep, int E, int device, double *out,
+                 const char *where, const int *tree_id) {
+  if (N < 2 || N > kMutrateMaxN) {
+    set_error("%s: trees of 2 <= N <= %d leaves (N=%d)", where, kMutrateMaxN, N);
+    return RL_EINVAL;
+  }
+  std::vector<int> flags((size_t)ntrees, kMutrateTreeRefused);
+  if (device >= 0) {
+    if (const int rc = mutrate_device(parents, bl, N, ntrees, ep, E, device, out, flags.data())) return rc;
+    if (std::count(flags.begin(), flags.end(), (int)kMutrateTreeDone) == ntrees) return RL_OK;
+  }
+  return host_rows(parents, bl, N, ntrees, ep, E, out, nullptr, where, tree_id, flags.data(), device >= 0);
 }
 
 // ------------------------------------------------------------------------------------------------ the file layer
@@ -257,6 +267,19 @@ int null_args(const char *who) {
 }
 
 }  // namespace
+
+int mutrate_host_rows(const int *parents, const double *bl, int N, int ntrees, const double *ep, int E, double *out,
+                      float *roots, const char *where, const int *tree_id, bool refused_by_device) {
+  if (N < 2 || N > kMutrateMaxN) {
+    set_error("%s: trees of 2 <= N <= %d leaves (N=%d)", where, kMutrateMaxN, N);
+    return RL_EINVAL;
+  }
+  const std::vector<int> flags((size_t)ntrees, kMutrateTreeRefused);
+  return host_rows(parents, bl, N, ntrees, ep, E, out, roots, where, tree_id, flags.data(), refused_by_device);
+}
+
+int mutrate_check_epochs(const char *who, const double *ep, int E) { return check_epochs(who, ep, E); }
+
 }  // namespace rl
 
 using namespace rl;

@@ -26,4 +26,19 @@ enum { kMutrateTreeDone = 0, kMutrateTreeRefused = 1 };
 int mutrate_device(const int *parents, const double *branch_length, int N, int ntrees, const double *epochs, int E,
                    int device, double *out, int *flags);
 
+// the host twin on trees [ntrees][2N-1]: out [ntrees][E]; roots (may be null) [ntrees]: the root's float time, the last
+// of the sorted coordinates.  RL_EINVAL names the tree (`where`: the trees' origin; tree_id or null: what a tree is
+// called).  with_device: the trees were refused by the device, so one the host accepts is refused too
+int mutrate_host_rows(const int *parents, const double *bl, int N, int ntrees, const double *ep, int E, double *out,
+                      float *roots, const char *where, const int *tree_id, bool refused_by_device = false);
+// RL_OK, or RL_EINVAL with the message of rl_mutrate_trees (`who` in its place)
+int mutrate_check_epochs(const char *who, const double *ep, int E);
+
+#ifdef __HIPCC__
+// the per-tree kernel on device pointers, n trees (n workgroups) on the null stream: rows [n][E] and flag [n] start at
+// 0; root (may be null) [n] floats
+hipError_t mutrate_launch(const int *par, const double *bl, const double *ep, int E, int N, int n, double *rows, int *flag,
+                          float *root);
+#endif
+
 }  // namespace rl

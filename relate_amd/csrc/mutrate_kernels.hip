@@ -36,7 +36,8 @@ constexpr int kMutrateSmallN = 2048;  // up to here a workgroup is 256 threads, 
 template <int T>
 __global__ void __launch_bounds__(T) mutrate_kernel(const int *__restrict__ PAR, const double *__restrict__ BL,
                                                     const double *__restrict__ EP, int E, int N, int ntrees,
-                                                    double *__restrict__ OUT, int *__restrict__ FLAG) {
+                                                    double *__restrict__ OUT, int *__restrict__ FLAG,
+                                                    float *__restrict__ ROOT) {
   extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
   __shared__ int bad;
   __shared__ double ep[kMutrateMaxEpochs];
@@ -53,6 +54,8 @@ __global__ void __launch_bounds__(T) mutrate_kernel(const int *__restrict__ PAR,
     if (tid == 0) FLAG[t] = kMutrateTreeRefused;
     return;
   }
+  // (MutationRateWithContext clamps a SNP's age_end to the root's time: the last of the sorted float times)
+  if (ROOT && tid == 0) ROOT[t] = S[ni - 1];
   if (wave != 0 || lane >= E) return;
 
   // ---- one lane per epoch
@@ -127,6 +130,13 @@ __global__ void __launch_bounds__(T) mutrate_kernel(const int *__restrict__ PAR,
 
 static size_t round16(size_t b) { return (b + 15) & ~(size_t)15; }
 
+hipError_t mutrate_launch(const int *par, const double *bl, const double *ep, int E, int N, int n, double *rows, int *flag,
+                          float *root) {
+  const size_t dyn = round16(8 * ((size_t)N - 1));
+  if (N <= kMutrateSmallN) return launch_with_lds(mutrate_kernel<256>, n, 256, dyn, nullptr, par, bl, ep, E, N, n, rows, flag, root);
+  return launch_with_lds(mutrate_kernel<1024>, n, 1024, dyn, nullptr, par, bl, ep, E, N, n, rows, flag, root);
+}
+
 int mutrate_device(const int *parents, const double *branch_length, int N, int ntrees, const double *epochs, int E,
                    int device, double *out, int *flags) {
   if (N < 2 || N > kMutrateMaxN) {
@@ -138,9 +148,8 @@ int mutrate_device(const int *parents, const double *branch_length, int N, int n
     return RL_EINVAL;
   }
   if (const int rc = select_device("rl_mutrate_trees", device)) return rc;
-  const size_t nodes = (size_t)2 * N - 1, ni = (size_t)N - 1;
+  const size_t nodes = (size_t)2 * N - 1;
   const int B = mutrate_batch_trees(N);
-  const size_t dyn = round16(8 * ni);
   DevBuf ep, par, bl, rows, flag;
   int rc = ep.alloc((size_t)E * 8);
   rc = rc ? rc : par.alloc((size_t)B * nodes * 4);
@@ -155,12 +164,7 @@ int mutrate_device(const int *parents, const double *branch_length, int N, int n
     RL_HIP(hipMemcpy(bl.p, branch_length + (size_t)t0 * nodes, (size_t)n * nodes * 8, hipMemcpyHostToDevice));
     RL_HIP(hipMemset(rows.p, 0, (size_t)n * E * 8));
     RL_HIP(hipMemset(flag.p, 0, (size_t)n * 4));
-    if (N <= kMutrateSmallN)
-      RL_HIP(launch_with_lds(mutrate_kernel<256>, n, 256, dyn, nullptr, par.as<int>(), bl.as<double>(), ep.as<double>(), E, N, n,
-                             rows.as<double>(), flag.as<int>()));
-    else
-      RL_HIP(launch_with_lds(mutrate_kernel<1024>, n, 1024, dyn, nullptr, par.as<int>(), bl.as<double>(), ep.as<double>(), E, N, n,
-                             rows.as<double>(), flag.as<int>()));
+    RL_HIP(mutrate_launch(par.as<int>(), bl.as<double>(), ep.as<double>(), E, N, n, rows.as<double>(), flag.as<int>(), nullptr));
     // (the copies wait for the kernel)
     RL_HIP(hipMemcpy(out + (size_t)t0 * E, rows.p, (size_t)n * E * 8, hipMemcpyDeviceToHost));
     RL_HIP(hipMemcpy(flags + t0, flag.p, (size_t)n * 4, hipMemcpyDeviceToHost));
