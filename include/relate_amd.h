@@ -239,6 +239,14 @@ int rl_debug_walk_table(const int *A4, int p0, int sh, int delta_lo, int delta_h
 #define RL_WALK_TABLE 1
 #define RL_WALK_CONSTANT 2
 int rl_debug_walk_lanes(const int *records, int lanes, int entry_delta, int *out_literal, int *out_scan);
+/* Test hook: what a device block of the library's memory cache holds when it is handed out.  Takes a block for `bytes`
+ * bytes as every device buffer of the library does, copies all of it to `out` (*got bytes: a cached block may be up
+ * to bytes / 8 + 4096 bytes larger than asked for, and `out` must hold bytes + bytes / 8 + 4096 bytes; a larger block
+ * is RL_ENOMEM and nothing is copied), then, if fill >= 0, writes the byte `fill` (0..255) over the whole block on the
+ * device, and gives the block back to the cache.  The cache returns a block as it was left: with
+ * RELATE_AMD_TEST_POISON unset a second call of the same size sees the first call's fill, with it set every call sees
+ * the poison byte. */
+int rl_debug_alloc_peek(size_t bytes, int fill, unsigned char *out, size_t *got);
 
 /* Experiment builds only (kernels compiled with -DRL_STATS and
  * RELATE_AMD_TEST_STATS set): 16 event counters of the last rl_paint. */

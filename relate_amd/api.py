@@ -181,6 +181,19 @@ def debug_wave_sum(x, sum_mode, rows_per_group=1, mismatch=None, th=0.001, nth=0
     return out, {"sums": int(st[0]), "fallbacks": int(st[1]), "walked": int(st[2]), "reruns": int(st[3])}
 
 
+def debug_alloc_peek(nbytes, fill=None):
+    """rl_debug_alloc_peek: the bytes of the device block the library's memory cache hands out for a request of
+    nbytes, all of the block (it may be larger than asked for) -> uint8 array; fill (0..255): the block is then
+    overwritten with that byte on the device before it goes back to the cache"""
+    nbytes = int(nbytes)
+    out = np.empty(nbytes + nbytes // 8 + 4096, np.uint8)
+    got = C.c_size_t()
+    f = lib().rl_debug_alloc_peek
+    f.argtypes = [C.c_size_t, C.c_int, C.c_void_p, C.POINTER(C.c_size_t)]
+    _check(f(nbytes, -1 if fill is None else int(fill), _p(out), C.byref(got)))
+    return out[:got.value].copy()
+
+
 def term_split(S):
     """rl_debug_term_split: -> (KS, R): of the S weighted terms of a backward step of tile S the exact order keeps
     the first KS in LDS and the last R in registers (host code, no GPU)"""

@@ -117,13 +117,50 @@ void cache_release(BlockCache &c, void *p, size_t bytes) {
   c.free_blocks.emplace(std::make_pair(dev, bytes), p);
   c.held += bytes;
 }
+// Test hook, RELATE_AMD_TEST_POISON=<byte> (decimal or 0x.., 0..255; read once): every block the two caches hand out
+// -- fresh, re-used, or the larger one of the out-of-memory path -- is filled with that byte first, all `got` bytes
+// of it, so that a test sees what a kernel makes of memory that is neither zero nor a previous owner's valid data
+// (tests/test_dirty_memory_gpu.py).  -1: unset, nothing changes.
+int test_poison() {
+  static const int byte = [] {
+    const char *e = getenv("RELATE_AMD_TEST_POISON");
+    if (!e || !*e) return -1;
+    char *end = nullptr;
+    const long v = strtol(e, &end, 0);
+    if (*end || v < 0 || v > 255) {
+      fprintf(stderr, "relate_amd: RELATE_AMD_TEST_POISON=%s is no byte (0..255): ignored\n", e);
+      return -1;
+    }
+    return (int)v;
+  }();
+  return byte;
+}
+// The fill of a device block is done when this returns.  It runs on a stream of the hook's own and waits for that
+// stream alone: a device-wide synchronise would wait for the tree builder's resident workers as hipFree does (above).
+// One stream per device behind one mutex; cache_alloc is called from up to 256 section threads at once.
+bool poison_device_block(void *p, size_t bytes, int byte) {
+  constexpr int kMaxDevices = 64;
+  static std::mutex m;
+  static hipStream_t streams[kMaxDevices] = {};
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= kMaxDevices) return false;
+  std::lock_guard<std::mutex> lk(m);
+  if (!streams[dev] && make_stream(&streams[dev], false) != hipSuccess) return false;
+  return hipMemsetAsync(p, byte, bytes, streams[dev]) == hipSuccess && hipStreamSynchronize(streams[dev]) == hipSuccess;
+}
 }  // namespace
 
 void *device_cache_alloc(size_t bytes, size_t *got) {
-  return cache_alloc(g_dev_cache, bytes, got, [](size_t n) -> void * {
+  void *p = cache_alloc(g_dev_cache, bytes, got, [](size_t n) -> void * {
     void *p = nullptr;
     return hipMalloc(&p, n) == hipSuccess ? p : nullptr;
   });
+  if (p && test_poison() >= 0 && !poison_device_block(p, *got, test_poison())) {
+    fprintf(stderr, "relate_amd: RELATE_AMD_TEST_POISON: the fill of a device block of %zu bytes failed\n", *got);
+    cache_release(g_dev_cache, p, *got);
+    return nullptr;
+  }
+  return p;
 }
 void device_cache_release(void *p, size_t bytes) { cache_release(g_dev_cache, p, bytes); }
 size_t device_cache_held(int device, size_t min_block) {
@@ -135,10 +172,12 @@ size_t device_cache_held(int device, size_t min_block) {
   return sum;
 }
 void *pinned_cache_alloc(size_t bytes, size_t *got) {
-  return cache_alloc(g_pin_cache, bytes, got, [](size_t n) -> void * {
+  void *p = cache_alloc(g_pin_cache, bytes, got, [](size_t n) -> void * {
     void *p = nullptr;
     return hipHostMalloc(&p, n, 0) == hipSuccess ? p : nullptr;
   });
+  if (p && test_poison() >= 0) memset(p, test_poison(), *got);
+  return p;
 }
 void pinned_cache_release(void *p, size_t bytes) { cache_release(g_pin_cache, p, bytes); }
 void device_cache_trim() {

@@ -203,6 +203,36 @@ extern "C" int rl_debug_wave_sum(const double *x, int n, int batch, int sum_mode
   return rl_debug_wave_sum_ex(x, n, batch, 1, sum_mode, nullptr, 0.0, 0.0, out, nullptr);
 }
 
+// what the memory cache hands out (common.h DevBuf): the block's bytes as they come, then a fill of the caller's
+extern "C" int rl_debug_alloc_peek(size_t bytes, int fill, unsigned char *out, size_t *got) {
+  using namespace rl;
+  if (!out || !got || fill > 255) {
+    set_error("rl_debug_alloc_peek: null out or got, or fill=%d above 255", fill);
+    return RL_EINVAL;
+  }
+  *got = 0;
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) {
+    (void)hipGetLastError();
+    set_error("no usable HIP device");
+    return RL_ENODEVICE;
+  }
+  DevBuf d;
+  int rc;
+  if ((rc = d.alloc(bytes))) return rc;
+  if (d.bytes > bytes + bytes / 8 + 4096) {
+    set_error("rl_debug_alloc_peek: a block of %zu bytes for %zu asked for: more than `out` has to hold", d.bytes, bytes);
+    return RL_ENOMEM;
+  }
+  RL_HIP(hipMemcpy(out, d.p, d.bytes, hipMemcpyDeviceToHost));
+  *got = d.bytes;
+  if (fill >= 0) {
+    RL_HIP(hipMemset(d.p, fill, d.bytes));
+    RL_HIP(hipStreamSynchronize(nullptr));
+  }
+  return RL_OK;
+}
+
 // host only: how K1's exact backward pass splits the S weighted terms of tile S (exact_sum.h) -- the first *ks through
 // LDS, the last *r in registers, the rest recomputed
 extern "C" int rl_debug_term_split(int S, int *ks, int *r) {

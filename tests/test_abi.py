@@ -88,6 +88,23 @@ def test_debug_wave_sum_refuses_bad_arguments():
     assert not out.any()
 
 
+def test_debug_alloc_peek_refuses_bad_arguments():
+    """rl_debug_alloc_peek: RL_EINVAL with a message before any device work; without a GPU a good call says so"""
+    lib = api.lib()
+    f = lib.rl_debug_alloc_peek
+    f.argtypes = [C.c_size_t, C.c_int, C.c_void_p, C.POINTER(C.c_size_t)]
+    out = np.zeros(16 + 4096, np.uint8)
+    got = C.c_size_t(7)
+    for args in ((16, -1, None, C.byref(got)), (16, -1, out.ctypes.data_as(C.c_void_p), None),
+                 (16, 256, out.ctypes.data_as(C.c_void_p), C.byref(got))):
+        assert f(*args) == -1, args[:2]  # RL_EINVAL
+        assert lib.rl_last_error().decode().startswith("rl_debug_alloc_peek:")
+    if api.device_count() == 0:
+        with pytest.raises(api.RelateError, match="no usable HIP device"):
+            api.debug_alloc_peek(16)
+    assert not out.any()
+
+
 def test_stage_opts_that_never_saw_init_are_refused():
     """a zeroed rl_stage_opts (size 0) must not silently run with the defaults: RL_EINVAL before any
     device work, from all three *_ex stages"""
