@@ -144,6 +144,14 @@ int ro_plan_target(const ro_data *d, const int *wb, int W, int k, int *site,
  * each run is summed left to right from 0.0, then an xor-butterfly (masks
  * 1..nl/2) combines the partial sums.  nl = 64 lanes; for N > 5120 a target
  * gets two wavefronts (nl = 128; relate_amd/csrc/launch.h target_waves). */
+static double lanes_butterfly(double *lane, int nl) {
+  for (int m = 1; m < nl; m <<= 1) {
+    double nxt[128];
+    for (int l = 0; l < nl; l++) nxt[l] = lane[l] + lane[l ^ m];
+    memcpy(lane, nxt, sizeof(double) * (size_t)nl);
+  }
+  return lane[0];
+}
 static double sum_lanes(const double *t, int N, int k, int nl) {
   const int q = N / nl, rem = N % nl;
   double lane[128];
@@ -155,21 +163,22 @@ static double sum_lanes(const double *t, int N, int k, int nl) {
     for (int i = 0; i < len; i++, p++) s += t[p];
     lane[l] = s;
   }
-  for (int m = 1; m < nl; m <<= 1) {
-    double nxt[128];
-    for (int l = 0; l < nl; l++) nxt[l] = lane[l] + lane[l ^ m];
-    memcpy(lane, nxt, sizeof lane);
-  }
-  return lane[0];
+  return lanes_butterfly(lane, nl);
 }
 static inline int paint_lanes(int N) { return N > 80 * 64 ? 128 : 64; }
+/* RO_SUM_LANES32 paints on a float state of its own (paint_target_lanes32);
+ * everywhere else -- the sums of ro_repaint_section -- it is the `lanes`
+ * order, as on the device (relate_amd/csrc/launch.h kernel_mode). */
+static inline int lanes_order(const ro_sum_order *o) {
+  return o != NULL && (o->mode == RO_SUM_LANES || o->mode == RO_SUM_LANES32);
+}
 
 static ro_sum_probe_fn g_probe = NULL;
 void ro_set_sum_probe(ro_sum_probe_fn fn) { g_probe = fn; }
 
 static inline double sum_alpha(const double *a, int N, int k, const ro_sum_order *o, int nl) {
   if (o != NULL && o->mode == RO_SUM_PROBE && g_probe) g_probe(a, N, 0);
-  if (o == NULL || o->mode != RO_SUM_LANES) {
+  if (!lanes_order(o)) {
     double s = 0.0;
     for (int n = 0; n < N; n++) s += a[n]; /* :300-303 */
     return s;
@@ -187,7 +196,7 @@ static inline double sum_beta(const double *b, const char *row, int k,
       scratch[n] = (seq_k > row[n]) ? c->theta * b[n] : c->ntheta * b[n];
     g_probe(scratch, N, 1);
   }
-  if (o == NULL || o->mode != RO_SUM_LANES) {
+  if (!lanes_order(o)) {
     double s = 0.0;
     for (int n = 0; n < N; n++) {
       if (seq_k > row[n])
@@ -208,6 +217,7 @@ typedef struct {
   int *site;
   double *r_prob, *nor_x_theta;
   double *a, *b, *scratch;
+  float *f32; /* the float state of RO_SUM_LANES32 */
   int cap_L, cap_N;
 } paint_ws;
 
@@ -218,10 +228,11 @@ static int ws_init(paint_ws *ws, int N, int L) {
   ws->a = (double *)malloc(sizeof(double) * (size_t)N);
   ws->b = (double *)malloc(sizeof(double) * (size_t)N);
   ws->scratch = (double *)malloc(sizeof(double) * (size_t)N);
+  ws->f32 = (float *)malloc(sizeof(float) * (size_t)N);
   ws->cap_L = L;
   ws->cap_N = N;
   return (ws->site && ws->r_prob && ws->nor_x_theta && ws->a && ws->b &&
-          ws->scratch)
+          ws->scratch && ws->f32)
              ? 0
              : -1;
 }
@@ -232,12 +243,21 @@ static void ws_free(paint_ws *ws) {
   free(ws->a);
   free(ws->b);
   free(ws->scratch);
+  free(ws->f32);
 }
+
+static int paint_target_lanes32(const ro_data *d, const paint_consts *c,
+                                const int *wb, int W, int k, paint_ws *ws,
+                                int *bsnp_begin, int *bsnp_end, float *alpha,
+                                float *beta, float *ls_alpha, float *ls_beta);
 
 static int paint_target(const ro_data *d, const paint_consts *c, const int *wb,
                         int W, int k, const ro_sum_order *order, paint_ws *ws,
                         int *bsnp_begin, int *bsnp_end, float *alpha,
                         float *beta, float *ls_alpha, float *ls_beta) {
+  if (order != NULL && order->mode == RO_SUM_LANES32)
+    return paint_target_lanes32(d, c, wb, W, k, ws, bsnp_begin, bsnp_end, alpha,
+                                beta, ls_alpha, ls_beta);
   const int N = d->N, L = d->L;
   const char *seq = d->seq;
   int *site = ws->site;
@@ -347,6 +367,211 @@ static int paint_target(const ro_data *d, const paint_consts *c, const int *wb,
     cfac *= trans_factor(c, r_prob[j]); /* :553-556 */
     while (we >= 0 && bsnp_end[we] == snp) { /* :559-578 */
       for (int n = 0; n < N; n++) beta[(size_t)we * N + n] = (float)b[n];
+      ls_beta[we] = (float)ls;
+      we--;
+    }
+  }
+  assert(we == -1);
+  return D;
+}
+
+/* ------------------------------------------------------------------ */
+/* RO_SUM_LANES32: the order of the HIP RL_SUM_LANES32 kernels, the packed-FP32
+ * stepping-stone pass.  This restates THIS PROJECT'S kernel, not the reference:
+ * citations "p32:" are to relate_amd/csrc/paint32_kernels.hip, "ctx:" to
+ * relate_amd/csrc/context.cpp.  Every float operator below is one IEEE
+ * binary32 operation (round to nearest even, denormals kept: the device code
+ * objects are built with float_denorm_mode_32 = 3 and float_round_mode_32 = 0,
+ * the default of the library's build, which passes no denormal flag; this file
+ * is built without fast-math, so the host keeps them too).
+ *
+ * Layout (paint_device.h PaintLane): all N donors in donor order are cut into
+ * nl = paint_lanes(N) balanced runs as in sum_lanes; the donor at position i
+ * of its run sits in half i & 1 of register pair i / 2.  The target's own slot
+ * is forced before every update so that it comes out +0.0; slots past a run
+ * hold +0.0, are in no mask and change no sum, so the runs are walked to their
+ * own lengths. */
+typedef struct {
+  float init0, init1, K1; /* (float) of PaintConsts' doubles, p32:183,217,317 */
+  double K1d, inv_theta, inv_ntheta, dtheta;
+} consts32;
+
+static void consts32_init(consts32 *f, const paint_consts *c) {
+  /* ctx:234-253 make_consts.  K1 = theta_ratio + 1.0, init0 = prior_ntheta,
+   * init1 = prior_theta + prior_ntheta; the reciprocals are IEEE divisions. */
+  f->K1d = c->theta_ratio + 1.0;
+  f->K1 = (float)f->K1d;
+  f->init0 = (float)c->prior_ntheta;
+  f->init1 = (float)(c->prior_theta + c->prior_ntheta);
+  f->inv_theta = 1.0 / c->theta;
+  f->inv_ntheta = 1.0 / c->ntheta;
+  f->dtheta = c->theta - c->ntheta; /* p32:364, formed in every step */
+}
+
+/* The forward sum of one step (p32:197-206 at SNP 0, :230,250-251,256-257
+ * after it): per lane four float chains -- pairs 0,2,4,.. into `sa`, pairs
+ * 1,3,5,.. into `sb`, the halves apart --, then sa += sb, then the halves in
+ * double; the lanes by the butterfly of sum_lanes. */
+static double sum_alpha32(const float *a, int N, int nl) {
+  const int q = N / nl, rem = N % nl;
+  double lane[128];
+  int p = 0;
+  for (int l = 0; l < nl; l++) {
+    const int len = q + (l < rem ? 1 : 0);
+    float sa[2] = {0.f, 0.f}, sb[2] = {0.f, 0.f};
+    for (int i = 0; i < len; i++, p++) {
+      if ((i >> 1) & 1)
+        sb[i & 1] = sb[i & 1] + a[p];
+      else
+        sa[i & 1] = sa[i & 1] + a[p];
+    }
+    sa[0] = sa[0] + sb[0];
+    sa[1] = sa[1] + sb[1];
+    lane[l] = (double)sa[0] + (double)sa[1];
+  }
+  return lanes_butterfly(lane, nl);
+}
+
+/* The backward sum (p32:333-334, 351-352 masked_fma_acc_f32x4 :93-110,
+ * :356, :363-364): `sall` is one packed chain over all new pairs in register
+ * order (its halves apart); smis0 / smis1 take the new .x / .y halves that
+ * mismatch at THIS site; the lane's value is two double products and a sum. */
+static double sum_beta32(const float *b, const char *row, int k, int N,
+                         const paint_consts *c, const consts32 *f, int nl) {
+  const int q = N / nl, rem = N % nl;
+  const char seq_k = row[k];
+  double lane[128];
+  int p = 0;
+  for (int l = 0; l < nl; l++) {
+    const int len = q + (l < rem ? 1 : 0);
+    float sall[2] = {0.f, 0.f}, smis[2] = {0.f, 0.f};
+    for (int i = 0; i < len; i++, p++) {
+      if (seq_k > row[p]) smis[i & 1] = smis[i & 1] + b[p];
+      sall[i & 1] = sall[i & 1] + b[p];
+    }
+    const double lane_all = (double)sall[0] + (double)sall[1];
+    const double lane_mis = (double)smis[0] + (double)smis[1];
+    lane[l] = c->ntheta * lane_all + f->dtheta * lane_mis;
+  }
+  return lanes_butterfly(lane, nl);
+}
+
+static int paint_target_lanes32(const ro_data *d, const paint_consts *c,
+                                const int *wb, int W, int k, paint_ws *ws,
+                                int *bsnp_begin, int *bsnp_end, float *alpha,
+                                float *beta, float *ls_alpha, float *ls_beta) {
+  const int N = d->N, L = d->L, nl = paint_lanes(N);
+  const char *seq = d->seq;
+  int *site = ws->site;
+  double *r_prob = ws->r_prob, *nxt = ws->nor_x_theta;
+  float *a = ws->f32, *b = ws->f32;
+  consts32 f;
+  consts32_init(&f, c);
+
+  const int D =
+      plan_target(d, c, wb, W, k, site, r_prob, nxt, bsnp_begin, bsnp_end);
+
+  /* ---------------- forward, paint32_forward (p32:167-274) ------------- */
+  int wa = 0;
+  {
+    const char *row = seq; /* SNP 0, p32:183-196 */
+    const char seq_k = row[k];
+    for (int n = 0; n < N; n++) a[n] = (seq_k > row[n]) ? f.init1 : f.init0;
+    a[k] = 0.0f;
+  }
+  double S = sum_alpha32(a, N, nl); /* p32:207 */
+  double ls = 0.0;
+  while (wa < W && bsnp_begin[wa] == 0) { /* p32:210-213 */
+    memcpy(alpha + (size_t)wa * N, a, sizeof(float) * (size_t)N);
+    alpha[(size_t)wa * N + k] = 0.0f; /* paint_pass.h write_forward_stone */
+    ls_alpha[wa] = (float)ls;
+    wa++;
+  }
+  double cfac = trans_factor(c, r_prob[0]) * S; /* p32:214 */
+  for (int i = 1; i < D; i++) {
+    const int snp = site[i];
+    const char *row = seq + (size_t)snp * N;
+    const char seq_k = row[k];
+    const float cf32 = (float)cfac; /* p32:227 */
+    a[k] = -cf32;                   /* p32:228: (-c) + c = +0.0 */
+    for (int n = 0; n < N; n++) {   /* p32:231-252 */
+      float v = a[n] + cf32;                /* v_pk_add_f32 / masked add */
+      if (seq_k > row[n]) v = v * f.K1;     /* masked v_mul_f32, p32:44-76 */
+      a[n] = v;
+    }
+    S = sum_alpha32(a, N, nl); /* p32:256-257 */
+    ls += nxt[i - 1];          /* p32:258 */
+    cfac = S;
+    if (cfac < c->lower || cfac > c->upper) { /* p32:260-266 */
+      const float inv = (float)(1.0 / S);     /* the reciprocal, not a/S */
+      for (int n = 0; n < N; n++) a[n] = a[n] * inv;
+      ls += log(S);
+      cfac = 1.0;
+    }
+    cfac *= trans_factor(c, r_prob[i]); /* p32:267, the plan's double factor */
+    while (wa < W && bsnp_begin[wa] == snp) { /* p32:268-271 */
+      memcpy(alpha + (size_t)wa * N, a, sizeof(float) * (size_t)N);
+      alpha[(size_t)wa * N + k] = 0.0f;
+      ls_alpha[wa] = (float)ls;
+      wa++;
+    }
+  }
+  assert(wa == W);
+
+  /* ---------------- backward, paint32_backward (p32:276-381) ----------- */
+  ls = (double)log(c->Nminusone) - D * c->log_ntheta; /* p32:291 */
+  int we = W - 1;
+  double B = 0.0;
+  {
+    const char *row = seq + (size_t)(L - 1) * N;
+    const char seq_k = row[k];
+    for (int n = 0; n < N; n++) b[n] = 1.0f; /* p32:293-300 */
+    b[k] = 0.0f;                             /* p32:301 */
+    /* p32:302 binit: the serial sum of constants of the host plan
+     * (ctx:365-377), as paint_target has it */
+    for (int n = 0; n < N; n++) {
+      if (seq_k > row[n])
+        B += c->theta;
+      else
+        B += c->ntheta;
+    }
+    B -= c->ntheta;
+  }
+  while (we >= 0 && bsnp_end[we] == L - 1) { /* p32:304-307 */
+    memcpy(beta + (size_t)we * N, b, sizeof(float) * (size_t)N);
+    beta[(size_t)we * N + k] = 1.0f; /* beta[k] = 1 at the last SNP */
+    ls_beta[we] = (float)ls;
+    we--;
+  }
+  cfac = trans_factor(c, r_prob[D - 1]) * B; /* p32:308 */
+  for (int j = D - 2; j >= 0; j--) {
+    const int snp = site[j], snp_next = site[j + 1];
+    const char *row_next = seq + (size_t)snp_next * N;
+    const char seqk_next = row_next[k];
+    const double b1d = cfac * f.inv_ntheta;       /* p32:328 */
+    const double btd = cfac * f.inv_theta - b1d;  /* p32:329 */
+    const float b1 = (float)b1d;                  /* p32:330 */
+    const float btK = (float)(btd * f.K1d);       /* p32:330 */
+    b[k] = -b1;                                   /* p32:331 */
+    for (int n = 0; n < N; n++) {                 /* p32:337-357 */
+      float v = b[n] + b1;
+      /* mismatch at the later site: one v_fma_f32, one rounding (p32:97-100) */
+      if (seqk_next > row_next[n]) v = fmaf(v, f.K1, btK);
+      b[n] = v;
+    }
+    B = sum_beta32(b, seq + (size_t)snp * N, k, N, c, &f, nl); /* p32:363-364 */
+    ls += nxt[j + 1]; /* p32:365 */
+    cfac = B;
+    if (cfac < c->lower || cfac > c->upper) { /* p32:367-373 */
+      const float inv = (float)(1.0 / B);
+      for (int n = 0; n < N; n++) b[n] = b[n] * inv;
+      ls += ro_fast_log((float)B);
+      cfac = 1.0;
+    }
+    cfac *= trans_factor(c, r_prob[j]); /* p32:374 */
+    while (we >= 0 && bsnp_end[we] == snp) { /* p32:375-378 */
+      memcpy(beta + (size_t)we * N, b, sizeof(float) * (size_t)N);
+      beta[(size_t)we * N + k] = 0.0f;
       ls_beta[we] = (float)ls;
       we--;
     }

@@ -42,8 +42,21 @@ typedef struct {
  *                   n != k are cut into 64 contiguous, balanced runs, each run
  *                   summed left to right, then an xor-butterfly over the 64
  *                   partial sums (masks 1,2,4,8,16,32).  Used to check those
- *                   kernels bit for bit; it is NOT the reference order. */
-enum { RO_SUM_SERIAL = 0, RO_SUM_LANES = 1, RO_SUM_PROBE = 2 };
+ *                   kernels bit for bit; it is NOT the reference order.
+ *   RO_SUM_LANES32: the arithmetic of the HIP RL_SUM_LANES32 kernels
+ *                   (relate_amd/csrc/paint32_kernels.hip), restated step by
+ *                   step: the per-donor state of the stepping-stone passes is
+ *                   a float, updated by single float operations (one fused
+ *                   multiply-add in the backward pass), rescaled by a float
+ *                   reciprocal; each of the 64 (N > 5120: 128) runs is summed
+ *                   in float chains by register pair and half, widened, and
+ *                   the runs are combined by the butterfly of RO_SUM_LANES in
+ *                   double.  ro_paint_stepping_stones and ro_paint_chunk take
+ *                   it; in ro_repaint_section it means RO_SUM_LANES, as on the
+ *                   device, whose RePaint has no float mode.  Used to check
+ *                   those kernels bit for bit; it is the DEVICE's order and
+ *                   arithmetic, NOT the reference's (which keeps doubles). */
+enum { RO_SUM_SERIAL = 0, RO_SUM_LANES = 1, RO_SUM_PROBE = 2, RO_SUM_LANES32 = 3 };
 /* RO_SUM_PROBE (experiments, tools/exact_sum_stats.py): the serial order, and
  * every normalising sum's term vector is shown to ro_sum_probe first
  * (dir 0: forward, alpha; 1: backward, e(n)*beta).  Not thread-safe. */

@@ -1,6 +1,6 @@
 // paint32_kernels.hip -- K1 in the FAST mode RL_SUM_LANES32: stepping-stone painting with the per-donor state in
 // packed FP32 (fast_painting.cpp:288-303, 481-503 restated, NOT bit-identical to the reference).
-//
+// Held bit for bit to RO_SUM_LANES32 (oracle/relate_oracle.c), which restates THIS file: tests/test_lanes32_gpu.py.
 // Why: the exact kernels are bound by FP64 issue -- 3 (forward) + 6 (backward) instructions per donor and site before
 // any summation order is paid for, and FP64 / non-packed FP32 instructions issue at one per lane and cycle.  Only the
 // PACKED FP32 forms (v_pk_add_f32, v_pk_mul_f32, v_pk_fma_f32: two donors per lane and instruction) go faster.  The

@@ -26,6 +26,9 @@ class RoSumOrder(C.Structure):
     _fields_ = [("mode", C.c_int), ("seg", C.c_int), ("nwaves", C.c_int)]
 
 
+# summation orders of the oracle (oracle/relate_oracle.h)
+RO_SUM_SERIAL, RO_SUM_LANES, RO_SUM_PROBE, RO_SUM_LANES32 = 0, 1, 2, 3
+
 _oracle = None
 
 

@@ -13,8 +13,8 @@ the GPU suite runs its steps in fresh processes, or on blocks that hold an earli
 
 No expected value comes from a device run: the modes are held to their host twins (device=None), computed in this
 process; files to the reference's bytes in tests/golden; the core to the golden fixtures and the oracle through the
-helpers of the tests that hold it to them today.  Everything is compared bit for bit, but for RL_SUM_LANES32, which
-keeps the bound and the reference of test_lanes32_gpu.compare.
+helpers of the tests that hold it to them today.  Everything is compared bit for bit, RL_SUM_LANES32 too: with
+test_lanes32_gpu.compare against RO_SUM_LANES32, the oracle's restatement of that order (and its floor over all targets).
 
 Every step that uses the GPU is a child process under a time limit of its own (rlutil.gpu_step), and the hook reaches it
 through the child's environment alone.  A child is this file, run as a script with the name of a step:

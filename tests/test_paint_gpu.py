@@ -11,13 +11,14 @@ pytestmark = pytest.mark.gpu
 
 
 def oracle_stones(ch, k, lanes):
+    """lanes: False / True (the serial and the `lanes` order), or an order of the oracle by number (rlutil.RO_SUM_*)"""
     o = rlutil.oracle()
     N, W = ch.N, ch.W
     bb = np.zeros(W, np.int32); be = np.zeros(W, np.int32)
     al = np.zeros((W, N), np.float32); bt = np.zeros((W, N), np.float32)
     la = np.zeros(W, np.float32); lb = np.zeros(W, np.float32)
     d = ch.ro()
-    order = rlutil.RoSumOrder(1 if lanes else 0, 0, 0)
+    order = rlutil.RoSumOrder(int(lanes), 0, 0)
     D = o.ro_paint_stepping_stones(C.byref(d), ch.wb.ctypes.data_as(C.c_void_p), W, k, C.byref(order),
                                    bb.ctypes.data_as(C.c_void_p), be.ctypes.data_as(C.c_void_p),
                                    al.ctypes.data_as(C.c_void_p), bt.ctypes.data_as(C.c_void_p),
