@@ -310,6 +310,15 @@ rl_window *rl_window_open_bounded(rl_ctx *ctx, int w, const char *paint_file,
                                   int first_snp, int sum_mode,
                                   long long max_rows, float *kernel_ms);
 int rl_window_repaints(const rl_window *win);
+/* Tests: where the window's last RePaint launch put target t (global index).
+ * out8 = row_lo, row_hi (the resident posterior rows [lo, hi)), start_row,
+ * save_row (the kept backward state the launch started from / left, -1:
+ * none), fstart_row, fsave_row (the forward state likewise), 1 if the launch
+ * was a part launch, 1 if its backward kernel ran without the LDS strip.
+ * Host bookkeeping only: nothing is launched, no kernel argument changes.
+ * RL_EINVAL for a null window or output and for t outside the window's
+ * targets. */
+int rl_debug_window_place(const rl_window *win, int t, int32_t *out8);
 void rl_window_close(rl_window *win);
 int rl_window_bounds(const rl_window *win, int *start, int *end);
 /* rows D_n of target n's topology and copies of it (tests / debugging):

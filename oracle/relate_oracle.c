@@ -791,11 +791,12 @@ long long ro_paint_sample(const ro_data *d, const int *wb, int W, int k0,
 
 /* ------------------------------------------------------------------ */
 /* RePaintSection, fast_painting.cpp:621-1092                          */
-int ro_repaint_section(const ro_data *d, const float *alpha_begin,
-                       const float *beta_end, int first_snp, int last_snp,
-                       float logscale_alpha, float logscale_beta, int k,
-                       const ro_sum_order *order, float *topology,
-                       float *logscales) {
+static int repaint_section(const ro_data *d, const float *alpha_begin,
+                           const float *beta_end, int first_snp, int last_snp,
+                           float logscale_alpha, float logscale_beta, int k,
+                           const ro_sum_order *order, float *topology,
+                           float *logscales, unsigned char *fwd_rescaled,
+                           unsigned char *bwd_rescaled) {
   const int N = d->N;
   const char *seq = d->seq;
   paint_consts cc;
@@ -833,6 +834,8 @@ int ro_repaint_section(const ro_data *d, const float *alpha_begin,
   double *alpha = (double *)malloc(sizeof(double) * (size_t)D * N);
   double *b = (double *)malloc(sizeof(double) * (size_t)N);
   for (int i = 0; i < D; i++) logscales[i] = 0.0f;
+  if (fwd_rescaled) memset(fwd_rescaled, 0, (size_t)D);
+  if (bwd_rescaled) memset(bwd_rescaled, 0, (size_t)D);
 
   /* ---------------- forward (:769-885) ---------------- */
   logscales[0] = logscale_alpha;
@@ -864,6 +867,7 @@ int ro_repaint_section(const ro_data *d, const float *alpha_begin,
       prev_logscale += log(tmp);
       logscales[i] = (float)(logscales[i] + log(tmp));
       cfac = 1.0;
+      if (fwd_rescaled) fwd_rescaled[i] = 1;
     }
     cfac *= trans_factor(c, r_prob[i]);
   }
@@ -907,12 +911,34 @@ int ro_repaint_section(const ro_data *d, const float *alpha_begin,
       prev_logscale += log(tmp);
       logscales[j] = (float)(logscales[j] + log(tmp));
       cfac = 1.0;
+      if (bwd_rescaled) bwd_rescaled[j] = 1;
     }
     cfac *= trans_factor(c, r_prob[j]);
   }
 
   free(site); free(r_prob); free(nxt); free(scratch); free(alpha); free(b);
   return D;
+}
+
+int ro_repaint_section(const ro_data *d, const float *alpha_begin,
+                       const float *beta_end, int first_snp, int last_snp,
+                       float logscale_alpha, float logscale_beta, int k,
+                       const ro_sum_order *order, float *topology,
+                       float *logscales) {
+  return repaint_section(d, alpha_begin, beta_end, first_snp, last_snp,
+                         logscale_alpha, logscale_beta, k, order, topology,
+                         logscales, NULL, NULL);
+}
+
+int ro_repaint_section_flags(const ro_data *d, const float *alpha_begin,
+                             const float *beta_end, int first_snp, int last_snp,
+                             float logscale_alpha, float logscale_beta, int k,
+                             const ro_sum_order *order, float *topology,
+                             float *logscales, unsigned char *fwd_rescaled,
+                             unsigned char *bwd_rescaled) {
+  return repaint_section(d, alpha_begin, beta_end, first_snp, last_snp,
+                         logscale_alpha, logscale_beta, k, order, topology,
+                         logscales, fwd_rescaled, bwd_rescaled);
 }
 
 /* ------------------------------------------------------------------ */
@@ -968,6 +994,9 @@ struct ro_window {
   float **log;    /* D_n floats */
   int *v_snp_prev;
   double *v_rpos_prev, *v_rpos_next;
+  const ro_sum_order *order; /* of the repaint (ro_window_open_targets) */
+  ro_sum_order order_copy;
+  const unsigned char *wanted; /* [N] targets to repaint, NULL: all */
 };
 
 typedef struct {
@@ -987,6 +1016,7 @@ static void *repaint_worker(void *arg) {
   float *be = (float *)malloc(sizeof(float) * (size_t)N);
   j->rc = 0;
   for (int n = j->n0; n < j->n1; n += j->stride) {
+    if (w->wanted && !w->wanted[n]) continue;
     const unsigned char *p = j->buf + j->off[n];
     size_t avail = j->len - j->off[n];
     int bb, bend;
@@ -1000,8 +1030,8 @@ static void *repaint_worker(void *arg) {
     int cap = bend - bb + 2;
     w->top[n] = (float *)malloc(sizeof(float) * (size_t)cap * N);
     w->log[n] = (float *)malloc(sizeof(float) * (size_t)cap);
-    w->rows[n] = ro_repaint_section(w->d, ab, be, bb, bend, la, lb, n, NULL,
-                                    w->top[n], w->log[n]);
+    w->rows[n] = ro_repaint_section(w->d, ab, be, bb, bend, la, lb, n,
+                                    w->order, w->top[n], w->log[n]);
   }
   free(ab); free(be);
   return NULL;
@@ -1009,18 +1039,38 @@ static void *repaint_worker(void *arg) {
 
 ro_window *ro_window_open(const ro_data *d, const char *paint_file, int snp,
                           int nthreads) {
+  return ro_window_open_targets(d, paint_file, snp, nthreads, NULL, NULL, 0);
+}
+
+ro_window *ro_window_open_targets(const ro_data *d, const char *paint_file,
+                                  int snp, int nthreads,
+                                  const ro_sum_order *order,
+                                  const int *targets, int ntargets) {
   const int N = d->N, L = d->L;
+  unsigned char *wanted = NULL;
+  if (targets) {
+    wanted = (unsigned char *)calloc((size_t)N, 1);
+    for (int i = 0; i < ntargets; i++) {
+      if (targets[i] < 0 || targets[i] >= N) { free(wanted); return NULL; }
+      wanted[targets[i]] = 1;
+    }
+  }
   FILE *fp = fopen(paint_file, "rb");
   if (!fp) return NULL;
   fseek(fp, 0, SEEK_END);
   size_t len = (size_t)ftell(fp);
   fseek(fp, 0, SEEK_SET);
   unsigned char *buf = (unsigned char *)malloc(len);
-  if (fread(buf, 1, len, fp) != len) { fclose(fp); free(buf); return NULL; }
+  if (fread(buf, 1, len, fp) != len) { fclose(fp); free(buf); free(wanted); return NULL; }
   fclose(fp);
 
   ro_window *w = (ro_window *)calloc(1, sizeof(ro_window));
   w->d = d;
+  w->wanted = wanted;
+  if (order) {
+    w->order_copy = *order;
+    w->order = &w->order_copy;
+  }
   w->rows = (int *)calloc((size_t)N, sizeof(int));
   w->top = (float **)calloc((size_t)N, sizeof(float *));
   w->log = (float **)calloc((size_t)N, sizeof(float *));
@@ -1089,6 +1139,7 @@ void ro_window_free(ro_window *w) {
     for (int n = 0; n < w->d->N; n++) free(w->log[n]);
   free(w->top); free(w->log); free(w->rows);
   free(w->v_snp_prev); free(w->v_rpos_prev); free(w->v_rpos_next);
+  free((void *)w->wanted);
   free(w);
 }
 
@@ -1103,31 +1154,44 @@ void ro_window_advance(ro_window *w, int snp) {
   }
 }
 
+static void window_matrix_row(ro_window *w, int snp, int n, float *row);
+
 void ro_window_matrix(ro_window *w, int snp, float *matrix) {
+  const int N = w->d->N;
+  for (int n = 0; n < N; n++)
+    if (w->top[n]) window_matrix_row(w, snp, n, matrix + (size_t)n * N);
+}
+
+int ro_window_matrix_row(ro_window *w, int snp, int n, float *row) {
+  if (!w || n < 0 || n >= w->d->N || !w->top[n]) return -1;
+  window_matrix_row(w, snp, n, row);
+  return 0;
+}
+
+/* row n of GetMatrix(snp) (anc_builder.cpp:116-194) */
+static void window_matrix_row(ro_window *w, int snp, int n, float *row) {
   const ro_data *d = w->d;
   const int N = d->N, L = d->L;
-  for (int n = 0; n < N; n++) {
-    const int p = w->v_snp_prev[n];
-    const int direct =
-        (d->seq[(size_t)snp * N + n] == '1' || snp == 0 || snp == L - 1);
-    if (direct) {
-      ro_distance_row(N, n, 1, w->top[n] + (size_t)p * N, NULL, w->log[n][p],
-                      0.0f, 0, 0, 0, matrix + (size_t)n * N);
-    } else {
-      if (w->v_rpos_next[n] <= w->v_rpos_prev[n]) { /* :134-141 */
-        for (int l = snp; l < L; l++) {
-          if (d->seq[(size_t)l * N + n] == '1' || l == L - 1) {
-            w->v_rpos_next[n] = d->rpos[l];
-            break;
-          }
-        }
+  const int p = w->v_snp_prev[n];
+  const int direct =
+      (d->seq[(size_t)snp * N + n] == '1' || snp == 0 || snp == L - 1);
+  if (direct) {
+    ro_distance_row(N, n, 1, w->top[n] + (size_t)p * N, NULL, w->log[n][p],
+                    0.0f, 0, 0, 0, row);
+    return;
+  }
+  if (w->v_rpos_next[n] <= w->v_rpos_prev[n]) { /* :134-141 */
+    for (int l = snp; l < L; l++) {
+      if (d->seq[(size_t)l * N + n] == '1' || l == L - 1) {
+        w->v_rpos_next[n] = d->rpos[l];
+        break;
       }
-      ro_distance_row(N, n, 0, w->top[n] + (size_t)p * N,
-                      w->top[n] + (size_t)(p + 1) * N, w->log[n][p],
-                      w->log[n][p + 1], w->v_rpos_prev[n], w->v_rpos_next[n],
-                      d->rpos[snp], matrix + (size_t)n * N);
     }
   }
+  ro_distance_row(N, n, 0, w->top[n] + (size_t)p * N,
+                  w->top[n] + (size_t)(p + 1) * N, w->log[n][p],
+                  w->log[n][p + 1], w->v_rpos_prev[n], w->v_rpos_next[n],
+                  d->rpos[snp], row);
 }
 
 int ro_window_rows(const ro_window *w, int n) { return w->rows[n]; }

@@ -125,6 +125,18 @@ int ro_repaint_section(const ro_data *d, const float *alpha_begin,
                        const ro_sum_order *order, float *topology,
                        float *logscales);
 
+/* The same computation, and where it rescaled (tests of the device kernels'
+ * rescale paths): fwd_rescaled[i] = 1 if the forward step into row i divided
+ * by its sum (:865-877), bwd_rescaled[j] = 1 if the backward step at row j did
+ * (:1047-1061); D entries each (caller allocates as for logscales), either
+ * may be NULL. */
+int ro_repaint_section_flags(const ro_data *d, const float *alpha_begin,
+                             const float *beta_end, int bsnp_begin, int bsnp_end,
+                             float ls_alpha, float ls_beta, int k,
+                             const ro_sum_order *order, float *topology,
+                             float *logscales, unsigned char *fwd_rescaled,
+                             unsigned char *bwd_rescaled);
+
 /* One row of DistanceMeasure::GetMatrix (anc_builder.cpp:116-194).
  *   top_prev/top_next : rows v_snp_prev[n] and v_snp_prev[n]+1 of target n's
  *                       topology (top_next may be NULL when `direct`)
@@ -143,6 +155,17 @@ typedef struct ro_window ro_window;
  * and repaint every target.  snp = first SNP the matrix is asked for. */
 ro_window *ro_window_open(const ro_data *d, const char *paint_file, int snp,
                           int nthreads);
+/* The same for the listed targets only (targets NULL: all), repainted in
+ * `order` (NULL: the reference's): the window of a panel too large to repaint
+ * every target on the CPU.  The rows, cursors and matrix rows of the listed
+ * targets are those of the whole window; ro_window_matrix leaves the rows of
+ * the others untouched. */
+ro_window *ro_window_open_targets(const ro_data *d, const char *paint_file,
+                                  int snp, int nthreads,
+                                  const ro_sum_order *order,
+                                  const int *targets, int ntargets);
+/* Row n of GetMatrix(snp) (N floats); -1 if n was not repainted. */
+int ro_window_matrix_row(ro_window *w, int snp, int n, float *row);
 void ro_window_free(ro_window *w);
 /* BuildTopology's cursor update for carriers of `snp`
  * (anc_builder.cpp:487-495). */

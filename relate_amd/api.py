@@ -463,6 +463,14 @@ class Window:
         """times RePaintSection has run for this window (> 1 only for a bounded one)"""
         return lib().rl_window_repaints(C.c_void_p(self._h))
 
+    def place(self, n):
+        """rl_debug_window_place: where the last RePaint launch put target n -> dict(row_lo, row_hi, start_row,
+        save_row, fstart_row, fsave_row, partial, nostrip); host bookkeeping, nothing is launched"""
+        out = np.zeros(8, np.int32)
+        _check(lib().rl_debug_window_place(C.c_void_p(self._h), int(n), _p(out)))
+        keys = ("row_lo", "row_hi", "start_row", "save_row", "fstart_row", "fsave_row", "partial", "nostrip")
+        return dict(zip(keys, (int(x) for x in out)))
+
     def topology(self, n):
         D, N = self.rows(n), self.ctx.N
         top = np.empty((D, N), np.float32)

@@ -57,6 +57,7 @@ struct rl_window {
   int64_t cap_rows = 0;                      // rows d_top holds; >= all rows: the whole window is resident
   int maxD = 0, sum_mode = 0, repaints = 0;
   bool have_logscales = false;
+  bool last_partial = false, last_nostrip = false;  // what the last launch was (rl_debug_window_place)
   // a window's distance matrices run on its own stream: the sections of a stage ask for theirs at the same time
   hipStream_t stream = nullptr;
   hipEvent_t e0 = nullptr, e2 = nullptr;
@@ -189,6 +190,8 @@ static int repaint_rows(rl_window *win, float *kernel_ms) {
   one_at_a_time.unlock();
   win->t_launch += std::chrono::duration<double>(std::chrono::steady_clock::now() - t_got).count();
   win->repaints++;
+  win->last_partial = p.partial != 0;
+  win->last_nostrip = p.partial && p.nostrip;  // (launch_repaint's rule for the strip-less backward kernel)
   for (size_t t = 0; t < win->save_row.size(); t++) {
     if (win->save_row[t] >= 0) win->b_row[t] = win->save_row[t];
     if (win->fsave_row[t] >= 0) win->f_row[t] = win->fsave_row[t];
@@ -608,6 +611,29 @@ rl_window *rl_window_open_bounded(rl_ctx *ctx, int w, const char *paint_file, in
 void rl_window_close(rl_window *win) { delete win; }
 
 int rl_window_repaints(const rl_window *win) { return win ? win->repaints : RL_EINVAL; }
+
+// Where the window's last launch put target t (host bookkeeping of place_rows / repaint_rows; nothing is launched).
+int rl_debug_window_place(const rl_window *win, int t, int32_t *out8) {
+  if (!win || !out8) {
+    set_error("rl_debug_window_place: null window or output");
+    return RL_EINVAL;
+  }
+  if (t < win->k0 || t >= win->k0 + win->nloc) {
+    set_error("rl_debug_window_place: target %d outside the window's range [%d, %d)", t, win->k0, win->k0 + win->nloc);
+    return RL_EINVAL;
+  }
+  const size_t i = (size_t)(t - win->k0);
+  auto at = [&](const std::vector<int32_t> &v) { return i < v.size() ? v[i] : -1; };
+  out8[0] = at(win->row_lo);
+  out8[1] = at(win->row_hi);
+  out8[2] = at(win->start_row);
+  out8[3] = at(win->save_row);
+  out8[4] = at(win->fstart_row);
+  out8[5] = at(win->fsave_row);
+  out8[6] = win->last_partial ? 1 : 0;
+  out8[7] = win->last_nostrip ? 1 : 0;
+  return RL_OK;
+}
 
 int rl_window_bounds(const rl_window *win, int *start, int *end) {
   if (!win) return RL_EINVAL;

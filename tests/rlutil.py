@@ -49,7 +49,13 @@ def oracle():
         lib.ro_paint_chunk.restype = C.c_int
         lib.ro_paint_sample.restype = C.c_longlong
         lib.ro_repaint_section.restype = C.c_int
+        lib.ro_repaint_section_flags.restype = C.c_int
         lib.ro_window_open.restype = C.c_void_p
+        lib.ro_window_open_targets.restype = C.c_void_p
+        lib.ro_window_open_targets.argtypes = [C.c_void_p, C.c_char_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                               C.c_int]
+        lib.ro_window_matrix_row.restype = C.c_int
+        lib.ro_window_matrix_row.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
         lib.ro_window_top.restype = C.c_void_p
         lib.ro_window_log.restype = C.c_void_p
         lib.ro_stone_max_bytes.restype = C.c_size_t

@@ -105,6 +105,19 @@ def test_debug_alloc_peek_refuses_bad_arguments():
     assert not out.any()
 
 
+def test_debug_window_place_refuses_bad_arguments():
+    """rl_debug_window_place: RL_EINVAL with a message for a null window or output, nothing written (a target outside
+    the window's range: test_repaint_geometry_gpu.py, it needs a window)"""
+    lib = api.lib()
+    f = lib.rl_debug_window_place
+    f.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
+    out = np.full(8, 7, np.int32)
+    assert f(None, 0, out.ctypes.data_as(C.c_void_p)) == -1  # RL_EINVAL
+    assert lib.rl_last_error().decode().startswith("rl_debug_window_place:")
+    assert f(None, 0, None) == -1
+    assert (out == 7).all()
+
+
 def test_stage_opts_that_never_saw_init_are_refused():
     """a zeroed rl_stage_opts (size 0) must not silently run with the defaults: RL_EINVAL before any
     device work, from all three *_ex stages"""

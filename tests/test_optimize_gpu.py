@@ -141,7 +141,7 @@ def numpy_cancel(d, carriers, log_ratio):
     return d, off.min(axis=1)
 
 
-@pytest.mark.parametrize("N", [5, 64, 65, 1000])
+@pytest.mark.parametrize("N", [5, 64, 65, 1000, 5120, 5121, 10240])
 @pytest.mark.parametrize("who", ["none", "all", "one", "random"])
 def test_cancel_rowmin_kernel_bitwise(N, who):
     rng = np.random.default_rng(1000 * N + ["none", "all", "one", "random"].index(who))
