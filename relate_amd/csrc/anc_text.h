@@ -1,7 +1,10 @@
 // anc_text.h -- the text inputs of the modes that read a dated tree sequence (coalrate.cpp: CoalescentRateForSection;
-// frequency.cpp: Frequency): a text file that is refused when compressed, and the text .anc one tree at a time; and
-// the writer of the text .anc for the modes that write one (subtrees.cpp: SubTreesForSubpopulation).  `mode` is the
-// name a message starts with.
+// frequency.cpp: Frequency; mutrate.cpp: AvgMutationRate; coaltree.cpp: CoalRateForTree; mutctx.cpp:
+// MutationRateWithContext; subtrees.cpp: SubTreesForSubpopulation): a text file that is refused when compressed, and
+// the text .anc one tree at a time (AncText); the two walks over its trees in batches -- the trees that carry a wanted
+// SNP (SnpTreeBatches: mutrate, frequency, mutctx) and every tree with a factor (FactorTreeBatches: coalrate,
+// coaltree); and the writer of the text .anc for the modes that write one (subtrees).  `mode` is the name a message
+// starts with.  The .mut and the --dist file: mut_text.h.
 #pragma once
 #include <cerrno>
 #include <cstdint>
@@ -137,6 +140,72 @@ struct AncText {
       return RL_EFORMAT;
     }
     return RL_OK;
+  }
+};
+
+// The trees of an .anc that carry a wanted SNP of its .mut, a batch at a time (mutrate.cpp, frequency.cpp,
+// mutctx.cpp).  The SNPs are numbered in the .mut's order, their tree indices do not fall.  The mode supplies
+// tree_of(k), the tree of SNP k; wanted(k), called once for every SNP in order: a tree with a wanted SNP is kept;
+// take(s, slot), called for every SNP of a kept tree with the tree's place in the batch (RL_OK, or the message set);
+// and flush(), called with `batch` trees held and at the end with what is left: tree_id names the trees held, parents
+// and bl hold them.  A tree that is not kept is read into a scratch tree (the file is read line by line).
+struct SnpTreeBatches {
+  const size_t nodes;
+  const int batch;
+  std::vector<int> parents, tree_id, scratch_parent;
+  std::vector<double> bl, scratch_bl;
+  SnpTreeBatches(int N, int batch_trees)
+      : nodes((size_t)2 * N - 1), batch(batch_trees), parents(batch * nodes), scratch_parent(nodes), bl(batch * nodes),
+        scratch_bl(nodes) {}
+  template <class TreeOf, class Wanted, class Take, class Flush>
+  int walk(AncText &anc, size_t nsnps, TreeOf tree_of, Wanted wanted, Take take, Flush flush) {
+    size_t k = 0;
+    for (int t = 0; t < anc.trees && k < nsnps; t++) {
+      bool keep = false;
+      const size_t k0 = k, slot = tree_id.size();
+      for (; k < nsnps && tree_of(k) == t; k++) keep |= wanted(k);
+      if (const int rc = anc.next(t, keep ? &parents[slot * nodes] : scratch_parent.data(), keep ? &bl[slot * nodes] : scratch_bl.data()))
+        return rc;
+      if (!keep) continue;
+      for (size_t s = k0; s < k; s++)
+        if (const int rc = take(s, (int)slot)) return rc;
+      tree_id.push_back(t);
+      if ((int)tree_id.size() < batch) continue;
+      if (const int rc = flush()) return rc;
+      tree_id.clear();
+    }
+    const int rc = tree_id.empty() ? RL_OK : flush();
+    tree_id.clear();
+    return rc;
+  }
+};
+
+// Every tree of an .anc with a factor, a batch at a time (coalrate.cpp, coaltree.cpp): read() puts tree t behind the
+// `held` trees of the batch, after a flush if the batch is full; the mode sets factors[held] and counts the tree in.
+// flush(add) hands the batch to add(parents, bl, factors, held, index0), index0 the number of its first tree in the
+// file.  Where the trees end is the mode's rule.
+struct FactorTreeBatches {
+  const size_t nodes;
+  const int batch;
+  std::vector<int> parents;
+  std::vector<double> bl;
+  std::vector<float> factors;
+  int held = 0;
+  long long index0 = 0;
+  FactorTreeBatches(int N, int batch_trees)
+      : nodes((size_t)2 * N - 1), batch(batch_trees), parents(batch * nodes), bl(batch * nodes), factors(batch) {}
+  template <class Add>
+  int flush(Add add) {
+    const int r = held ? add(parents.data(), bl.data(), factors.data(), held, index0) : RL_OK;
+    index0 += held;
+    held = 0;
+    return r;
+  }
+  template <class Add>
+  int read(AncText &anc, int t, Add add) {
+    if (held == batch)
+      if (const int rc = flush(add)) return rc;
+    return anc.next(t, &parents[held * nodes], &bl[held * nodes]);
   }
 };
 

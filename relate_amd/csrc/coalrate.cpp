@@ -21,45 +21,10 @@
 #include "anc_text.h"
 #include "coalrate.h"
 #include "common.h"
+#include "mut_text.h"
 #include "tree_host.h"
 
 namespace rl {
-
-// Mutations::Read (src/mutations.cpp:230-318): `;`-separated, the second column pos, the third dist, the fifth tree
-int read_mut_rows(const char *mode, const std::string &fn, std::vector<MutRow> &rows) {
-  std::ifstream is;
-  if (const int rc = open_text(mode, fn, is)) return rc;
-  std::string line, field;
-  getline(is, line);  // the header
-  long long n = 1;
-  while (getline(is, line)) {
-    n++;
-    if (line.empty()) continue;
-    std::istringstream ls(line);
-    MutRow r{0, 0, 0};
-    bool ok = true;
-    for (int c = 0; c < 5 && ok; c++) {
-      ok = (bool)getline(ls, field, ';');
-      if (ok && c == 1) ok = parse_int(field, &r.pos);
-      if (ok && c == 2) ok = parse_int(field, &r.dist);
-      if (ok && c == 4) ok = parse_int(field, &r.tree);
-    }
-    if (!ok) {
-      set_error("%s: %s: line %lld is not `snp;pos;dist;rs_id;tree;...`", mode, fn.c_str(), n);
-      return RL_EFORMAT;
-    }
-    if (!rows.empty() && r.tree < rows.back().tree) {
-      set_error("%s: %s: line %lld: tree index %d after %d: the tree indices must not fall", mode, fn.c_str(), n, r.tree, rows.back().tree);
-      return RL_EINVAL;
-    }
-    rows.push_back(r);
-  }
-  if (rows.empty()) {
-    set_error("%s: %s holds no SNP", mode, fn.c_str());
-    return RL_EFORMAT;
-  }
-  return RL_OK;
-}
 
 // Sample::Read (src/sample.cpp:4-110): the group names sorted, and the group of every haplotype -- two haplotypes per
 // line, one if any line's fourth column is `1`.  `mode` is the name a message starts with (FinalizePopulationSize; subtrees.cpp:
@@ -118,23 +83,6 @@ inline float term(float factor, float hi, float lo) {
   return factor * w;
 }
 
-int check_epochs(const char *who, const float *ep, int E) {
-  if (E < 2 || E > kCoalrateMaxEpochs) {
-    set_error("%s: 2 <= epochs <= %d (%d given)", who, kCoalrateMaxEpochs, E);
-    return RL_EINVAL;
-  }
-  if (ep[0] != 0.0f) {
-    set_error("%s: the first epoch boundary is %g, not 0", who, (double)ep[0]);
-    return RL_EINVAL;
-  }
-  for (int e = 1; e < E; e++)
-    if (!(ep[e] > ep[e - 1] && ep[e] <= FLT_MAX)) {
-      set_error("%s: epoch boundary %d (%g) is not finite and above boundary %d (%g)", who, e, (double)ep[e], e - 1, (double)ep[e - 1]);
-      return RL_EINVAL;
-    }
-  return RL_OK;
-}
-
 // one tree's tables and its contribution to D
 struct HostCoalrate : TreeTables {
   std::vector<int> order, g, es;
@@ -182,13 +130,6 @@ struct HostCoalrate : TreeTables {
   }
 };
 
-// 0, or the first node whose branch length is negative or not finite + 1 (the root's is not read)
-int first_bad_length(const double *bl, int N) {
-  for (int v = 0; v < 2 * N - 2; v++)
-    if (!(bl[v] >= 0.0 && bl[v] <= DBL_MAX)) return v + 1;
-  return 0;
-}
-
 // the sum in the making, on the host (in the caller's planes) or on a device
 struct Coalrate {
   int N = 0, E = 0, device = -1;
@@ -225,12 +166,7 @@ struct Coalrate {
       const double *b = bl + t * nodes;
       const std::string tree = std::string(where) + ": tree " + std::to_string(index0 + t);
       std::vector<unsigned char> kids;
-      if (first_bad_node(parent, N, kids)) return refuse_tree(tree.c_str(), parent, N);
-      if (const int v = first_bad_length(b, N)) {
-        set_error("%s: branch length %g of node %d is negative or not finite", tree.c_str(), b[v - 1], v - 1);
-        return RL_EINVAL;
-      }
-      if (dev) return refuse_tree(tree.c_str(), parent, N);  // (refused by the device and not by the host)
+      if (const int rc = check_tree(tree.c_str(), parent, b, N, 2 * N - 2, dev != nullptr, kids)) return rc;
       host->prepare(parent, b, ep, E);
       float fw[kCoalrateMaxEpochs];
       for (int e = 0; e < E - 1; e++) fw[e] = term(factors[t], ep[e + 1], ep[e]);
@@ -241,13 +177,6 @@ struct Coalrate {
   int finish() { return dev ? coalrate_device_finish(dev, out) : RL_OK; }
 };
 
-// ------------------------------------------------------------------------------------------------ the file layer
-
-int null_args(const char *who) {
-  set_error("%s: bad arguments (no null pointers)", who);
-  return RL_EINVAL;
-}
-
 }  // namespace
 }  // namespace rl
 
@@ -256,50 +185,7 @@ using namespace rl;
 extern "C" int rl_coalrate_batch_trees(int N) { return N < 2 ? 0 : coalrate_batch_trees(N); }
 
 extern "C" int rl_coalrate_epochs(float years_per_gen, const char *bins_or_null, float *epochs, int *nepochs) {
-  if (!epochs || !nepochs) return null_args("rl_coalrate_epochs");
-  if (!(years_per_gen > 0.0f && years_per_gen <= FLT_MAX)) {
-    set_error("rl_coalrate_epochs: years_per_gen %g is not positive and finite", (double)years_per_gen);
-    return RL_EINVAL;
-  }
-  const int cap = *nepochs;
-  std::vector<float> ep;
-  const float log_10 = std::log(10);
-  if (bins_or_null) {  // CoalescentRateForSection.cpp:306-367
-    double v[3];
-    const char *p = bins_or_null;
-    for (int k = 0; k < 3; k++) {
-      char *end = nullptr;
-      v[k] = strtof(p, &end);  // (std::stof)
-      if (end == p || (k < 2 && *end != ',') || (k == 2 && *end != '\0' && *end != ',')) {
-        set_error("rl_coalrate_epochs: bins `%s`: epochs format is wrong. Specify x,y,stepsize.", bins_or_null);
-        return RL_EINVAL;
-      }
-      p = end + 1;
-    }
-    const double lower = v[0], upper = v[1], step = v[2];
-    if (!(step > 0.0) || !(std::fabs(lower) <= 1e30) || !(std::fabs(upper) <= 1e30) || (upper - lower) / step > 1e6) {
-      set_error("rl_coalrate_epochs: bins `%s`: the step must be positive and the range finite", bins_or_null);
-      return RL_EINVAL;
-    }
-    ep.push_back(0.0f);
-    for (double boundary = lower; boundary < upper; boundary += step) ep.push_back(std::exp(log_10 * boundary) / years_per_gen);
-    ep.push_back(std::exp(log_10 * upper) / years_per_gen);
-    ep.push_back(std::max(1e8, 10.0 * ep[ep.size() - 1]) / years_per_gen);
-  } else {  // :371-378
-    const int E = 31;
-    ep.resize(E);
-    ep[0] = 0.0;
-    ep[1] = 1e3 / years_per_gen;
-    for (int e = 2; e < E - 1; e++) ep[e] = std::exp(log_10 * (3.0 + 4.0 * (e - 1.0) / (E - 3.0))) / years_per_gen;
-    ep[E - 1] = 1e8 / years_per_gen;
-  }
-  *nepochs = (int)ep.size();
-  if ((int)ep.size() > cap) {
-    set_error("rl_coalrate_epochs: %zu epoch boundaries, room for %d", ep.size(), cap);
-    return RL_EINVAL;
-  }
-  memcpy(epochs, ep.data(), ep.size() * sizeof(float));
-  return RL_OK;
+  return make_epochs("rl_coalrate_epochs", years_per_gen, bins_or_null, epochs, nepochs);
 }
 
 extern "C" int rl_coalrate_trees(const int *parents, const double *branch_length, const float *factors, int N,
@@ -312,7 +198,7 @@ extern "C" int rl_coalrate_trees(const int *parents, const double *branch_length
     set_error("rl_coalrate_trees: N=%d: no pair to take", N);
     return RL_EINVAL;
   }
-  if (const int rc = check_epochs("rl_coalrate_trees", epochs, nepochs)) return rc;
+  if (const int rc = check_epochs("rl_coalrate_trees", epochs, nepochs, kCoalrateMaxEpochs)) return rc;
   Coalrate cr;
   int rc = cr.begin(N, epochs, nepochs, device, out);
   rc = rc ? rc : cr.add(parents, branch_length, factors, ntrees, "rl_coalrate_trees", 0);
@@ -322,7 +208,7 @@ extern "C" int rl_coalrate_trees(const int *parents, const double *branch_length
 extern "C" int rl_coalrate_anc(const char *anc_path, const char *mut_path, const float *epochs, int nepochs, int device,
                                float *out_or_null, int *N_out) {
   if (!anc_path || !mut_path || !epochs || !N_out) return null_args("rl_coalrate_anc");
-  if (const int rc = check_epochs("rl_coalrate_anc", epochs, nepochs)) return rc;
+  if (const int rc = check_epochs("rl_coalrate_anc", epochs, nepochs, kCoalrateMaxEpochs)) return rc;
   AncText anc("CoalescentRateForSection");
   int rc = anc.open(anc_path);
   if (rc) return rc;
@@ -343,40 +229,31 @@ extern "C" int rl_coalrate_anc(const char *anc_path, const char *mut_path, const
   if ((rc = cr.begin(N, epochs, nepochs, device, out_or_null))) return rc;
   // the loop of CoalescentRateForSection.cpp:441-480: every tree with the bases it persists for -- and, NextTree
   // having returned -1 with the last tree still in place, the last tree once more with the factor -1
-  const size_t nodes = (size_t)2 * N - 1;
-  const int batch = coalrate_batch_trees(N);
-  std::vector<int> parents((size_t)batch * nodes);
-  std::vector<double> bl((size_t)batch * nodes);
-  std::vector<float> factors(batch);
+  FactorTreeBatches w(N, coalrate_batch_trees(N));
+  const size_t nodes = w.nodes;
   Persistence persistence(mut);
-  int held = 0;
-  long long index0 = 0;
-  const auto flush = [&]() {
-    const int r = held ? cr.add(parents.data(), bl.data(), factors.data(), held, anc_path, index0) : RL_OK;
-    index0 += held;
-    held = 0;
-    return r;
+  const auto add = [&](const int *p, const double *b, const float *f, int n, long long index0) {
+    return cr.add(p, b, f, n, anc_path, index0);
   };
   bool over = false;  // a negative factor ends the reference's loop
   for (int t = 0; t < anc.trees && !over; t++) {
-    if (held == batch && (rc = flush())) return rc;
-    if ((rc = anc.next(t, &parents[held * nodes], &bl[held * nodes]))) return rc;
-    factors[held] = (float)persistence.next(t);
-    over = !(factors[held] >= 0.0f);
-    held++;
+    if ((rc = w.read(anc, t, add))) return rc;
+    w.factors[w.held] = (float)persistence.next(t);
+    over = !(w.factors[w.held] >= 0.0f);
+    w.held++;
   }
   if (!over) {
-    const size_t last = (size_t)(held - 1) * nodes;  // (held >= 1: the batch is flushed before a tree is read)
-    const std::vector<int> p(parents.begin() + last, parents.begin() + last + nodes);
-    const std::vector<double> b(bl.begin() + last, bl.begin() + last + nodes);
-    if ((rc = flush())) return rc;
-    std::copy(p.begin(), p.end(), parents.begin());
-    std::copy(b.begin(), b.end(), bl.begin());
-    factors[0] = -1.0f;
-    held = 1;
-    index0--;  // (a message names the tree, not the pass)
+    const size_t last = (size_t)(w.held - 1) * nodes;  // (held >= 1: the batch is flushed before a tree is read)
+    const std::vector<int> p(w.parents.begin() + last, w.parents.begin() + last + nodes);
+    const std::vector<double> b(w.bl.begin() + last, w.bl.begin() + last + nodes);
+    if ((rc = w.flush(add))) return rc;
+    std::copy(p.begin(), p.end(), w.parents.begin());
+    std::copy(b.begin(), b.end(), w.bl.begin());
+    w.factors[0] = -1.0f;
+    w.held = 1;
+    w.index0--;  // (a message names the tree, not the pass)
   }
-  if ((rc = flush())) return rc;
+  if ((rc = w.flush(add))) return rc;
   return cr.finish();
 }
 

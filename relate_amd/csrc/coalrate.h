@@ -4,6 +4,8 @@
 #include <string>
 #include <vector>
 
+#include "tree_batch.h"
+
 namespace rl {
 
 constexpr int kCoalrateMaxN = 10240;   // 16-bit labels and ranks, the LDS layout of the accumulation
@@ -14,44 +16,9 @@ constexpr size_t kCoalrateBatchBytes = (size_t)2 << 20;
 // trees per batch at N leaves: kCoalrateBatchBytes over the bytes one tree takes on the device (parents 4, branch
 // lengths 8 per node; rank 2, g 2, time 4, epoch index 1 per leaf; factor and flag 4 each), at least 1
 inline int coalrate_batch_trees(int N) {
-  const size_t nodes = (size_t)2 * N - 1, per_tree = nodes * 12 + (size_t)N * 9 + 8;
-  const size_t b = kCoalrateBatchBytes / per_tree;
-  return b < 1 ? 1 : (b > (1u << 20) ? 1 << 20 : (int)b);
+  const size_t nodes = (size_t)2 * N - 1;
+  return batch_trees(kCoalrateBatchBytes, nodes * 12 + (size_t)N * 9 + 8);
 }
-
-// ---- the .mut as the modes that weigh a tree by the bases it persists for read it (coalrate.cpp; coaltree.cpp:
-// CoalRateForTree)
-struct MutRow {
-  int pos, dist, tree;
-};
-
-// Mutations::Read (src/mutations.cpp:230-318): `;`-separated, the second column pos, the third dist, the fifth tree.
-// `mode` is the name a message starts with (defined in coalrate.cpp)
-int read_mut_rows(const char *mode, const std::string &fn, std::vector<MutRow> &rows);
-
-// AncMutIterators::NextTree, mode 0 (src/mutations.cpp:854-912), with pos and dist the .mut's own (no --dist): the
-// bases tree `tree` persists for -- half the dist before its first SNP, its SNPs' dists, minus half the last --
-// or 0 for a tree without SNPs
-struct Persistence {
-  const std::vector<MutRow> &mut;
-  size_t k = 0;
-  int tree_in_mut;
-  explicit Persistence(const std::vector<MutRow> &m) : mut(m), tree_in_mut(m[0].tree) {}
-  double next(int tree) {
-    if (tree != tree_in_mut) return 0.0;
-    double bases = k != 0 ? mut[k - 1].dist / 2.0 : 0.0;
-    while (tree_in_mut == mut[k].tree) {
-      bases += mut[k].dist;
-      k++;
-      if (k == mut.size()) break;
-    }
-    if (k != mut.size()) {
-      bases -= mut[k - 1].dist / 2.0;
-      tree_in_mut = mut[k].tree;
-    }
-    return bases;
-  }
-};
 
 // ---- the .poplabels as FinalizePopulationSize and SubTreesForSubpopulation (subtrees.cpp) read it
 // Sample::Read (src/sample.cpp:4-103): the group names sorted, and the group of every haplotype -- two haplotypes per

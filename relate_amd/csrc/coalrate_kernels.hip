@@ -57,8 +57,9 @@ __global__ void __launch_bounds__(T) coalrate_prepare_kernel(const int *__restri
   const bool wave0 = threadIdx.x < 64;
 
   if (threadIdx.x < E) ep[threadIdx.x] = EP[threadIdx.x];
+  // (checked_kids of tree_passes.h written out: through the call this kernel's scalar register count comes out different)
   if (!build_kids<T>(par, N, K, nullptr, &bad)) {
-    if (threadIdx.x == 0) BAD[t] = 1;
+    if (threadIdx.x == 0) BAD[t] = kTreeRefused;
     return;
   }
   __syncthreads();  // (every thread has read build_kids' verdict)
@@ -66,7 +67,7 @@ __global__ void __launch_bounds__(T) coalrate_prepare_kernel(const int *__restri
     if (!(bl[v] >= 0.0 && bl[v] <= DBL_MAX)) bad = 1;  // negative, infinite or NaN: the times would not rise
   __syncthreads();
   if (bad) {
-    if (threadIdx.x == 0) BAD[t] = 1;
+    if (threadIdx.x == 0) BAD[t] = kTreeRefused;
     return;
   }
   if (wave0) {
@@ -201,12 +202,10 @@ __global__ void __launch_bounds__(T) coalrate_accumulate_kernel(const u16 *__res
   }
 }
 
-static size_t round16(size_t b) { return (b + 15) & ~(size_t)15; }
-
 struct CoalrateDevice {
-  int N = 0, E = 0, device = 0, batch = 0;
-  DevBuf D, ep, par, bl, f, rank, g, tm, es, bad;
-  std::vector<int> flags;
+  int N = 0, E = 0, device = 0;
+  DevBuf D, ep, f, rank, g, tm, es;
+  TreeBatch trees;
 };
 
 void coalrate_device_free(CoalrateDevice *d) { delete d; }
@@ -236,17 +235,14 @@ int coalrate_device_begin(CoalrateDevice **out, int N, const float *epochs, int 
   d->N = N;
   d->E = E;
   d->device = device;
-  d->batch = (int)B;
   int rc = d->D.alloc(dbytes);
   rc = rc ? rc : d->ep.alloc((size_t)E * 4);
-  rc = rc ? rc : d->par.alloc(B * nodes * 4);
-  rc = rc ? rc : d->bl.alloc(B * nodes * 8);
+  rc = rc ? rc : d->trees.alloc(N, (int)B);
   rc = rc ? rc : d->f.alloc(B * 4);
   rc = rc ? rc : d->rank.alloc(B * N * 2);
   rc = rc ? rc : d->g.alloc(B * N * 2);
   rc = rc ? rc : d->tm.alloc(B * N * 4);
   rc = rc ? rc : d->es.alloc(B * N);
-  rc = rc ? rc : d->bad.alloc(B * 4);
   if (rc) {
     delete d;
     return rc;
@@ -258,7 +254,6 @@ int coalrate_device_begin(CoalrateDevice **out, int N, const float *epochs, int 
     set_error("rl_coalrate_trees: %s", hipGetErrorString(e));
     return RL_EHIP;
   }
-  d->flags.resize(B);
   *out = d;
   return RL_OK;
 }
@@ -268,27 +263,25 @@ template <bool SMALL>
 static int coalrate_add_batches(CoalrateDevice *d, const int *parents, const double *branch_length, const float *factors,
                                 int ntrees, int *bad_tree) {
   const int N = d->N, E = d->E;
-  const size_t nodes = (size_t)2 * N - 1;
+  TreeBatch &tb = d->trees;
   const size_t dyn_prepare = round16((size_t)8 * (N - 1)), dyn_accumulate = round16((size_t)11 * N);
   const int rows = (N + 511) / 512, blocks = (N + rows - 1) / rows;
   u16 *rank = d->rank.as<u16>(), *g = d->g.as<u16>();
-  for (int t0 = 0; t0 < ntrees; t0 += d->batch) {
-    const int n = std::min(d->batch, ntrees - t0);
-    RL_HIP(hipMemcpy(d->par.p, parents + (size_t)t0 * nodes, (size_t)n * nodes * 4, hipMemcpyHostToDevice));
-    RL_HIP(hipMemcpy(d->bl.p, branch_length + (size_t)t0 * nodes, (size_t)n * nodes * 8, hipMemcpyHostToDevice));
+  for (int t0 = 0; t0 < ntrees; t0 += tb.batch) {
+    const int n = std::min(tb.batch, ntrees - t0);
     RL_HIP(hipMemcpy(d->f.p, factors + t0, (size_t)n * 4, hipMemcpyHostToDevice));
-    RL_HIP(hipMemset(d->bad.p, 0, (size_t)n * 4));
-    RL_HIP(launch_with_lds(coalrate_prepare_kernel<SMALL ? 64 : 256>, n, SMALL ? 64 : 256, dyn_prepare, nullptr, d->par.as<int>(),
-                           d->bl.as<double>(), d->ep.as<float>(), E, N, n, rank, g, d->tm.as<float>(),
-                           d->es.as<unsigned char>(), d->bad.as<int>()));
-    // (the copy waits for the kernel.)  Nothing of a batch is added unless all of its trees passed: the accumulation
-    // uses rank, g and the epoch indices as indices
-    RL_HIP(hipMemcpy(d->flags.data(), d->bad.p, (size_t)n * 4, hipMemcpyDeviceToHost));
-    for (int k = 0; k < n; k++)
-      if (d->flags[k]) {
-        *bad_tree = t0 + k;
-        return RL_EINVAL;
-      }
+    if (const int rc = tb.upload(parents, branch_length, t0, n)) return rc;
+    RL_HIP(launch_with_lds(coalrate_prepare_kernel<SMALL ? 64 : 256>, n, SMALL ? 64 : 256, dyn_prepare, nullptr, tb.par.as<int>(),
+                           tb.bl.as<double>(), d->ep.as<float>(), E, N, n, rank, g, d->tm.as<float>(),
+                           d->es.as<unsigned char>(), tb.flag.as<int>()));
+    // Nothing of a batch is added unless all of its trees passed: the accumulation uses rank, g and the epoch indices
+    // as indices
+    int bad = -1;
+    if (const int rc = tb.first_not_done(n, &bad)) return rc;
+    if (bad >= 0) {
+      *bad_tree = t0 + bad;
+      return RL_EINVAL;
+    }
     RL_HIP(launch_with_lds(coalrate_accumulate_kernel<SMALL ? 256 : 1024>, blocks, SMALL ? 256 : 1024, dyn_accumulate, nullptr, rank,
                            g, d->tm.as<float>(), d->es.as<unsigned char>(), d->f.as<float>(), d->ep.as<float>(), E, N, n,
                            rows, d->D.as<float>()));

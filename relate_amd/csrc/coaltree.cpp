@@ -5,7 +5,7 @@
 // label), the lineage count per group of equal times, the walk over the ranks with its epoch cursor, every term added
 // straight onto the accumulators of the current block of trees -- and is the `device < 0` path and the authority the
 // device (coaltree_kernels.hip) is held to, bit for bit.  This file also holds the loop over the text .anc with the
-// factors of AncMutIterators::NextTree (coalrate.h), the sum of the blocks, the rate rule and the writer of
+// factors of AncMutIterators::NextTree (mut_text.h), the sum of the blocks, the rate rule and the writer of
 // coal_tree::Dump, and the C entry points.
 #include <algorithm>
 #include <cfloat>
@@ -18,9 +18,9 @@
 #include <vector>
 
 #include "anc_text.h"
-#include "coalrate.h"
 #include "coaltree.h"
 #include "common.h"
+#include "mut_text.h"
 #include "tree_host.h"
 
 namespace rl {
@@ -104,30 +104,6 @@ struct HostCoalTree : TreeTables {
   }
 };
 
-int check_epochs(const char *who, const double *ep, int E) {
-  if (E < 2 || E > kCoaltreeMaxEpochs) {
-    set_error("%s: 2 <= epochs <= %d (%d given)", who, kCoaltreeMaxEpochs, E);
-    return RL_EINVAL;
-  }
-  if (ep[0] != 0.0) {
-    set_error("%s: the first epoch boundary is %g, not 0", who, ep[0]);
-    return RL_EINVAL;
-  }
-  for (int e = 1; e < E; e++)
-    if (!(ep[e] > ep[e - 1] && ep[e] <= DBL_MAX)) {
-      set_error("%s: epoch boundary %d (%g) is not finite and above boundary %d (%g)", who, e, ep[e], e - 1, ep[e - 1]);
-      return RL_EINVAL;
-    }
-  return RL_OK;
-}
-
-// 0, or the first node whose branch length is negative or not finite + 1 (the root's is not read)
-int first_bad_length(const double *bl, int N) {
-  for (int v = 0; v < 2 * N - 2; v++)
-    if (!(bl[v] >= 0.0 && bl[v] <= DBL_MAX)) return v + 1;
-  return 0;
-}
-
 // the accumulators in the making, on the host or on a device
 struct Coaltree {
   int N = 0, E = 0;
@@ -168,12 +144,7 @@ struct Coaltree {
       const int *parent = parents + t * nodes;
       const double *b = bl + t * nodes;
       const std::string tree = std::string(where) + ": tree " + std::to_string(index0 + t);
-      if (first_bad_node(parent, N, kids)) return refuse_tree(tree.c_str(), parent, N);
-      if (const int v = first_bad_length(b, N)) {
-        set_error("%s: branch length %g of node %d is negative or not finite", tree.c_str(), b[v - 1], v - 1);
-        return RL_EINVAL;
-      }
-      if (dev) return refuse_tree(tree.c_str(), parent, N);  // (refused by the device and not by the host)
+      if (const int rc = check_tree(tree.c_str(), parent, b, N, 2 * N - 2, dev != nullptr, kids)) return rc;
       if (const int failed = host->populate(parent, b, (double)factors[t], ep)) {
         set_error("%s: the reference's assert `%s` fails", tree.c_str(), failed == 1 ? "lins >= 1" : "current_block < num_blocks");
         return RL_EINVAL;
@@ -189,11 +160,6 @@ struct Coaltree {
     return RL_OK;
   }
 };
-
-int null_args(const char *who) {
-  set_error("%s: bad arguments (no null pointers)", who);
-  return RL_EINVAL;
-}
 
 }  // namespace
 }  // namespace rl
@@ -213,7 +179,7 @@ extern "C" int rl_coaltree_trees(const int *parents, const double *branch_length
     set_error("rl_coaltree_trees: bad arguments (ntrees=%d, block_size=%d; no null pointers)", ntrees, block_size);
     return RL_EINVAL;
   }
-  if (const int rc = check_epochs("rl_coaltree_trees", epochs, nepochs)) return rc;
+  if (const int rc = check_epochs("rl_coaltree_trees", epochs, nepochs, kCoaltreeMaxEpochs)) return rc;
   const int blocks = coaltree_num_blocks(ntrees, block_size), room = *num_blocks;
   *num_blocks = blocks;
   if (blocks > room) {
@@ -229,7 +195,7 @@ extern "C" int rl_coaltree_trees(const int *parents, const double *branch_length
 extern "C" int rl_coaltree_anc(const char *anc_path, const char *mut_path, const double *epochs, int nepochs, int device,
                                double *num, double *denom, int *ntrees) {
   if (!anc_path || !mut_path || !epochs || !num || !denom) return null_args("rl_coaltree_anc");
-  if (const int rc = check_epochs("rl_coaltree_anc", epochs, nepochs)) return rc;
+  if (const int rc = check_epochs("rl_coaltree_anc", epochs, nepochs, kCoaltreeMaxEpochs)) return rc;
   const int E = nepochs;
   AncText anc(kMode);
   int rc = anc.open(anc_path);
@@ -249,28 +215,18 @@ extern "C" int rl_coaltree_anc(const char *anc_path, const char *mut_path, const
   if ((rc = ct.begin(anc_path, N, epochs, E, anc.trees, kCoaltreeBlockSize, device))) return rc;
   // the loop of CoalescentRateForSection.cpp:757-766: every tree with the bases it persists for, until NextTree
   // returns a negative number -- after the last tree, or a negative persistence
-  const size_t nodes = (size_t)2 * N - 1;
-  const int batch = coaltree_batch_trees(N);
-  std::vector<int> parents((size_t)batch * nodes);
-  std::vector<double> bl((size_t)batch * nodes);
-  std::vector<float> factors(batch);
+  FactorTreeBatches w(N, coaltree_batch_trees(N));
   Persistence persistence(mut);
-  int held = 0;
-  long long index0 = 0;
-  const auto flush = [&]() {
-    const int r = held ? ct.add(parents.data(), bl.data(), factors.data(), held, anc_path, index0) : RL_OK;
-    index0 += held;
-    held = 0;
-    return r;
+  const auto add = [&](const int *p, const double *b, const float *f, int n, long long index0) {
+    return ct.add(p, b, f, n, anc_path, index0);
   };
   for (int t = 0; t < anc.trees; t++) {
-    if (held == batch && (rc = flush())) return rc;
-    if ((rc = anc.next(t, &parents[held * nodes], &bl[held * nodes]))) return rc;
+    if ((rc = w.read(anc, t, add))) return rc;
     const float num_bases_tree_persists = (float)persistence.next(t);
     if (!(num_bases_tree_persists >= 0.0)) break;
-    factors[held++] = num_bases_tree_persists;
+    w.factors[w.held++] = num_bases_tree_persists;
   }
-  if ((rc = flush())) return rc;
+  if ((rc = w.flush(add))) return rc;
   const int blocks = coaltree_num_blocks(anc.trees, kCoaltreeBlockSize);
   std::vector<double> block_num((size_t)blocks * E), block_denom((size_t)blocks * E);
   if ((rc = ct.finish(block_num.data(), block_denom.data()))) return rc;
@@ -281,7 +237,7 @@ extern "C" int rl_coaltree_anc(const char *anc_path, const char *mut_path, const
       num[e] += 1 * block_num[(size_t)b * E + e];
       denom[e] += 1 * block_denom[(size_t)b * E + e];
     }
-  if (ntrees) *ntrees = (int)index0;
+  if (ntrees) *ntrees = (int)w.index0;
   return RL_OK;
 }
 

@@ -2,6 +2,8 @@
 #pragma once
 #include <cstddef>
 
+#include "tree_batch.h"
+
 namespace rl {
 
 constexpr int kCoaltreeMaxN = 10240;    // the LDS layout of a tree: kids, then times and their sorted copy
@@ -15,16 +17,12 @@ constexpr size_t kCoaltreeBatchBytes = (size_t)16 << 20;
 // lengths 8 per node; a term of 8 per internal node; first 4, count 4 and exit term 8 per epoch at the most epochs;
 // factor and flag 4 each), at least 1
 inline int coaltree_batch_trees(int N) {
-  const size_t nodes = (size_t)2 * N - 1, per_tree = nodes * 12 + ((size_t)N - 1) * 8 + (size_t)kCoaltreeMaxEpochs * 16 + 8;
-  const size_t b = kCoaltreeBatchBytes / per_tree;
-  return b < 1 ? 1 : (b > (1u << 20) ? 1 << 20 : (int)b);
+  const size_t nodes = (size_t)2 * N - 1;
+  return batch_trees(kCoaltreeBatchBytes, nodes * 12 + ((size_t)N - 1) * 8 + (size_t)kCoaltreeMaxEpochs * 16 + 8);
 }
 
 // (int)(ntrees / (double)block_size + 1), coal_tree::update_ancmut (coal_tree.cpp:78): the last block may stay empty
 inline int coaltree_num_blocks(long long ntrees, int block_size) { return (int)((double)ntrees / (double)block_size + 1); }
-
-// what the device says of a tree
-enum { kCoaltreeTreeDone = 0, kCoaltreeTreeRefused = 1 };
 
 struct CoaltreeDevice;  // the accumulators [num_blocks][E] on the device and the room of one batch of trees
 

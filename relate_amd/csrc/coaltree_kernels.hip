@@ -75,7 +75,7 @@ __global__ void __launch_bounds__(T) coaltree_terms_kernel(const int *__restrict
 
   if (tid < E) ep[tid] = EP[tid];
   if (!sorted_max_times<T>(par, bl, N, K, S, &bad)) {
-    if (tid == 0) FLAG[t] = kCoaltreeTreeRefused;
+    if (tid == 0) FLAG[t] = kTreeRefused;
     return;
   }
   const double bases = (double)F[t];
@@ -169,13 +169,11 @@ __global__ void __launch_bounds__(kChainsThreads)
 }
 
 struct CoaltreeDevice {
-  int N = 0, E = 0, device = 0, batch = 0, num_blocks = 0, block_size = 0;
+  int N = 0, E = 0, device = 0, num_blocks = 0, block_size = 0;
   long long total = 0, added = 0;  // trees announced, trees added
-  DevBuf ep, num, den, par, bl, f, term, first, cnt, exit, flag;
-  std::vector<int> flags;
+  DevBuf ep, num, den, f, term, first, cnt, exit;
+  TreeBatch trees;
 };
-
-static size_t round16(size_t b) { return (b + 15) & ~(size_t)15; }
 
 int coaltree_device_begin(CoaltreeDevice **out, int N, const double *epochs, int E, long long ntrees, int block_size,
                           int device) {
@@ -189,22 +187,20 @@ int coaltree_device_begin(CoaltreeDevice **out, int N, const double *epochs, int
     return RL_EINVAL;
   }
   if (const int rc = select_device("rl_coaltree_trees", device)) return rc;
-  const size_t nodes = (size_t)2 * N - 1, ni = (size_t)N - 1, B = (size_t)coaltree_batch_trees(N);
+  const size_t ni = (size_t)N - 1, B = (size_t)coaltree_batch_trees(N);
   CoaltreeDevice *d = new CoaltreeDevice;
-  d->N = N, d->E = E, d->device = device, d->batch = (int)B, d->block_size = block_size, d->total = ntrees;
+  d->N = N, d->E = E, d->device = device, d->block_size = block_size, d->total = ntrees;
   d->num_blocks = coaltree_num_blocks(ntrees, block_size);
   const size_t acc = (size_t)d->num_blocks * E * 8;
   int rc = d->ep.alloc((size_t)E * 8);
   rc = rc ? rc : d->num.alloc(acc);
   rc = rc ? rc : d->den.alloc(acc);
-  rc = rc ? rc : d->par.alloc(B * nodes * 4);
-  rc = rc ? rc : d->bl.alloc(B * nodes * 8);
+  rc = rc ? rc : d->trees.alloc(N, (int)B);
   rc = rc ? rc : d->f.alloc(B * 4);
   rc = rc ? rc : d->term.alloc(B * ni * 8);
   rc = rc ? rc : d->first.alloc(B * E * 4);
   rc = rc ? rc : d->cnt.alloc(B * E * 4);
   rc = rc ? rc : d->exit.alloc(B * E * 8);
-  rc = rc ? rc : d->flag.alloc(B * 4);
   if (rc) {
     delete d;
     return rc;
@@ -217,7 +213,6 @@ int coaltree_device_begin(CoaltreeDevice **out, int N, const double *epochs, int
     set_error("rl_coaltree_trees: %s", hipGetErrorString(e));
     return RL_EHIP;
   }
-  d->flags.resize(B);
   *out = d;
   return RL_OK;
 }
@@ -231,29 +226,26 @@ int coaltree_device_add(CoaltreeDevice *d, const int *parents, const double *bra
   }
   RL_HIP(hipSetDevice(d->device));
   const int N = d->N, E = d->E, ni = N - 1, bs = d->block_size;
-  const size_t nodes = (size_t)2 * N - 1, dyn = round16((size_t)8 * ni);
-  for (int t0 = 0; t0 < ntrees; t0 += d->batch) {
-    const int n = std::min(d->batch, ntrees - t0);
-    RL_HIP(hipMemcpy(d->par.p, parents + (size_t)t0 * nodes, (size_t)n * nodes * 4, hipMemcpyHostToDevice));
-    RL_HIP(hipMemcpy(d->bl.p, branch_length + (size_t)t0 * nodes, (size_t)n * nodes * 8, hipMemcpyHostToDevice));
+  const size_t dyn = round16((size_t)8 * ni);
+  TreeBatch &tb = d->trees;
+  for (int t0 = 0; t0 < ntrees; t0 += tb.batch) {
+    const int n = std::min(tb.batch, ntrees - t0);
     RL_HIP(hipMemcpy(d->f.p, factors + t0, (size_t)n * 4, hipMemcpyHostToDevice));
-    RL_HIP(hipMemset(d->flag.p, 0, (size_t)n * 4));
-    if (N <= kCoaltreeSmallN)
-      RL_HIP(launch_with_lds(coaltree_terms_kernel<256>, n, 256, dyn, nullptr, d->par.as<int>(), d->bl.as<double>(),
-                             d->f.as<float>(), d->ep.as<double>(), E, N, n, d->term.as<double>(), d->first.as<int>(),
-                             d->cnt.as<int>(), d->exit.as<double>(), d->flag.as<int>()));
-    else
-      RL_HIP(launch_with_lds(coaltree_terms_kernel<1024>, n, 1024, dyn, nullptr, d->par.as<int>(), d->bl.as<double>(),
-                             d->f.as<float>(), d->ep.as<double>(), E, N, n, d->term.as<double>(), d->first.as<int>(),
-                             d->cnt.as<int>(), d->exit.as<double>(), d->flag.as<int>()));
-    // (the copy waits for the kernel.)  Nothing of a batch is added unless all of its trees passed: the chains use
-    // first and cnt as indices, and a refused tree leaves none
-    RL_HIP(hipMemcpy(d->flags.data(), d->flag.p, (size_t)n * 4, hipMemcpyDeviceToHost));
-    for (int k = 0; k < n; k++)
-      if (d->flags[k] != kCoaltreeTreeDone) {
-        *bad_tree = t0 + k;
-        return RL_EINVAL;
-      }
+    if (const int rc = tb.upload(parents, branch_length, t0, n)) return rc;
+    const auto go = [&](auto kernel, int threads) {
+      return launch_with_lds(kernel, n, threads, dyn, nullptr, tb.par.as<int>(), tb.bl.as<double>(), d->f.as<float>(),
+                             d->ep.as<double>(), E, N, n, d->term.as<double>(), d->first.as<int>(), d->cnt.as<int>(),
+                             d->exit.as<double>(), tb.flag.as<int>());
+    };
+    RL_HIP(N <= kCoaltreeSmallN ? go(coaltree_terms_kernel<256>, 256) : go(coaltree_terms_kernel<1024>, 1024));
+    // Nothing of a batch is added unless all of its trees passed: the chains use first and cnt as indices, and a
+    // refused tree leaves none
+    int bad = -1;
+    if (const int rc = tb.first_not_done(n, &bad)) return rc;
+    if (bad >= 0) {
+      *bad_tree = t0 + bad;
+      return RL_EINVAL;
+    }
     const long long g0 = d->added, first_block = g0 / bs, last_block = (g0 + n - 1) / bs;
     RL_HIP(launch_with_lds(coaltree_chains_kernel, (int)(last_block - first_block + 1), kChainsThreads, dyn, nullptr, d->term.as<double>(),
                            d->first.as<int>(), d->cnt.as<int>(), d->exit.as<double>(), d->f.as<float>(), E, ni, n, g0, bs,

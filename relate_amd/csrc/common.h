@@ -20,6 +20,11 @@
 namespace rl {
 
 void set_error(const char *fmt, ...);
+// the refusal of an entry point `who` that was handed a null pointer; RL_EINVAL
+inline int null_args(const char *who) {
+  set_error("%s: bad arguments (no null pointers)", who);
+  return RL_EINVAL;
+}
 // RELATE_AMD_TIMING: 0 / unset -- quiet; 1 -- where the wall-clock goes, on stderr; 2 -- also the tree builder's
 // progress marks (which worker holds which tree, the merge and phase a waiting build has reached)
 inline int timing_level() {

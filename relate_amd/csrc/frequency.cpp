@@ -21,6 +21,7 @@
 #include "anc_text.h"
 #include "common.h"
 #include "frequency.h"
+#include "mut_text.h"
 #include "tree_host.h"
 
 namespace rl {
@@ -194,30 +195,6 @@ struct HostWalk : TreeTables {
   std::vector<float> tmp_;
 };
 
-int check_epochs(const char *who, const float *ep, int E) {
-  if (E < 2 || E > kFrequencyMaxEpochs) {
-    set_error("%s: 2 <= epochs <= %d (%d given)", who, kFrequencyMaxEpochs, E);
-    return RL_EINVAL;
-  }
-  if (ep[0] != 0.0f) {
-    set_error("%s: the first epoch boundary is %g, not 0", who, (double)ep[0]);
-    return RL_EINVAL;
-  }
-  for (int e = 1; e < E; e++)
-    if (!(ep[e] > ep[e - 1] && ep[e] <= FLT_MAX)) {
-      set_error("%s: epoch boundary %d (%g) is not finite and above boundary %d (%g)", who, e, (double)ep[e], e - 1, (double)ep[e - 1]);
-      return RL_EINVAL;
-    }
-  return RL_OK;
-}
-
-// 0, or the first node whose branch length is negative or not finite + 1 (the root's is not read)
-int first_bad_length(const double *bl, int N) {
-  for (int v = 0; v < 2 * N - 2; v++)
-    if (!(bl[v] >= 0.0 && bl[v] <= DBL_MAX)) return v + 1;
-  return 0;
-}
-
 // The rows of nsnps SNPs (tree indices rising) over ntrees trees: freq [nsnps][E+1] (the counts, TreeFreq), lin
 // [nsnps][E+2] (the counts, when_DAF_is_half, when_mutation_has_freq2), marks [nsnps] (1: the row is there; 0: the
 // branch is -1 or the root), root_time [ntrees].  `where` names the trees' origin in a message; tree_id / snp_id (or
@@ -243,7 +220,7 @@ int frequency_rows(const int *parents, const double *bl, int N, int ntrees, cons
     snp_first[snp_tree[s] + 1]++;
   }
   for (int t = 0; t < ntrees; t++) snp_first[t + 1] += snp_first[t];
-  std::vector<int> flags((size_t)ntrees, kFrequencyTreeNeedsHost), rows;
+  std::vector<int> flags((size_t)ntrees, kTreeNeedsHost), rows;
   if (device >= 0) {
     rows.resize((size_t)nsnps * (2 * E + 2));
     if (const int rc = frequency_device(parents, bl, N, ntrees, snp_first.data(), snp_branch, nsnps, ep, E, device,
@@ -255,7 +232,7 @@ int frequency_rows(const int *parents, const double *bl, int N, int ntrees, cons
   for (int t = 0; t < ntrees; t++) {
     const int *parent = parents + t * nodes;
     const double *b = bl + t * nodes;
-    if (flags[t] == kFrequencyTreeDone) {
+    if (flags[t] == kTreeDone) {
       for (int s = snp_first[t]; s < snp_first[t + 1]; s++) {
         if (!marks[s]) continue;
         const int *row = &rows[(size_t)s * (2 * E + 2)];
@@ -266,12 +243,7 @@ int frequency_rows(const int *parents, const double *bl, int N, int ntrees, cons
       continue;
     }
     std::vector<unsigned char> kids;
-    if (first_bad_node(parent, N, kids)) return refuse_tree(tree_name(t).c_str(), parent, N);
-    if (const int v = first_bad_length(b, N)) {
-      set_error("%s: branch length %g of node %d is negative or not finite", tree_name(t).c_str(), b[v - 1], v - 1);
-      return RL_EINVAL;
-    }
-    if (flags[t] == kFrequencyTreeRefused) return refuse_tree(tree_name(t).c_str(), parent, N);  // (refused by the device and not by the host)
+    if (const int rc = check_tree(tree_name(t).c_str(), parent, b, N, 2 * N - 2, flags[t] == kTreeRefused, kids)) return rc;
     if (!host) host.reset(new HostWalk(N));
     bool walked = false;
     host->prepare(parent, b);
@@ -306,23 +278,9 @@ struct MutSnp {
 
 // `snp;pos;dist;rs_id;tree;branches;is_not_mapping;is_flipped;age_begin;age_end;alleles;[upstream;downstream;[freq;...]]`
 int read_mut(const std::string &fn, std::vector<MutSnp> &snps) {
-  std::ifstream is;
-  if (const int rc = open_text(kMode, fn, is)) return rc;
-  std::string line;
-  getline(is, line);  // the header
-  long long n = 1;
-  std::vector<std::string> col;
-  while (getline(is, line)) {
-    n++;
-    if (line.empty()) continue;
-    col.assign(1, std::string());
-    for (char c : line) {
-      if (c == ';') col.emplace_back();
-      else col.back() += c;
-    }
-    if (!col.back().empty()) col.emplace_back();  // (a last field without its `;`)
-    col.pop_back();
-    MutSnp m;
+  const char *const format = "snp;pos;dist;rs_id;tree;branches;is_not_mapping;is_flipped;age_begin;age_end;...";
+  return read_mut_lines(kMode, fn, format, nullptr, snps, [&fn](std::vector<std::string> &col, MutSnp &m, long long n) {
+    if (col.back().empty()) col.pop_back();  // (what follows the last `;`; a last field without its `;` stays)
     int dist = 0, flipped = 0;
     bool ok = col.size() >= 10 && parse_int(col[1], &m.pos) && parse_int(col[2], &dist) && parse_int(col[4], &m.tree) &&
               parse_int(col[7], &flipped);
@@ -339,25 +297,13 @@ int read_mut(const std::string &fn, std::vector<MutSnp> &snps) {
         if (m.branches++ == 0) m.branch = v;
       }
     }
-    if (!ok) {
-      set_error("%s: %s: line %lld is not `snp;pos;dist;rs_id;tree;branches;is_not_mapping;is_flipped;age_begin;age_end;...`", kMode, fn.c_str(), n);
-      return RL_EFORMAT;
-    }
+    if (!ok) return RL_EFORMAT;
     if (col.size() > 13) {
       set_error("%s: %s: line %lld has population-frequency columns: annotated .mut files are not part of this build", kMode, fn.c_str(), n);
       return RL_EINVAL;
     }
-    if (!snps.empty() && m.tree < snps.back().tree) {
-      set_error("%s: %s: line %lld: tree index %d after %d: the tree indices must not fall", kMode, fn.c_str(), n, m.tree, snps.back().tree);
-      return RL_EINVAL;
-    }
-    snps.push_back(m);
-  }
-  if (snps.empty()) {
-    set_error("%s: %s holds no SNP", kMode, fn.c_str());
-    return RL_EFORMAT;
-  }
-  return RL_OK;
+    return RL_OK;
+  });
 }
 
 // pos rs_id, the boundaries from the oldest to 0 with std::to_string (:497-508)
@@ -365,11 +311,6 @@ std::string header(const float *ep, int E, const char *tail) {
   std::string h = "pos rs_id ";
   for (int e = E - 1; e >= 0; e--) h += std::to_string(ep[e]) + " ";
   return h + tail;
-}
-
-int null_args(const char *who) {
-  set_error("%s: bad arguments (no null pointers)", who);
-  return RL_EINVAL;
 }
 
 }  // namespace
@@ -391,7 +332,7 @@ extern "C" int rl_frequency_trees(const int *parents, const double *branch_lengt
     set_error("rl_frequency_trees: N=%d: no branch below the root", N);
     return RL_EINVAL;
   }
-  if (const int rc = check_epochs("rl_frequency_trees", epochs, nepochs)) return rc;
+  if (const int rc = check_epochs("rl_frequency_trees", epochs, nepochs, kFrequencyMaxEpochs)) return rc;
   return frequency_rows(parents, branch_length, N, ntrees, snp_tree, snp_branch, nsnps, epochs, nepochs, device, freq, lin,
                         marks, root_time, host_trees, "rl_frequency_trees", nullptr, nullptr);
 }
@@ -399,7 +340,7 @@ extern "C" int rl_frequency_trees(const int *parents, const double *branch_lengt
 extern "C" int rl_frequency_anc(const char *anc_path, const char *mut_path, const float *epochs, int nepochs, int device,
                                 const char *freq_path, const char *lin_path, long long *rows_out, int *host_trees_out) {
   if (!anc_path || !mut_path || !epochs || !freq_path || !lin_path) return null_args("rl_frequency_anc");
-  if (const int rc = check_epochs("rl_frequency_anc", epochs, nepochs)) return rc;
+  if (const int rc = check_epochs("rl_frequency_anc", epochs, nepochs, kFrequencyMaxEpochs)) return rc;
   const int E = nepochs;
   AncText anc(kMode);
   int rc = anc.open(anc_path);
@@ -425,26 +366,21 @@ extern "C" int rl_frequency_anc(const char *anc_path, const char *mut_path, cons
 
   // the trees that have a SNP the filter may keep (:539-554: one branch, not flipped; the age is compared with the
   // root's time once that is known) go up batch by batch with those SNPs; the rows come back in the .mut's order
-  const size_t nodes = (size_t)2 * N - 1;
-  const int batch = frequency_batch_trees(N);
-  std::vector<int> parents((size_t)batch * nodes), tree_id, snp_tree, snp_branch, snp_id, freq, lin;
-  std::vector<double> bl((size_t)batch * nodes);
+  SnpTreeBatches w(N, frequency_batch_trees(N));
+  std::vector<int> snp_tree, snp_branch, snp_id, freq, lin;
   std::vector<unsigned char> marks;
-  std::vector<float> root_time(batch);
-  std::vector<int> scratch_parent(nodes);
-  std::vector<double> scratch_bl(nodes);
+  std::vector<float> root_time(w.batch);
   long long rows = 0;
   int host_trees = 0;
   std::string out_freq, out_lin;
   const auto flush = [&]() -> int {
-    const int held = (int)tree_id.size(), ns = (int)snp_id.size();
-    if (!held) return RL_OK;
+    const int held = (int)w.tree_id.size(), ns = (int)snp_id.size();
     freq.assign((size_t)ns * (E + 1), 0);
     lin.assign((size_t)ns * (E + 2), 0);
     marks.assign(ns, 0);
     int on_host = 0;
-    const int r = frequency_rows(parents.data(), bl.data(), N, held, snp_tree.data(), snp_branch.data(), ns, epochs, E, device,
-                                 freq.data(), lin.data(), marks.data(), root_time.data(), &on_host, anc_path, tree_id.data(),
+    const int r = frequency_rows(w.parents.data(), w.bl.data(), N, held, snp_tree.data(), snp_branch.data(), ns, epochs, E, device,
+                                 freq.data(), lin.data(), marks.data(), root_time.data(), &on_host, anc_path, w.tree_id.data(),
                                  snp_id.data());
     if (r) return r;
     host_trees += on_host;
@@ -466,32 +402,22 @@ extern "C" int rl_frequency_anc(const char *anc_path, const char *mut_path, cons
     }
     os_freq << out_freq;
     os_lin << out_lin;
-    tree_id.clear(), snp_tree.clear(), snp_branch.clear(), snp_id.clear();
+    snp_tree.clear(), snp_branch.clear(), snp_id.clear();
     return RL_OK;
   };
-  size_t k = 0;
-  for (int t = 0; t < anc.trees && k < mut.size(); t++) {
-    bool wanted = false;
-    const size_t k0 = k;
-    for (; k < mut.size() && mut[k].tree == t; k++) wanted |= mut[k].branches == 1 && !mut[k].flipped;
-    int *parent = wanted ? &parents[tree_id.size() * nodes] : scratch_parent.data();
-    double *b = wanted ? &bl[tree_id.size() * nodes] : scratch_bl.data();
-    if ((rc = anc.next(t, parent, b))) return rc;
-    if (!wanted) continue;
-    for (size_t s = k0; s < k; s++) {
-      if (mut[s].branches != 1 || mut[s].flipped) continue;
-      if (mut[s].branch < -1 || mut[s].branch > root) {
-        set_error("%s: %s: SNP %zu is on branch %d of a tree with %zu nodes", kMode, mut_path, s, mut[s].branch, nodes);
-        return RL_EINVAL;
-      }
-      snp_tree.push_back((int)tree_id.size());
-      snp_branch.push_back(mut[s].branch);
-      snp_id.push_back((int)s);
+  const auto wanted = [&](size_t k) { return mut[k].branches == 1 && !mut[k].flipped; };
+  const auto take = [&](size_t s, int slot) {
+    if (!wanted(s)) return RL_OK;
+    if (mut[s].branch < -1 || mut[s].branch > root) {
+      set_error("%s: %s: SNP %zu is on branch %d of a tree with %zu nodes", kMode, mut_path, s, mut[s].branch, w.nodes);
+      return RL_EINVAL;
     }
-    tree_id.push_back(t);
-    if ((int)tree_id.size() == batch && (rc = flush())) return rc;
-  }
-  if ((rc = flush())) return rc;
+    snp_tree.push_back(slot);
+    snp_branch.push_back(mut[s].branch);
+    snp_id.push_back((int)s);
+    return RL_OK;
+  };
+  if ((rc = w.walk(anc, mut.size(), [&](size_t k) { return mut[k].tree; }, wanted, take, flush))) return rc;
   os_freq.close();
   os_lin.close();
   if (os_freq.fail() || os_lin.fail()) {

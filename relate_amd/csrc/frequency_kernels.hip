@@ -79,16 +79,8 @@ __global__ void __launch_bounds__(T) frequency_kernel(const int *__restrict__ PA
 
   if (tid < E) ep[tid] = EP[tid];
   if (tid == 0) tied = 0;
-  if (!build_kids<T>(par, N, K, U, &bad)) {
-    if (tid == 0) FLAG[t] = kFrequencyTreeRefused;
-    return;
-  }
-  __syncthreads();  // (every thread has read build_kids' verdict)
-  for (int v = tid; v < nodes - 1; v += T)
-    if (!(bl[v] >= 0.0 && bl[v] <= DBL_MAX)) bad = 1;  // negative, infinite or NaN: the times would not rise
-  __syncthreads();
-  if (bad) {
-    if (tid == 0) FLAG[t] = kFrequencyTreeRefused;
+  if (!checked_kids<T>(par, bl, nodes - 1, N, K, U, &bad)) {
+    if (tid == 0) FLAG[t] = kTreeRefused;
     return;
   }
   if (wave == 0) {
@@ -135,7 +127,7 @@ __global__ void __launch_bounds__(T) frequency_kernel(const int *__restrict__ PA
   if (tid == 0) ROOT[t] = root_time;
   __syncthreads();  // TM is done with
   if (tied) {
-    if (tid == 0) FLAG[t] = kFrequencyTreeNeedsHost;
+    if (tid == 0) FLAG[t] = kTreeNeedsHost;
     return;
   }
   for (int r = tid; r < ni; r += T) RANK[IDX[r]] = (u16)r;
@@ -208,8 +200,6 @@ __global__ void __launch_bounds__(T) frequency_kernel(const int *__restrict__ PA
   }
 }
 
-static size_t round16(size_t b) { return (b + 15) & ~(size_t)15; }
-
 int frequency_device(const int *parents, const double *branch_length, int N, int ntrees, const int *snp_first,
                      const int *snp_branch, int nsnps, const float *epochs, int E, int device, int *out,
                      float *root_time, int *flags) {
@@ -222,43 +212,40 @@ int frequency_device(const int *parents, const double *branch_length, int N, int
     return RL_EINVAL;
   }
   if (const int rc = select_device("rl_frequency_trees", device)) return rc;
-  const size_t nodes = (size_t)2 * N - 1, ni = (size_t)N - 1, width = (size_t)2 * E + 2;
+  const size_t ni = (size_t)N - 1, width = (size_t)2 * E + 2;
   const int B = frequency_batch_trees(N);
   const size_t dyn = round16(((12 * ni + 3) & ~(size_t)3) + 4 * ((ni + 31) / 32));
   size_t most = 0;  // SNPs of one batch
   for (int t0 = 0; t0 < ntrees; t0 += B) most = std::max(most, (size_t)(snp_first[std::min(ntrees, t0 + B)] - snp_first[t0]));
-  DevBuf ep, par, bl, first, branch, rows, root, flag;
+  DevBuf ep, first, branch, rows, root;
+  TreeBatch tb;
   int rc = ep.alloc((size_t)E * 4);
-  rc = rc ? rc : par.alloc((size_t)B * nodes * 4);
-  rc = rc ? rc : bl.alloc((size_t)B * nodes * 8);
+  rc = rc ? rc : tb.alloc(N, B);
   rc = rc ? rc : first.alloc(((size_t)B + 1) * 4);
   rc = rc ? rc : branch.alloc(most * 4);
   rc = rc ? rc : rows.alloc(most * width * 4);
   rc = rc ? rc : root.alloc((size_t)B * 4);
-  rc = rc ? rc : flag.alloc((size_t)B * 4);
   if (rc) return rc;
   RL_HIP(hipMemcpy(ep.p, epochs, (size_t)E * 4, hipMemcpyHostToDevice));
   std::vector<int> rebased((size_t)B + 1);
   for (int t0 = 0; t0 < ntrees; t0 += B) {
     const int n = std::min(B, ntrees - t0), s0 = snp_first[t0], ns = snp_first[t0 + n] - s0;
     for (int k = 0; k <= n; k++) rebased[k] = snp_first[t0 + k] - s0;
-    RL_HIP(hipMemcpy(par.p, parents + (size_t)t0 * nodes, (size_t)n * nodes * 4, hipMemcpyHostToDevice));
-    RL_HIP(hipMemcpy(bl.p, branch_length + (size_t)t0 * nodes, (size_t)n * nodes * 8, hipMemcpyHostToDevice));
     RL_HIP(hipMemcpy(first.p, rebased.data(), ((size_t)n + 1) * 4, hipMemcpyHostToDevice));
     if (ns) RL_HIP(hipMemcpy(branch.p, snp_branch + s0, (size_t)ns * 4, hipMemcpyHostToDevice));
+    if ((rc = tb.upload(parents, branch_length, t0, n))) return rc;
     if (ns) RL_HIP(hipMemset(rows.p, 0, (size_t)ns * width * 4));
-    RL_HIP(hipMemset(flag.p, 0, (size_t)n * 4));
     RL_HIP(hipMemset(root.p, 0, (size_t)n * 4));
-    if (N <= kFrequencySmallN)
-      RL_HIP(launch_with_lds(frequency_kernel<256>, n, 256, dyn, nullptr, par.as<int>(), bl.as<double>(), ep.as<float>(), E, N, n,
-                             first.as<int>(), branch.as<int>(), rows.as<int>(), root.as<float>(), flag.as<int>()));
-    else
-      RL_HIP(launch_with_lds(frequency_kernel<1024>, n, 1024, dyn, nullptr, par.as<int>(), bl.as<double>(), ep.as<float>(), E, N, n,
-                             first.as<int>(), branch.as<int>(), rows.as<int>(), root.as<float>(), flag.as<int>()));
+    const auto go = [&](auto kernel, int threads) {
+      return launch_with_lds(kernel, n, threads, dyn, nullptr, tb.par.as<int>(), tb.bl.as<double>(), ep.as<float>(), E, N, n,
+                             first.as<int>(), branch.as<int>(), rows.as<int>(), root.as<float>(), tb.flag.as<int>());
+    };
+    RL_HIP(N <= kFrequencySmallN ? go(frequency_kernel<256>, 256) : go(frequency_kernel<1024>, 1024));
     // (the copies wait for the kernel)
     if (ns) RL_HIP(hipMemcpy(out + (size_t)s0 * width, rows.p, (size_t)ns * width * 4, hipMemcpyDeviceToHost));
     RL_HIP(hipMemcpy(root_time + t0, root.p, (size_t)n * 4, hipMemcpyDeviceToHost));
-    RL_HIP(hipMemcpy(flags + t0, flag.p, (size_t)n * 4, hipMemcpyDeviceToHost));
+    if ((rc = tb.download(n))) return rc;
+    std::copy(tb.flags.begin(), tb.flags.begin() + n, flags + t0);
   }
   return RL_OK;
 }

@@ -1,7 +1,14 @@
-// mut_text.h -- the text .mut with every column, for the modes that write one (subtrees.cpp: SubTreesForSubpopulation):
-// the reader of Mutations::Read (src/mutations.cpp:230-430) and the writer of Mutations::Dump (:457-508).  The modes
-// that only weigh a tree by its SNPs read three columns with read_mut_rows (coalrate.h).  `mode` is the name a message
-// starts with.
+// mut_text.h -- the text .mut (Mutations::Read, src/mutations.cpp:230-430) and the --dist file.  `mode` is the name a
+// message starts with.
+//   read_mut_lines   the line loop every reader of a .mut shares and nothing of what a reader accepts: read_mut_rows
+//                    and read_mut_full below, the read_mut of mutrate.cpp (AvgMutationRate) and that of frequency.cpp
+//                    (Frequency) each bring the parser of their own row
+//   read_mut_rows, Persistence   three columns, for the modes that weigh a tree by the bases it persists for
+//                    (coalrate.cpp: CoalescentRateForSection; coaltree.cpp: CoalRateForTree)
+//   read_mut_full, write_mut_text   every column, for the modes that write a .mut or read its alleles (subtrees.cpp:
+//                    SubTreesForSubpopulation; mutctx.cpp: MutationRateWithContext); the writer of Mutations::Dump
+//                    (:457-508)
+//   read_dist        the --dist file (mutrate.cpp, mutctx.cpp)
 #pragma once
 #include <cstdlib>
 #include <fstream>
@@ -12,6 +19,109 @@
 #include "common.h"
 
 namespace rl {
+
+// The lines of a .mut: the header (kept if asked for), then per line that is not empty its fields, split at `;` --
+// what follows the last `;` is a field too, the reader decides what an empty one means.  parse(fields, row, line
+// number) fills the row: RL_OK; RL_EFORMAT, and the message here names the line and `format`; or another code with
+// the message set.  Row has a member `tree`: a file whose tree indices fall, or one without a SNP, is refused.
+template <class Row, class Parse>
+int read_mut_lines(const char *mode, const std::string &fn, const char *format, std::string *header_or_null,
+                   std::vector<Row> &rows, Parse parse) {
+  std::ifstream is;
+  if (const int rc = open_text(mode, fn, is)) return rc;
+  std::string line;
+  getline(is, line);  // the header
+  if (header_or_null) *header_or_null = line;
+  long long n = 1;
+  std::vector<std::string> f;
+  while (getline(is, line)) {
+    n++;
+    if (line.empty()) continue;
+    f.assign(1, std::string());
+    for (char c : line) {
+      if (c == ';') f.emplace_back();
+      else f.back() += c;
+    }
+    Row r{};
+    if (const int rc = parse(f, r, n)) {
+      if (rc == RL_EFORMAT) set_error("%s: %s: line %lld is not `%s`", mode, fn.c_str(), n, format);
+      return rc;
+    }
+    if (!rows.empty() && r.tree < rows.back().tree) {
+      set_error("%s: %s: line %lld: tree index %d after %d: the tree indices must not fall", mode, fn.c_str(), n, r.tree, rows.back().tree);
+      return RL_EINVAL;
+    }
+    rows.push_back(std::move(r));
+  }
+  if (rows.empty()) {
+    set_error("%s: %s holds no SNP", mode, fn.c_str());
+    return RL_EFORMAT;
+  }
+  return RL_OK;
+}
+
+// ---- the .mut as the modes that weigh a tree by the bases it persists for read it
+struct MutRow {
+  int pos, dist, tree;
+};
+
+// the second column pos, the third dist, the fifth tree; what follows the fifth is not read
+inline int read_mut_rows(const char *mode, const std::string &fn, std::vector<MutRow> &rows) {
+  return read_mut_lines(mode, fn, "snp;pos;dist;rs_id;tree;...", nullptr, rows, [](std::vector<std::string> &f, MutRow &r, long long) {
+    return f.size() >= 5 && parse_int(f[1], &r.pos) && parse_int(f[2], &r.dist) && parse_int(f[4], &r.tree) ? RL_OK : RL_EFORMAT;
+  });
+}
+
+// AncMutIterators::NextTree, mode 0 (src/mutations.cpp:854-912), with pos and dist the .mut's own (no --dist): the
+// bases tree `tree` persists for -- half the dist before its first SNP, its SNPs' dists, minus half the last --
+// or 0 for a tree without SNPs
+struct Persistence {
+  const std::vector<MutRow> &mut;
+  size_t k = 0;
+  int tree_in_mut;
+  explicit Persistence(const std::vector<MutRow> &m) : mut(m), tree_in_mut(m[0].tree) {}
+  double next(int tree) {
+    if (tree != tree_in_mut) return 0.0;
+    double bases = k != 0 ? mut[k - 1].dist / 2.0 : 0.0;
+    while (tree_in_mut == mut[k].tree) {
+      bases += mut[k].dist;
+      k++;
+      if (k == mut.size()) break;
+    }
+    if (k != mut.size()) {
+      bases -= mut[k - 1].dist / 2.0;
+      tree_in_mut = mut[k].tree;
+    }
+    return bases;
+  }
+};
+
+// the --dist file (AvgMutationRate.cpp:326-357): one header line, then `pos dist` per line (sscanf "%d %d"); dist
+// may be null
+inline int read_dist(const char *mode, const std::string &fn, std::vector<int> &pos, std::vector<int> *dist_or_null) {
+  std::ifstream is;
+  if (const int rc = open_text(mode, fn, is)) return rc;
+  std::string line;
+  getline(is, line);
+  long long n = 1;
+  while (getline(is, line)) {
+    n++;
+    int p = 0, d = 0;
+    if (sscanf(line.c_str(), "%d %d", &p, &d) != 2) {
+      set_error("%s: %s: line %lld is not `pos dist`", mode, fn.c_str(), n);
+      return RL_EFORMAT;
+    }
+    pos.push_back(p);
+    if (dist_or_null) dist_or_null->push_back(d);
+  }
+  if (pos.empty()) {
+    set_error("%s: %s holds no position", mode, fn.c_str());
+    return RL_EFORMAT;
+  }
+  return RL_OK;
+}
+
+// ---- the .mut with every column
 
 // SNPInfo (src/mutations.hpp:11-25)
 struct MutFull {
@@ -28,22 +138,9 @@ struct MutFull {
 // `upstream;downstream;freq;...;`.  The branches are blank separated; is_not_mapping is not kept (the writer derives it
 // from the number of branches).  A file whose tree indices fall is refused
 inline int read_mut_full(const char *mode, const std::string &fn, std::string &header, std::vector<MutFull> &rows) {
-  std::ifstream is;
-  if (const int rc = open_text(mode, fn, is)) return rc;
-  std::string line;
-  getline(is, header);
-  long long n = 1;
-  std::vector<std::string> f;
-  while (getline(is, line)) {
-    n++;
-    if (line.empty()) continue;
-    f.assign(1, std::string());
-    for (char c : line) {
-      if (c == ';') f.emplace_back();
-      else f.back() += c;
-    }
+  const char *const format = "snp;pos;dist;rs_id;tree;branches;is_not_mapping;is_flipped;age_begin;age_end;[alleles;[upstream;downstream;freq;...]]";
+  return read_mut_lines(mode, fn, format, &header, rows, [](std::vector<std::string> &f, MutFull &r, long long) {
     if (f.back().empty()) f.pop_back();  // (what follows the last `;`)
-    MutFull r;
     int flipped = 0;
     bool ok = f.size() >= 10 && f.size() != 12 && parse_int(f[0], &r.snp_id) && parse_int(f[1], &r.pos) &&
               parse_int(f[2], &r.dist) && parse_int(f[4], &r.tree) && parse_int(f[7], &flipped);
@@ -79,21 +176,8 @@ inline int read_mut_full(const char *mode, const std::string &fn, std::string &h
         r.freq.push_back(x);
       }
     }
-    if (!ok) {
-      set_error("%s: %s: line %lld is not `snp;pos;dist;rs_id;tree;branches;is_not_mapping;is_flipped;age_begin;age_end;[alleles;[upstream;downstream;freq;...]]`", mode, fn.c_str(), n);
-      return RL_EFORMAT;
-    }
-    if (!rows.empty() && r.tree < rows.back().tree) {
-      set_error("%s: %s: line %lld: tree index %d after %d: the tree indices must not fall", mode, fn.c_str(), n, r.tree, rows.back().tree);
-      return RL_EINVAL;
-    }
-    rows.push_back(std::move(r));
-  }
-  if (rows.empty()) {
-    set_error("%s: %s holds no SNP", mode, fn.c_str());
-    return RL_EFORMAT;
-  }
-  return RL_OK;
+    return ok ? RL_OK : RL_EFORMAT;
+  });
 }
 
 // Mutations::Dump (src/mutations.cpp:457-508): the header (the standard one if empty), then a line per SNP; the ages

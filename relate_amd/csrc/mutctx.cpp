@@ -22,6 +22,7 @@
 #include "common.h"
 #include "mut_text.h"
 #include "mutctx.h"
+#include "tree_host.h"
 
 namespace rl {
 
@@ -102,29 +103,6 @@ int read_fasta(const std::string &fn, bool upper, std::string &seq) {
     if (upper)
       for (char &c : line) c = (char)std::toupper((unsigned char)c);
     seq += line;
-  }
-  return RL_OK;
-}
-
-// the positions of the --dist file (:625-648): one header line, then `pos dist` per line (sscanf "%d %d")
-int read_dist_positions(const std::string &fn, std::vector<int> &pos) {
-  std::ifstream is;
-  if (const int rc = open_text(kMode, fn, is)) return rc;
-  std::string line;
-  getline(is, line);
-  long long n = 1;
-  while (getline(is, line)) {
-    n++;
-    int p = 0, d = 0;
-    if (sscanf(line.c_str(), "%d %d", &p, &d) != 2) {
-      set_error("%s: %s: line %lld is not `pos dist`", kMode, fn.c_str(), n);
-      return RL_EFORMAT;
-    }
-    pos.push_back(p);
-  }
-  if (pos.empty()) {
-    set_error("%s: %s holds no position", kMode, fn.c_str());
-    return RL_EFORMAT;
   }
   return RL_OK;
 }
@@ -229,11 +207,6 @@ int count_bases(std::string ancestor, std::string mask, const int *pos, long lon
     p++;
   }
   return RL_OK;
-}
-
-int null_args(const char *who) {
-  set_error("%s: bad arguments (no null pointers)", who);
-  return RL_EINVAL;
 }
 
 // :842-848: both flanks not `NA`, alleles `X/Y` of three characters, X != Y, both in ACGT
@@ -484,7 +457,7 @@ extern "C" int rl_mutctx_trees(const int *parents, const double *branch_length, 
     set_error("rl_mutctx_trees: bad arguments (ntrees=%d, nsnps=%lld; no null pointers)", ntrees, nsnps);
     return RL_EINVAL;
   }
-  if (const int rc = mutrate_check_epochs("rl_mutctx_trees", epochs, nepochs)) return rc;
+  if (const int rc = check_epochs("rl_mutctx_trees", epochs, nepochs, kMutrateMaxEpochs)) return rc;
   for (long long s = 0; s < nsnps; s++)
     if (snp_tree[s] < 0 || snp_tree[s] >= ntrees || (s && snp_tree[s] < snp_tree[s - 1])) {
       set_error("rl_mutctx_trees: SNP %lld names tree %d (of %d; the tree before: %d): the tree indices must not fall", s,
@@ -519,7 +492,7 @@ extern "C" int rl_mutctx_anc(const char *anc_path, const char *mut_path, const c
                              const char *dist_path_or_null, const double *epochs, int nepochs, int device, double *mutation,
                              double *opportunity, long long *snps3) {
   if (!anc_path || !mut_path || !mask_path || !ancestor_path || !epochs || !mutation || !opportunity) return null_args("rl_mutctx_anc");
-  if (const int rc = mutrate_check_epochs("rl_mutctx_anc", epochs, nepochs)) return rc;
+  if (const int rc = check_epochs("rl_mutctx_anc", epochs, nepochs, kMutrateMaxEpochs)) return rc;
   const int E = nepochs;
   typedef std::chrono::steady_clock Clock;
   const auto since = [](Clock::time_point t0) { return std::chrono::duration<double>(Clock::now() - t0).count(); };
@@ -544,7 +517,7 @@ extern "C" int rl_mutctx_anc(const char *anc_path, const char *mut_path, const c
   std::vector<unsigned char> one_branch(L);
   for (size_t s = 0; s < L; s++) snp_pos[s] = mut[s].pos, one_branch[s] = mut[s].branch.size() == 1;
   if (dist_path_or_null) {
-    if ((rc = read_dist_positions(dist_path_or_null, pos))) return rc;
+    if ((rc = read_dist(kMode, dist_path_or_null, pos, nullptr))) return rc;
   } else {
     pos = snp_pos;
   }
@@ -558,24 +531,20 @@ extern "C" int rl_mutctx_anc(const char *anc_path, const char *mut_path, const c
   // and the numerator is added on the host, in the .mut's order (:829-908)
   Adder adder(N, epochs, E, device);
   if ((rc = adder.begin())) return rc;
-  const size_t nodes = (size_t)2 * N - 1;
-  const int batch = mutrate_batch_trees(N);
-  std::vector<int> parents((size_t)batch * nodes), tree_id, scratch_parent(nodes);
-  std::vector<double> bl((size_t)batch * nodes), scratch_bl(nodes);
+  SnpTreeBatches w(N, mutrate_batch_trees(N));
   std::vector<size_t> snp_id;  // the qualifying SNPs of the batch
   std::vector<int> snp_tree;   // ... and the tree of each, within the batch
   std::vector<uint32_t> rows;  // ... and its counts
-  std::vector<float> roots((size_t)batch);
+  std::vector<float> roots((size_t)w.batch);
   std::fill(mutation, mutation + (size_t)E * C96, 0.0);
   long long ones = 0, qualifying = 0;
   int trees_done = 0;
   double add_seconds = 0.0;
   const auto flush = [&]() -> int {
-    const int held = (int)tree_id.size();
-    if (!held) return RL_OK;
+    const int held = (int)w.tree_id.size();
     const Clock::time_point t0 = Clock::now();
-    if (const int r = adder.add(parents.data(), bl.data(), held, snp_tree.data(), rows.data(), (long long)snp_id.size(),
-                                roots.data(), anc_path, tree_id.data()))
+    if (const int r = adder.add(w.parents.data(), w.bl.data(), held, snp_tree.data(), rows.data(), (long long)snp_id.size(),
+                                roots.data(), anc_path, w.tree_id.data()))
       return r;
     add_seconds += since(t0);
     for (size_t i = 0; i < snp_id.size(); i++) {
@@ -583,31 +552,22 @@ extern "C" int rl_mutctx_anc(const char *anc_path, const char *mut_path, const c
       if (const int r = add_mutation(mut_path, snp_id[i], m, category_of(m), roots[snp_tree[i]], epochs, E, mutation)) return r;
     }
     trees_done += held;
-    tree_id.clear(), snp_id.clear(), snp_tree.clear(), rows.clear();
+    snp_id.clear(), snp_tree.clear(), rows.clear();
     return RL_OK;
   };
-  size_t k = 0;
-  for (int t = 0; t < anc.trees && k < L; t++) {
-    bool wanted = false;
-    const size_t k0 = k;
-    for (; k < L && mut[k].tree == t; k++) {
-      ones += one_branch[k];
-      wanted |= one_branch[k] && qualifies(mut[k]);
+  const auto wanted = [&](size_t k) {
+    ones += one_branch[k];
+    return one_branch[k] && qualifies(mut[k]);
+  };
+  const auto take = [&](size_t s, int slot) {
+    if (one_branch[s] && qualifies(mut[s])) {
+      snp_id.push_back(s), snp_tree.push_back(slot);
+      rows.insert(rows.end(), counts.begin() + s * C96, counts.begin() + (s + 1) * C96);
+      qualifying++;
     }
-    int *parent = wanted ? &parents[tree_id.size() * nodes] : scratch_parent.data();
-    double *b = wanted ? &bl[tree_id.size() * nodes] : scratch_bl.data();
-    if ((rc = anc.next(t, parent, b))) return rc;
-    if (!wanted) continue;
-    for (size_t s = k0; s < k; s++)
-      if (one_branch[s] && qualifies(mut[s])) {
-        snp_id.push_back(s), snp_tree.push_back((int)tree_id.size());
-        rows.insert(rows.end(), counts.begin() + s * C96, counts.begin() + (s + 1) * C96);
-        qualifying++;
-      }
-    tree_id.push_back(t);
-    if ((int)tree_id.size() == batch && (rc = flush())) return rc;
-  }
-  if ((rc = flush())) return rc;
+    return RL_OK;
+  };
+  if ((rc = w.walk(anc, L, [&](size_t k) { return mut[k].tree; }, wanted, take, flush))) return rc;
   double seconds[3];
   if ((rc = adder.finish(opportunity, seconds))) return rc;
   if (timing_level() >= 1)

@@ -58,9 +58,9 @@ __global__ void __launch_bounds__(64) mutctx_chains_kernel(const double *__restr
 }
 
 struct MutctxDevice {
-  int N = 0, E = 0, device = 0, batch = 0;
-  DevBuf ep, opp, par, bl, len, flag, root, tree, cnt;
-  std::vector<int> flags;
+  int N = 0, E = 0, device = 0;
+  DevBuf ep, opp, len, root, tree, cnt;
+  TreeBatch trees;
   double seconds[3] = {0.0, 0.0, 0.0};
 };
 
@@ -76,14 +76,12 @@ int mutctx_device_begin(MutctxDevice **out, int N, const double *epochs, int E, 
   }
   if (const int rc = select_device("rl_mutctx_trees", device)) return rc;
   MutctxDevice *d = new MutctxDevice;
-  d->N = N, d->E = E, d->device = device, d->batch = mutrate_batch_trees(N);
-  const size_t nodes = (size_t)2 * N - 1, B = (size_t)d->batch;
+  d->N = N, d->E = E, d->device = device;
+  const size_t B = (size_t)mutrate_batch_trees(N);
   int rc = d->ep.alloc((size_t)E * 8);
   rc = rc ? rc : d->opp.alloc((size_t)E * kMutctxCategories * 8);
-  rc = rc ? rc : d->par.alloc(B * nodes * 4);
-  rc = rc ? rc : d->bl.alloc(B * nodes * 8);
+  rc = rc ? rc : d->trees.alloc(N, (int)B);
   rc = rc ? rc : d->len.alloc(B * E * 8);
-  rc = rc ? rc : d->flag.alloc(B * 4);
   rc = rc ? rc : d->root.alloc(B * 4);
   rc = rc ? rc : d->tree.alloc((size_t)kMutctxSnpChunk * 4);
   rc = rc ? rc : d->cnt.alloc((size_t)kMutctxSnpChunk * kMutctxCategories * 4);
@@ -95,7 +93,6 @@ int mutctx_device_begin(MutctxDevice **out, int N, const double *epochs, int E, 
     delete d;
     return rc ? rc : RL_EHIP;
   }
-  d->flags.resize(B);
   *out = d;
   return RL_OK;
 }
@@ -105,8 +102,9 @@ int mutctx_device_add(MutctxDevice *d, const int *parents, const double *branch_
   typedef std::chrono::steady_clock Clock;
   const auto since = [](Clock::time_point t0) { return std::chrono::duration<double>(Clock::now() - t0).count(); };
   *bad_tree = -1;
-  if (ntrees < 1 || ntrees > d->batch || nsnps < 0) {
-    set_error("rl_mutctx_trees: a batch of %d trees, %lld SNPs (1 <= trees <= %d)", ntrees, nsnps, d->batch);
+  TreeBatch &tb = d->trees;
+  if (ntrees < 1 || ntrees > tb.batch || nsnps < 0) {
+    set_error("rl_mutctx_trees: a batch of %d trees, %lld SNPs (1 <= trees <= %d)", ntrees, nsnps, tb.batch);
     return RL_EINVAL;
   }
   for (long long s = 0; s < nsnps; s++)
@@ -116,24 +114,21 @@ int mutctx_device_add(MutctxDevice *d, const int *parents, const double *branch_
     }
   RL_HIP(hipSetDevice(d->device));
   const int N = d->N, E = d->E;
-  const size_t nodes = (size_t)2 * N - 1;
   Clock::time_point t0 = Clock::now();
-  RL_HIP(hipMemcpy(d->par.p, parents, (size_t)ntrees * nodes * 4, hipMemcpyHostToDevice));
-  RL_HIP(hipMemcpy(d->bl.p, branch_length, (size_t)ntrees * nodes * 8, hipMemcpyHostToDevice));
+  if (const int rc = tb.upload(parents, branch_length, 0, ntrees)) return rc;
   RL_HIP(hipMemset(d->len.p, 0, (size_t)ntrees * E * 8));
-  RL_HIP(hipMemset(d->flag.p, 0, (size_t)ntrees * 4));
   RL_HIP(hipMemset(d->root.p, 0, (size_t)ntrees * 4));
-  RL_HIP(mutrate_launch(d->par.as<int>(), d->bl.as<double>(), d->ep.as<double>(), E, N, ntrees, d->len.as<double>(),
-                        d->flag.as<int>(), d->root.as<float>()));
+  RL_HIP(mutrate_launch(tb.par.as<int>(), tb.bl.as<double>(), d->ep.as<double>(), E, N, ntrees, d->len.as<double>(),
+                        tb.flag.as<int>(), d->root.as<float>()));
   // (the copies wait for the kernel)
-  RL_HIP(hipMemcpy(d->flags.data(), d->flag.p, (size_t)ntrees * 4, hipMemcpyDeviceToHost));
+  int bad = -1;
+  if (const int rc = tb.first_not_done(ntrees, &bad)) return rc;
   RL_HIP(hipMemcpy(roots, d->root.p, (size_t)ntrees * 4, hipMemcpyDeviceToHost));
   d->seconds[0] += since(t0);
-  for (int t = 0; t < ntrees; t++)
-    if (d->flags[t] != kMutrateTreeDone) {
-      *bad_tree = t;
-      return RL_EINVAL;
-    }
+  if (bad >= 0) {
+    *bad_tree = bad;
+    return RL_EINVAL;
+  }
   const int cells = E * kMutctxCategories, grid = (cells + 63) / 64;
   for (long long s0 = 0; s0 < nsnps; s0 += kMutctxSnpChunk) {
     const int n = (int)std::min<long long>(kMutctxSnpChunk, nsnps - s0);

@@ -20,6 +20,7 @@
 
 #include "anc_text.h"
 #include "common.h"
+#include "mut_text.h"
 #include "mutrate.h"
 #include "tree_host.h"
 
@@ -92,31 +93,7 @@ struct HostLengths : TreeTables {
   }
 };
 
-int check_epochs(const char *who, const double *ep, int E) {
-  if (E < 2 || E > kMutrateMaxEpochs) {
-    set_error("%s: 2 <= epochs <= %d (%d given)", who, kMutrateMaxEpochs, E);
-    return RL_EINVAL;
-  }
-  if (ep[0] != 0.0) {
-    set_error("%s: the first epoch boundary is %g, not 0", who, ep[0]);
-    return RL_EINVAL;
-  }
-  for (int e = 1; e < E; e++)
-    if (!(ep[e] > ep[e - 1] && ep[e] <= DBL_MAX)) {
-      set_error("%s: epoch boundary %d (%g) is not finite and above boundary %d (%g)", who, e, ep[e], e - 1, ep[e - 1]);
-      return RL_EINVAL;
-    }
-  return RL_OK;
-}
-
-// 0, or the first node whose branch length is negative or not finite + 1 (the root's is not read)
-int first_bad_length(const double *bl, int N) {
-  for (int v = 0; v < 2 * N - 2; v++)
-    if (!(bl[v] >= 0.0 && bl[v] <= DBL_MAX)) return v + 1;
-  return 0;
-}
-
-// the trees whose flag is not kMutrateTreeDone, on the host: checked, then -- unless the device has refused them --
+// the trees whose flag is not kTreeDone, on the host: checked, then -- unless the device has refused them --
 // walked.  roots: null, or [ntrees]
 int host_rows(const int *parents, const double *bl, int N, int ntrees, const double *ep, int E, double *out, float *roots,
               const char *where, const int *tree_id, const int *flags, bool refused_by_device) {
@@ -125,15 +102,10 @@ int host_rows(const int *parents, const double *bl, int N, int ntrees, const dou
   HostLengths host(N);
   std::vector<unsigned char> kids;
   for (int t = 0; t < ntrees; t++) {
-    if (flags[t] == kMutrateTreeDone) continue;
+    if (flags[t] == kTreeDone) continue;
     const int *parent = parents + t * nodes;
     const double *b = bl + t * nodes;
-    if (first_bad_node(parent, N, kids)) return refuse_tree(tree_name(t).c_str(), parent, N);
-    if (const int v = first_bad_length(b, N)) {
-      set_error("%s: branch length %g of node %d is negative or not finite", tree_name(t).c_str(), b[v - 1], v - 1);
-      return RL_EINVAL;
-    }
-    if (refused_by_device) return refuse_tree(tree_name(t).c_str(), parent, N);  // (refused by the device and not by the host)
+    if (const int rc = check_tree(tree_name(t).c_str(), parent, b, N, 2 * N - 2, refused_by_device, kids)) return rc;
     host.run(parent, b, ep, E, out + (size_t)t * E);
     if (roots) roots[t] = host.root;
   }
@@ -147,10 +119,10 @@ int mutrate_rows(const int *parents, const double *bl, int N, int ntrees, const 
     set_error("%s: trees of 2 <= N <= %d leaves (N=%d)", where, kMutrateMaxN, N);
     return RL_EINVAL;
   }
-  std::vector<int> flags((size_t)ntrees, kMutrateTreeRefused);
+  std::vector<int> flags((size_t)ntrees, kTreeRefused);
   if (device >= 0) {
     if (const int rc = mutrate_device(parents, bl, N, ntrees, ep, E, device, out, flags.data())) return rc;
-    if (std::count(flags.begin(), flags.end(), (int)kMutrateTreeDone) == ntrees) return RL_OK;
+    if (std::count(flags.begin(), flags.end(), (int)kTreeDone) == ntrees) return RL_OK;
   }
   return host_rows(parents, bl, N, ntrees, ep, E, out, nullptr, where, tree_id, flags.data(), device >= 0);
 }
@@ -165,21 +137,8 @@ struct MutSnp {
 
 // `snp;pos;dist;rs_id;tree;branches;is_not_mapping;is_flipped;age_begin;age_end;...`
 int read_mut(const std::string &fn, std::vector<MutSnp> &snps) {
-  std::ifstream is;
-  if (const int rc = open_text(kMode, fn, is)) return rc;
-  std::string line;
-  getline(is, line);  // the header
-  long long n = 1;
-  std::vector<std::string> col;
-  while (getline(is, line)) {
-    n++;
-    if (line.empty()) continue;
-    col.assign(1, std::string());
-    for (char c : line) {
-      if (c == ';') col.emplace_back();
-      else col.back() += c;
-    }
-    MutSnp m;
+  const char *const format = "snp;pos;dist;rs_id;tree;branches;is_not_mapping;is_flipped;age_begin;age_end;...";
+  return read_mut_lines(kMode, fn, format, nullptr, snps, [](std::vector<std::string> &col, MutSnp &m, long long) {
     bool ok = col.size() >= 10 && parse_int(col[1], &m.pos) && parse_int(col[2], &m.dist) && parse_int(col[4], &m.tree);
     if (ok) {
       char *end = nullptr;
@@ -194,45 +153,8 @@ int read_mut(const std::string &fn, std::vector<MutSnp> &snps) {
         m.branches++;
       }
     }
-    if (!ok) {
-      set_error("%s: %s: line %lld is not `snp;pos;dist;rs_id;tree;branches;is_not_mapping;is_flipped;age_begin;age_end;...`", kMode, fn.c_str(), n);
-      return RL_EFORMAT;
-    }
-    if (!snps.empty() && m.tree < snps.back().tree) {
-      set_error("%s: %s: line %lld: tree index %d after %d: the tree indices must not fall", kMode, fn.c_str(), n, m.tree, snps.back().tree);
-      return RL_EINVAL;
-    }
-    snps.push_back(m);
-  }
-  if (snps.empty()) {
-    set_error("%s: %s holds no SNP", kMode, fn.c_str());
-    return RL_EFORMAT;
-  }
-  return RL_OK;
-}
-
-// the --dist file (:326-357): one header line, then `pos dist` per line (sscanf "%d %d")
-int read_dist(const std::string &fn, std::vector<int> &pos, std::vector<int> &dist) {
-  std::ifstream is;
-  if (const int rc = open_text(kMode, fn, is)) return rc;
-  std::string line;
-  getline(is, line);
-  long long n = 1;
-  while (getline(is, line)) {
-    n++;
-    int p = 0, d = 0;
-    if (sscanf(line.c_str(), "%d %d", &p, &d) != 2) {
-      set_error("%s: %s: line %lld is not `pos dist`", kMode, fn.c_str(), n);
-      return RL_EFORMAT;
-    }
-    pos.push_back(p);
-    dist.push_back(d);
-  }
-  if (pos.empty()) {
-    set_error("%s: %s holds no position", kMode, fn.c_str());
-    return RL_EFORMAT;
-  }
-  return RL_OK;
+    return ok ? RL_OK : RL_EFORMAT;
+  });
 }
 
 // :458-494: the scan of the position list for the .mut's positions, in order
@@ -261,11 +183,6 @@ int count_bases_of(const std::vector<MutSnp> &mut, const std::vector<int> &pos, 
   return RL_OK;
 }
 
-int null_args(const char *who) {
-  set_error("%s: bad arguments (no null pointers)", who);
-  return RL_EINVAL;
-}
-
 }  // namespace
 
 int mutrate_host_rows(const int *parents, const double *bl, int N, int ntrees, const double *ep, int E, double *out,
@@ -274,11 +191,9 @@ int mutrate_host_rows(const int *parents, const double *bl, int N, int ntrees, c
     set_error("%s: trees of 2 <= N <= %d leaves (N=%d)", where, kMutrateMaxN, N);
     return RL_EINVAL;
   }
-  const std::vector<int> flags((size_t)ntrees, kMutrateTreeRefused);
+  const std::vector<int> flags((size_t)ntrees, kTreeRefused);
   return host_rows(parents, bl, N, ntrees, ep, E, out, roots, where, tree_id, flags.data(), refused_by_device);
 }
-
-int mutrate_check_epochs(const char *who, const double *ep, int E) { return check_epochs(who, ep, E); }
 
 }  // namespace rl
 
@@ -287,50 +202,7 @@ using namespace rl;
 extern "C" int rl_mutrate_batch_trees(int N) { return N < 2 ? 0 : mutrate_batch_trees(N); }
 
 extern "C" int rl_mutrate_epochs(float years_per_gen, const char *bins_or_null, double *epochs, int *nepochs) {
-  if (!epochs || !nepochs) return null_args("rl_mutrate_epochs");
-  if (!(years_per_gen > 0.0f && years_per_gen <= FLT_MAX)) {
-    set_error("rl_mutrate_epochs: years_per_gen %g is not positive and finite", (double)years_per_gen);
-    return RL_EINVAL;
-  }
-  const int cap = *nepochs;
-  std::vector<double> ep;
-  const float log_10 = std::log(10);
-  if (bins_or_null) {  // :382-443
-    double v[3];
-    const char *p = bins_or_null;
-    for (int k = 0; k < 3; k++) {
-      char *end = nullptr;
-      v[k] = strtof(p, &end);  // (std::stof)
-      if (end == p || (k < 2 && *end != ',') || (k == 2 && *end != '\0' && *end != ',')) {
-        set_error("rl_mutrate_epochs: bins `%s`: epochs format is wrong. Specify x,y,stepsize.", bins_or_null);
-        return RL_EINVAL;
-      }
-      p = end + 1;
-    }
-    const double lower = v[0], upper = v[1], step = v[2];
-    if (!(step > 0.0) || !(std::fabs(lower) <= 1e30) || !(std::fabs(upper) <= 1e30) || (upper - lower) / step > 1e6) {
-      set_error("rl_mutrate_epochs: bins `%s`: the step must be positive and the range finite", bins_or_null);
-      return RL_EINVAL;
-    }
-    ep.push_back(0.0);
-    for (double boundary = lower; boundary < upper; boundary += step) ep.push_back(std::exp(log_10 * boundary) / years_per_gen);
-    ep.push_back(std::exp(log_10 * upper) / years_per_gen);
-    ep.push_back(std::max(1e8, 10.0 * ep[ep.size() - 1]) / years_per_gen);
-  } else {  // :447-454
-    const int E = 31;
-    ep.resize(E);
-    ep[0] = 0.0;
-    ep[1] = 1e3 / years_per_gen;
-    for (int e = 2; e < E - 1; e++) ep[e] = std::exp(log_10 * (3.0 + 4.0 * (e - 1.0) / (E - 3.0))) / years_per_gen;
-    ep[E - 1] = 1e8 / years_per_gen;
-  }
-  *nepochs = (int)ep.size();
-  if ((int)ep.size() > cap) {
-    set_error("rl_mutrate_epochs: %zu epoch boundaries, room for %d", ep.size(), cap);
-    return RL_EINVAL;
-  }
-  memcpy(epochs, ep.data(), ep.size() * sizeof(double));
-  return RL_OK;
+  return make_epochs("rl_mutrate_epochs", years_per_gen, bins_or_null, epochs, nepochs);
 }
 
 extern "C" int rl_mutrate_trees(const int *parents, const double *branch_length, int N, int ntrees, const double *epochs,
@@ -339,7 +211,7 @@ extern "C" int rl_mutrate_trees(const int *parents, const double *branch_length,
     set_error("rl_mutrate_trees: bad arguments (ntrees=%d; no null pointers)", ntrees);
     return RL_EINVAL;
   }
-  if (const int rc = check_epochs("rl_mutrate_trees", epochs, nepochs)) return rc;
+  if (const int rc = check_epochs("rl_mutrate_trees", epochs, nepochs, kMutrateMaxEpochs)) return rc;
   return mutrate_rows(parents, branch_length, N, ntrees, epochs, nepochs, device, out, "rl_mutrate_trees", nullptr);
 }
 
@@ -347,7 +219,7 @@ extern "C" int rl_mutrate_anc(const char *anc_path, const char *mut_path, const 
                               const double *epochs, int nepochs, int device, double *mutation, double *opportunity,
                               long long *mapped_snps) {
   if (!anc_path || !mut_path || !epochs || !mutation || !opportunity) return null_args("rl_mutrate_anc");
-  if (const int rc = check_epochs("rl_mutrate_anc", epochs, nepochs)) return rc;
+  if (const int rc = check_epochs("rl_mutrate_anc", epochs, nepochs, kMutrateMaxEpochs)) return rc;
   const int E = nepochs;
   AncText anc(kMode);
   int rc = anc.open(anc_path);
@@ -369,7 +241,7 @@ extern "C" int rl_mutrate_anc(const char *anc_path, const char *mut_path, const 
   }
   std::vector<int> pos, dist;
   if (dist_path_or_null) {
-    if ((rc = read_dist(dist_path_or_null, pos, dist))) return rc;
+    if ((rc = read_dist(kMode, dist_path_or_null, pos, &dist))) return rc;
   } else {
     for (const MutSnp &m : mut) pos.push_back(m.pos), dist.push_back(m.dist);
   }
@@ -378,10 +250,8 @@ extern "C" int rl_mutrate_anc(const char *anc_path, const char *mut_path, const 
 
   // the trees with a one-branch SNP go up batch by batch; their E doubles come back and the SNPs of the batch are
   // added in the .mut's order (:519-586)
-  const size_t nodes = (size_t)2 * N - 1;
-  const int batch = mutrate_batch_trees(N);
-  std::vector<int> parents((size_t)batch * nodes), tree_id, scratch_parent(nodes);
-  std::vector<double> bl((size_t)batch * nodes), scratch_bl(nodes), lengths;
+  SnpTreeBatches w(N, mutrate_batch_trees(N));
+  std::vector<double> lengths;
   std::vector<size_t> snp_id;  // the mapped SNPs of the batch
   std::vector<int> snp_tree;   // ... and the tree of each, within the batch
   std::fill(mutation, mutation + E, 0.0);
@@ -394,11 +264,10 @@ extern "C" int rl_mutrate_anc(const char *anc_path, const char *mut_path, const 
   double trees_seconds = 0.0, snps_seconds = 0.0;
   int trees_done = 0;
   const auto flush = [&]() -> int {
-    const int held = (int)tree_id.size();
-    if (!held) return RL_OK;
+    const int held = (int)w.tree_id.size();
     lengths.assign((size_t)held * E, 0.0);
     Clock::time_point t0 = Clock::now();
-    if (const int r = mutrate_rows(parents.data(), bl.data(), N, held, epochs, E, device, lengths.data(), anc_path, tree_id.data()))
+    if (const int r = mutrate_rows(w.parents.data(), w.bl.data(), N, held, epochs, E, device, lengths.data(), anc_path, w.tree_id.data()))
       return r;
     trees_seconds += since(t0);
     trees_done += held;
@@ -435,24 +304,15 @@ extern "C" int rl_mutrate_anc(const char *anc_path, const char *mut_path, const 
       for (int e = 0; e < E; e++) opportunity[e] += in_epoch[e] * count_bases[snp_id[i]];
     }
     snps_seconds += since(t0);
-    tree_id.clear(), snp_id.clear(), snp_tree.clear();
+    snp_id.clear(), snp_tree.clear();
     return RL_OK;
   };
-  size_t k = 0;
-  for (int t = 0; t < anc.trees && k < mut.size(); t++) {
-    bool wanted = false;
-    const size_t k0 = k;
-    for (; k < mut.size() && mut[k].tree == t; k++) wanted |= mut[k].branches == 1;
-    int *parent = wanted ? &parents[tree_id.size() * nodes] : scratch_parent.data();
-    double *b = wanted ? &bl[tree_id.size() * nodes] : scratch_bl.data();
-    if ((rc = anc.next(t, parent, b))) return rc;
-    if (!wanted) continue;
-    for (size_t s = k0; s < k; s++)
-      if (mut[s].branches == 1) snp_id.push_back(s), snp_tree.push_back((int)tree_id.size());
-    tree_id.push_back(t);
-    if ((int)tree_id.size() == batch && (rc = flush())) return rc;
-  }
-  if ((rc = flush())) return rc;
+  const auto take = [&](size_t s, int slot) {
+    if (mut[s].branches == 1) snp_id.push_back(s), snp_tree.push_back(slot);
+    return RL_OK;
+  };
+  if ((rc = w.walk(anc, mut.size(), [&](size_t k) { return mut[k].tree; }, [&](size_t k) { return mut[k].branches == 1; }, take, flush)))
+    return rc;
   if (timing_level() >= 1)
     fprintf(stderr, "[mutrate] %d trees of N=%d on %s: %.6f s; SNP loop (%lld mapped): %.6f s; reading the text and the rest: %.6f s\n",
             trees_done, N, device >= 0 ? "the device" : "the host", trees_seconds, mapped, snps_seconds,

@@ -2,6 +2,8 @@
 #pragma once
 #include <cstddef>
 
+#include "tree_batch.h"
+
 namespace rl {
 
 constexpr int kMutrateMaxN = 10240;    // the LDS layout of a tree: kids, then times and their sorted copy
@@ -12,16 +14,12 @@ constexpr size_t kMutrateBatchBytes = (size_t)2 << 20;
 // trees per batch at N leaves: kMutrateBatchBytes over the bytes one tree takes on the device (parents 4, branch
 // lengths 8 per node; a flag of 4), at least 1
 inline int mutrate_batch_trees(int N) {
-  const size_t nodes = (size_t)2 * N - 1, per_tree = nodes * 12 + 4;
-  const size_t b = kMutrateBatchBytes / per_tree;
-  return b < 1 ? 1 : (b > (1u << 20) ? 1 << 20 : (int)b);
+  const size_t nodes = (size_t)2 * N - 1;
+  return batch_trees(kMutrateBatchBytes, nodes * 12 + 4);
 }
 
-// what the device says of a tree
-enum { kMutrateTreeDone = 0, kMutrateTreeRefused = 1 };
-
 // out [ntrees][E] doubles: the branch length of every tree in every epoch (entry E-1 is 0); the row of a tree whose
-// flag is not kMutrateTreeDone keeps zeros.  flags: [ntrees].  epochs [E] have passed the host's checks; N and E
+// flag is not kTreeDone keeps zeros.  flags: [ntrees].  epochs [E] have passed the host's checks; N and E
 // beyond the limits are RL_EINVAL before any launch.
 int mutrate_device(const int *parents, const double *branch_length, int N, int ntrees, const double *epochs, int E,
                    int device, double *out, int *flags);
@@ -31,8 +29,6 @@ int mutrate_device(const int *parents, const double *branch_length, int N, int n
 // called).  with_device: the trees were refused by the device, so one the host accepts is refused too
 int mutrate_host_rows(const int *parents, const double *bl, int N, int ntrees, const double *ep, int E, double *out,
                       float *roots, const char *where, const int *tree_id, bool refused_by_device = false);
-// RL_OK, or RL_EINVAL with the message of rl_mutrate_trees (`who` in its place)
-int mutrate_check_epochs(const char *who, const double *ep, int E);
 
 #ifdef __HIPCC__
 // the per-tree kernel on device pointers, n trees (n workgroups) on the null stream: rows [n][E] and flag [n] start at

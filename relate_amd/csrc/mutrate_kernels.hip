@@ -51,7 +51,7 @@ __global__ void __launch_bounds__(T) mutrate_kernel(const int *__restrict__ PAR,
 
   if (tid < E) ep[tid] = EP[tid];
   if (!sorted_max_times<T>(par, bl, N, K, S, &bad)) {  // steps 1 and 2
-    if (tid == 0) FLAG[t] = kMutrateTreeRefused;
+    if (tid == 0) FLAG[t] = kTreeRefused;
     return;
   }
   // (MutationRateWithContext clamps a SNP's age_end to the root's time: the last of the sorted float times)
@@ -128,13 +128,13 @@ __global__ void __launch_bounds__(T) mutrate_kernel(const int *__restrict__ PAR,
   OUT[(size_t)t * E + e] = acc;
 }
 
-static size_t round16(size_t b) { return (b + 15) & ~(size_t)15; }
-
 hipError_t mutrate_launch(const int *par, const double *bl, const double *ep, int E, int N, int n, double *rows, int *flag,
                           float *root) {
   const size_t dyn = round16(8 * ((size_t)N - 1));
-  if (N <= kMutrateSmallN) return launch_with_lds(mutrate_kernel<256>, n, 256, dyn, nullptr, par, bl, ep, E, N, n, rows, flag, root);
-  return launch_with_lds(mutrate_kernel<1024>, n, 1024, dyn, nullptr, par, bl, ep, E, N, n, rows, flag, root);
+  const auto go = [&](auto kernel, int threads) {
+    return launch_with_lds(kernel, n, threads, dyn, nullptr, par, bl, ep, E, N, n, rows, flag, root);
+  };
+  return N <= kMutrateSmallN ? go(mutrate_kernel<256>, 256) : go(mutrate_kernel<1024>, 1024);
 }
 
 int mutrate_device(const int *parents, const double *branch_length, int N, int ntrees, const double *epochs, int E,
@@ -148,26 +148,23 @@ int mutrate_device(const int *parents, const double *branch_length, int N, int n
     return RL_EINVAL;
   }
   if (const int rc = select_device("rl_mutrate_trees", device)) return rc;
-  const size_t nodes = (size_t)2 * N - 1;
   const int B = mutrate_batch_trees(N);
-  DevBuf ep, par, bl, rows, flag;
+  DevBuf ep, rows;
+  TreeBatch tb;
   int rc = ep.alloc((size_t)E * 8);
-  rc = rc ? rc : par.alloc((size_t)B * nodes * 4);
-  rc = rc ? rc : bl.alloc((size_t)B * nodes * 8);
+  rc = rc ? rc : tb.alloc(N, B);
   rc = rc ? rc : rows.alloc((size_t)B * E * 8);
-  rc = rc ? rc : flag.alloc((size_t)B * 4);
   if (rc) return rc;
   RL_HIP(hipMemcpy(ep.p, epochs, (size_t)E * 8, hipMemcpyHostToDevice));
   for (int t0 = 0; t0 < ntrees; t0 += B) {
     const int n = std::min(B, ntrees - t0);
-    RL_HIP(hipMemcpy(par.p, parents + (size_t)t0 * nodes, (size_t)n * nodes * 4, hipMemcpyHostToDevice));
-    RL_HIP(hipMemcpy(bl.p, branch_length + (size_t)t0 * nodes, (size_t)n * nodes * 8, hipMemcpyHostToDevice));
-    RL_HIP(hipMemset(rows.p, 0, (size_t)n * E * 8));
-    RL_HIP(hipMemset(flag.p, 0, (size_t)n * 4));
-    RL_HIP(mutrate_launch(par.as<int>(), bl.as<double>(), ep.as<double>(), E, N, n, rows.as<double>(), flag.as<int>(), nullptr));
+    if ((rc = tb.upload(parents, branch_length, t0, n))) return rc;
+    RL_HIP(hipMemset(rows.p, 0, (size_t)n * E * 8));  // (after the copies: a copy behind a memset waits for it)
+    RL_HIP(mutrate_launch(tb.par.as<int>(), tb.bl.as<double>(), ep.as<double>(), E, N, n, rows.as<double>(), tb.flag.as<int>(), nullptr));
     // (the copies wait for the kernel)
     RL_HIP(hipMemcpy(out + (size_t)t0 * E, rows.p, (size_t)n * E * 8, hipMemcpyDeviceToHost));
-    RL_HIP(hipMemcpy(flags + t0, flag.p, (size_t)n * 4, hipMemcpyDeviceToHost));
+    if ((rc = tb.download(n))) return rc;
+    std::copy(tb.flags.begin(), tb.flags.begin() + n, flags + t0);
   }
   return RL_OK;
 }

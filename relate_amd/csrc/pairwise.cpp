@@ -23,8 +23,9 @@ namespace rl {
 
 namespace {
 
-int refuse_at(const char *where, long long index, const int *parent, int N) {
-  return refuse_tree((std::string(where) + ": tree " + std::to_string(index)).c_str(), parent, N);
+// check_tree of tree `index` of `where`; the branch lengths are not checked: any double is added
+int check_at(const char *where, long long index, const int *parent, int N, bool refused_by_device, std::vector<unsigned char> &kids) {
+  return check_tree((std::string(where) + ": tree " + std::to_string(index)).c_str(), parent, nullptr, N, 0, refused_by_device, kids);
 }
 
 // one tree's tables and its contribution to S
@@ -102,11 +103,12 @@ struct Pairwise {
     if (dev) {
       int bad = -1;
       const int rc = pairwise_device_add(dev, parents, bl, weights, ntrees, &bad);
-      return bad >= 0 ? refuse_at(where, bad, parents + (size_t)bad * nodes, N) : rc;
+      std::vector<unsigned char> kids;
+      return bad >= 0 ? check_at(where, bad, parents + (size_t)bad * nodes, N, true, kids) : rc;
     }
     for (int t = 0; t < ntrees; t++) {
       const int *parent = parents + t * nodes;
-      if (first_bad_node(parent, N, host->kids)) return refuse_at(where, t, parent, N);
+      if (const int rc = check_at(where, t, parent, N, false, host->kids)) return rc;
       host->prepare(parent, time ? bl + t * nodes : nullptr);
       const HostPairwise &h = *host;
       for (int i = 0; i < N; i++) {

@@ -35,6 +35,7 @@
 
 #include "common.h"
 #include "pairwise.h"
+#include "tree_batch.h"
 #include "tree_passes.h"
 
 namespace rl {
@@ -65,8 +66,8 @@ __global__ void __launch_bounds__(T) pairwise_prepare_kernel(const int *__restri
   const int lane = threadIdx.x & 63;
   const bool wave0 = threadIdx.x < 64;
 
-  if (!build_kids<T>(par, N, K, nullptr, &bad)) {
-    if (threadIdx.x == 0) BAD[t] = 1;
+  if (!build_kids<T>(par, N, K, nullptr, &bad)) {  // (the branch lengths are not checked: any double is added)
+    if (threadIdx.x == 0) BAD[t] = kTreeRefused;
     return;
   }
   if (TIME) {
@@ -203,13 +204,11 @@ __global__ void __launch_bounds__(T) pairwise_accumulate_kernel(const u16 *__res
   }
 }
 
-static size_t round16(size_t b) { return (b + 15) & ~(size_t)15; }
-
 struct PairwiseDevice {
-  int N = 0, device = 0, batch = 0;
+  int N = 0, device = 0;
   bool time = false;
-  DevBuf S, par, bl, w, rank, g, val, bad;
-  std::vector<int> flags;
+  DevBuf S, w, rank, g, val;
+  TreeBatch trees;  // (branch lengths only for metric time)
 };
 
 void pairwise_device_free(PairwiseDevice *d) { delete d; }
@@ -241,21 +240,17 @@ int pairwise_device_begin(PairwiseDevice **out, int N, bool time, int device) {
   }
   const size_t nodes = (size_t)2 * N - 1;
   const size_t per_tree = nodes * 4 + (time ? nodes * 8 : 0) + 8 + (size_t)N * (2 + 2 + (time ? 8 : 2)) + 4;
-  d->batch = (int)std::min<size_t>(std::min(kPairwiseBatchBytes, free_b / 2) / per_tree, 1 << 20);
-  if (d->batch < 1) d->batch = 1;  // (a tree of 10,240 leaves is 0.4 MB: the allocations below say so if it does not fit)
-  const size_t B = (size_t)d->batch;
-  rc = d->par.alloc(B * nodes * 4);
-  if (!rc && time) rc = d->bl.alloc(B * nodes * 8);
+  // (a tree of 10,240 leaves is 0.4 MB: the allocations below say so if it does not fit)
+  const size_t B = (size_t)batch_trees(std::min(kPairwiseBatchBytes, free_b / 2), per_tree);
+  rc = d->trees.alloc(N, (int)B, time);
   rc = rc ? rc : d->w.alloc(B * 8);
   rc = rc ? rc : d->rank.alloc(B * N * 2);
   rc = rc ? rc : d->g.alloc(B * N * 2);
   rc = rc ? rc : d->val.alloc(B * N * (time ? 8 : 2));
-  rc = rc ? rc : d->bad.alloc(B * 4);
   if (rc) {
     delete d;
     return rc;
   }
-  d->flags.resize(B);
   *out = d;
   return RL_OK;
 }
@@ -265,26 +260,23 @@ template <bool TIME, bool SMALL>
 static int pairwise_add_batches(PairwiseDevice *d, const int *parents, const double *branch_length,
                                 const long long *weights, int ntrees, int *bad_tree) {
   const int N = d->N;
-  const size_t nodes = (size_t)2 * N - 1;
+  TreeBatch &tb = d->trees;
   const size_t dyn_prepare = round16((size_t)(TIME ? 12 : 8) * (N - 1)), dyn_accumulate = round16((size_t)(TIME ? 14 : 8) * N);
   const int rows = (N + 511) / 512, blocks = (N + rows - 1) / rows;
   u16 *rank = d->rank.as<u16>(), *g = d->g.as<u16>();
-  for (int t0 = 0; t0 < ntrees; t0 += d->batch) {
-    const int n = std::min(d->batch, ntrees - t0);
-    RL_HIP(hipMemcpy(d->par.p, parents + (size_t)t0 * nodes, (size_t)n * nodes * 4, hipMemcpyHostToDevice));
-    if (TIME) RL_HIP(hipMemcpy(d->bl.p, branch_length + (size_t)t0 * nodes, (size_t)n * nodes * 8, hipMemcpyHostToDevice));
+  for (int t0 = 0; t0 < ntrees; t0 += tb.batch) {
+    const int n = std::min(tb.batch, ntrees - t0);
     RL_HIP(hipMemcpy(d->w.p, weights + t0, (size_t)n * 8, hipMemcpyHostToDevice));
-    RL_HIP(hipMemset(d->bad.p, 0, (size_t)n * 4));
-    RL_HIP(launch_with_lds(pairwise_prepare_kernel<SMALL ? 64 : 256, TIME>, n, SMALL ? 64 : 256, dyn_prepare, nullptr, d->par.as<int>(),
-                           TIME ? d->bl.as<double>() : nullptr, N, n, rank, g, d->val.p, d->bad.as<int>()));
-    // (the copy waits for the kernel.)  Nothing of a batch is added unless all of its trees passed: the accumulation
-    // uses rank and g as indices
-    RL_HIP(hipMemcpy(d->flags.data(), d->bad.p, (size_t)n * 4, hipMemcpyDeviceToHost));
-    for (int k = 0; k < n; k++)
-      if (d->flags[k]) {
-        *bad_tree = t0 + k;
-        return RL_EINVAL;
-      }
+    if (const int rc = tb.upload(parents, TIME ? branch_length : nullptr, t0, n)) return rc;
+    RL_HIP(launch_with_lds(pairwise_prepare_kernel<SMALL ? 64 : 256, TIME>, n, SMALL ? 64 : 256, dyn_prepare, nullptr, tb.par.as<int>(),
+                           TIME ? tb.bl.as<double>() : nullptr, N, n, rank, g, d->val.p, tb.flag.as<int>()));
+    // Nothing of a batch is added unless all of its trees passed: the accumulation uses rank and g as indices
+    int bad = -1;
+    if (const int rc = tb.first_not_done(n, &bad)) return rc;
+    if (bad >= 0) {
+      *bad_tree = t0 + bad;
+      return RL_EINVAL;
+    }
     RL_HIP(launch_with_lds(pairwise_accumulate_kernel<SMALL ? 256 : 1024, TIME>, blocks, SMALL ? 256 : 1024, dyn_accumulate, nullptr, rank,
                            g, d->val.p, d->w.as<long long>(), N, n, rows, d->S.p));
     RL_HIP(hipDeviceSynchronize());  // the next batch overwrites the arrays this one reads

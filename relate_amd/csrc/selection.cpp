@@ -83,11 +83,6 @@ bool row_numbers(const std::string &line, std::string *pos, std::string *rs_id, 
   return true;
 }
 
-int null_args(const char *who) {
-  set_error("%s: bad arguments (no null pointers)", who);
-  return RL_EINVAL;
-}
-
 }  // namespace
 }  // namespace rl
 

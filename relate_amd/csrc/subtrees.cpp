@@ -93,13 +93,6 @@ struct HostSubTree : TreeTables {
   }
 };
 
-// 0, or the first node whose branch length is negative or not finite + 1 (the root's ends in the subtree root's)
-int first_bad_length(const double *bl, int N) {
-  for (int v = 0; v < 2 * N - 1; v++)
-    if (!(bl[v] >= 0.0 && bl[v] <= DBL_MAX)) return v + 1;
-  return 0;
-}
-
 // N and the subset [M]: labels of leaves, rising.  labels [N]: the new label of every leaf, -1 outside the subset
 int check_subset(const char *who, int N, const int *subset, int M, std::vector<int> &labels) {
   if (N < 2 || N > kSubtreesMaxN) {
@@ -143,12 +136,8 @@ int subtrees_of(const char *where, long long index0, const int *parents, const d
     const int *parent = parents + t * nodes;
     const double *b = bl + t * nodes;
     const std::string tree = std::string(where) + ": tree " + std::to_string(index0 + t);
-    if (first_bad_node(parent, N, kids)) return refuse_tree(tree.c_str(), parent, N);
-    if (const int v = first_bad_length(b, N)) {
-      set_error("%s: branch length %g of node %d is negative or not finite", tree.c_str(), b[v - 1], v - 1);
-      return RL_EINVAL;
-    }
-    if (device >= 0) return refuse_tree(tree.c_str(), parent, N);  // (refused by the device and not by the host)
+    // (all 2N-1 lengths: the root's ends in the subtree root's)
+    if (const int rc = check_tree(tree.c_str(), parent, b, N, 2 * N - 1, device >= 0, kids)) return rc;
     if (!host.run(parent, b, sub_parent + t * sub, sub_bl + t * sub, sub_time + t * sub, convert_index + t * nodes,
                   number_in_subpop + t * nodes)) {
       set_error("%s: the reference's assert `node == 2*subpop.size()-1` fails", tree.c_str());
@@ -181,11 +170,6 @@ int assign_pop_of_interest(const std::vector<std::string> &groups, const std::st
   }
   std::sort(of_interest.begin(), of_interest.end());
   return RL_OK;
-}
-
-int null_args(const char *who) {
-  set_error("%s: bad arguments (no null pointers)", who);
-  return RL_EINVAL;
 }
 
 double now() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }

@@ -3,6 +3,8 @@
 #pragma once
 #include <cstddef>
 
+#include "tree_batch.h"
+
 namespace rl {
 
 constexpr int kSubtreesMaxN = 10240;  // the LDS layout of a tree: kids, then counts and new labels, 8 bytes a node
@@ -14,13 +16,9 @@ constexpr size_t kSubtreesBatchBytes = (size_t)16 << 20;
 // 4, branch lengths 8 per node; out: convert_index 4, number_in_subpop 4, the subtree's parent 4, branch length 8 and
 // time 4 per node; a flag of 4), at least 1
 inline int subtrees_batch_trees(int N) {
-  const size_t nodes = (size_t)2 * N - 1, per_tree = nodes * 36 + 4;
-  const size_t b = kSubtreesBatchBytes / per_tree;
-  return b < 1 ? 1 : (b > (1u << 20) ? 1 << 20 : (int)b);
+  const size_t nodes = (size_t)2 * N - 1;
+  return batch_trees(kSubtreesBatchBytes, nodes * 36 + 4);
 }
-
-// what the device says of a tree
-enum { kSubtreesTreeDone = 0, kSubtreesTreeRefused = 1 };
 
 // The subtrees of ntrees trees of N leaves for the M leaves whose new labels leaf_label [N] gives (k for the k-th
 // leaf of the subset in rising label order, -1 for any other leaf; the host has checked the subset).  Outputs per

@@ -80,16 +80,8 @@ __global__ void __launch_bounds__(T) subtrees_kernel(const int *__restrict__ PAR
   u16 *NL = CNT + ni;                                        // [ni] new label, kNotKept for a node that is not kept
 
   // ---- 1. the checks
-  if (!build_kids<T>(par, N, K, nullptr, &bad)) {
-    if (tid == 0) FLAG[t] = kSubtreesTreeRefused;
-    return;
-  }
-  __syncthreads();  // (every thread has read build_kids' verdict)
-  for (int v = tid; v < nodes; v += T)
-    if (!(bl[v] >= 0.0 && bl[v] <= DBL_MAX)) bad = 1;
-  __syncthreads();
-  if (bad) {
-    if (tid == 0) FLAG[t] = kSubtreesTreeRefused;
+  if (!checked_kids<T>(par, bl, nodes, N, K, nullptr, &bad)) {  // (the root's length ends in the subtree root's)
+    if (tid == 0) FLAG[t] = kTreeRefused;
     return;
   }
 
@@ -116,7 +108,7 @@ __global__ void __launch_bounds__(T) subtrees_kernel(const int *__restrict__ PAR
     total += wave_kept[w];
   }
   if (total != M - 1) {  // (the same verdict in every thread)
-    if (tid == 0) FLAG[t] = kSubtreesTreeRefused;
+    if (tid == 0) FLAG[t] = kTreeRefused;
     return;
   }
   for (int i = a; i < b; i++) NL[i] = kept(i) ? (u16)(M + rank++) : kNotKept;
@@ -154,7 +146,7 @@ __global__ void __launch_bounds__(T) subtrees_kernel(const int *__restrict__ PAR
   unsigned *K2 = reinterpret_cast<unsigned *>(lds);                  // [M-1] the subtree's kids
   float *TM = reinterpret_cast<float *>(lds + (size_t)4 * (M - 1));  // [M-1] its times
   if (!build_kids<T>(sub_parent, M, K2, nullptr, &bad)) {
-    if (tid == 0) FLAG[t] = kSubtreesTreeRefused;
+    if (tid == 0) FLAG[t] = kTreeRefused;
     return;
   }
   __syncthreads();
@@ -162,8 +154,6 @@ __global__ void __launch_bounds__(T) subtrees_kernel(const int *__restrict__ PAR
   __syncthreads();
   for (int s = tid; s < sub_nodes; s += T) sub_time[s] = s < M ? 0.0f : TM[s - M];
 }
-
-static size_t round16(size_t b) { return (b + 15) & ~(size_t)15; }
 
 int subtrees_device(const int *parents, const double *branch_length, int N, int ntrees, const int *leaf_label, int M,
                     int device, int *sub_parent, double *sub_bl, float *sub_time, int *convert_index,
@@ -177,38 +167,31 @@ int subtrees_device(const int *parents, const double *branch_length, int N, int 
   const size_t nodes = (size_t)2 * N - 1, sub = (size_t)2 * M - 1, ni = (size_t)N - 1;
   const size_t B = (size_t)std::min(subtrees_batch_trees(N), std::max(ntrees, 1));
   const size_t dyn = round16((size_t)8 * ni);
-  DevBuf par, bl, leaf, spar, sbl, stm, conv, cnt, flag;
-  int rc = par.alloc(B * nodes * 4);
-  rc = rc ? rc : bl.alloc(B * nodes * 8);
+  DevBuf leaf, spar, sbl, stm, conv, cnt;
+  TreeBatch tb;
+  int rc = tb.alloc(N, (int)B);
   rc = rc ? rc : leaf.alloc((size_t)N * 4);
   rc = rc ? rc : spar.alloc(B * sub * 4);
   rc = rc ? rc : sbl.alloc(B * sub * 8);
   rc = rc ? rc : stm.alloc(B * sub * 4);
   rc = rc ? rc : conv.alloc(B * nodes * 4);
   rc = rc ? rc : cnt.alloc(B * nodes * 4);
-  rc = rc ? rc : flag.alloc(B * 4);
   if (rc) return rc;
   RL_HIP(hipMemcpy(leaf.p, leaf_label, (size_t)N * 4, hipMemcpyHostToDevice));
-  std::vector<int> flags(B);
   for (int t0 = 0; t0 < ntrees; t0 += (int)B) {
     const int n = std::min((int)B, ntrees - t0);
-    RL_HIP(hipMemcpy(par.p, parents + (size_t)t0 * nodes, (size_t)n * nodes * 4, hipMemcpyHostToDevice));
-    RL_HIP(hipMemcpy(bl.p, branch_length + (size_t)t0 * nodes, (size_t)n * nodes * 8, hipMemcpyHostToDevice));
-    RL_HIP(hipMemset(flag.p, 0, (size_t)n * 4));
-    if (N <= kSubtreesSmallN)
-      RL_HIP(launch_with_lds(subtrees_kernel<256>, n, 256, dyn, nullptr, par.as<int>(), bl.as<double>(), leaf.as<int>(), N, M,
-                             n, spar.as<int>(), sbl.as<double>(), stm.as<float>(), conv.as<int>(), cnt.as<int>(),
-                             flag.as<int>()));
-    else
-      RL_HIP(launch_with_lds(subtrees_kernel<1024>, n, 1024, dyn, nullptr, par.as<int>(), bl.as<double>(), leaf.as<int>(), N,
-                             M, n, spar.as<int>(), sbl.as<double>(), stm.as<float>(), conv.as<int>(), cnt.as<int>(),
-                             flag.as<int>()));
-    RL_HIP(hipMemcpy(flags.data(), flag.p, (size_t)n * 4, hipMemcpyDeviceToHost));  // (the copy waits for the kernel)
-    for (int k = 0; k < n; k++)
-      if (flags[k] != kSubtreesTreeDone) {
-        *bad_tree = t0 + k;
-        return RL_EINVAL;
-      }
+    if ((rc = tb.upload(parents, branch_length, t0, n))) return rc;
+    const auto go = [&](auto kernel, int threads) {
+      return launch_with_lds(kernel, n, threads, dyn, nullptr, tb.par.as<int>(), tb.bl.as<double>(), leaf.as<int>(), N, M, n,
+                             spar.as<int>(), sbl.as<double>(), stm.as<float>(), conv.as<int>(), cnt.as<int>(), tb.flag.as<int>());
+    };
+    RL_HIP(N <= kSubtreesSmallN ? go(subtrees_kernel<256>, 256) : go(subtrees_kernel<1024>, 1024));
+    int bad = -1;
+    if ((rc = tb.first_not_done(n, &bad))) return rc;
+    if (bad >= 0) {
+      *bad_tree = t0 + bad;
+      return RL_EINVAL;
+    }
     RL_HIP(hipMemcpy(sub_parent + (size_t)t0 * sub, spar.p, (size_t)n * sub * 4, hipMemcpyDeviceToHost));
     RL_HIP(hipMemcpy(sub_bl + (size_t)t0 * sub, sbl.p, (size_t)n * sub * 8, hipMemcpyDeviceToHost));
     RL_HIP(hipMemcpy(sub_time + (size_t)t0 * sub, stm.p, (size_t)n * sub * 4, hipMemcpyDeviceToHost));

@@ -1,8 +1,13 @@
 // tree_passes.h -- the per-tree passes the tree kernels share (compare_kernels.hip: CompareTopology; pairwise_kernels.hip:
-// PairwiseCoalescence; coalrate_kernels.hip: CoalescentRateForSection).  A tree comes as a parent array with labels
-// rising from child to parent; its tables live in LDS, internal node v at index v - N (ni = N - 1 of them).
+// PairwiseCoalescence; coalrate_kernels.hip: CoalescentRateForSection; frequency_kernels.hip: Frequency;
+// mutrate_kernels.hip: AvgMutationRate and MutationRateWithContext; coaltree_kernels.hip: CoalRateForTree;
+// subtrees_kernels.hip: SubTreesForSubpopulation).  A tree comes as a parent array with labels rising from child to
+// parent; its tables live in LDS, internal node v at index v - N (ni = N - 1 of them).  What the drivers around the
+// kernels share -- the staging of a batch, the flag of a tree -- is in tree_batch.h.
 //   build_kids      all threads: kids of every internal node, with the validity checks that must precede any use of a
 //                   label as an index;
+//   checked_kids    all threads: build_kids and the check of the branch lengths, the prologue of every kernel that
+//                   takes a dated tree;
 //   wave_pull       one wavefront: the scan every pass below and in the kernels is an instance of;
 //   wave_clade_sizes   one wavefront: leaves below every internal node, label order;
 //   wave_float_times   one wavefront: the float time of every internal node, rounded at every node, label order;
@@ -55,6 +60,21 @@ __device__ bool build_kids(const int *__restrict__ par, int N, unsigned *K, u16 
     const unsigned k = K[i];
     if ((k & 0xffffu) == 0u || (k >> 16) == 0u) *bad = 1;
   }
+  __syncthreads();
+  return *bad == 0;
+}
+
+// The checked prologue of a kernel that takes a dated tree: build_kids, then the first n_lengths branch lengths
+// (2N-2: the root's is not read; 2N-1 in subtrees_kernels.hip) -- one that is negative, infinite or NaN is refused: the
+// times would not rise.  All threads of the workgroup call it; returns the same value to all, after a barrier.  The
+// kernel writes its flag for a refused tree.
+template <int T>
+__device__ bool checked_kids(const int *__restrict__ par, const double *__restrict__ bl, int n_lengths, int N, unsigned *K,
+                             u16 *up, int *bad) {
+  if (!build_kids<T>(par, N, K, up, bad)) return false;
+  __syncthreads();  // (every thread has read build_kids' verdict)
+  for (int v = threadIdx.x; v < n_lengths; v += T)
+    if (!(bl[v] >= 0.0 && bl[v] <= DBL_MAX)) *bad = 1;
   __syncthreads();
   return *bad == 0;
 }
@@ -210,12 +230,7 @@ __device__ bool sorted_max_times(const int *__restrict__ par, const double *__re
   const int nodes = 2 * N - 1, ni = N - 1, tid = threadIdx.x;
   int P = 1;
   while (P < ni) P <<= 1;
-  if (!build_kids<T>(par, N, K, nullptr, bad)) return false;
-  __syncthreads();  // (every thread has read build_kids' verdict)
-  for (int v = tid; v < nodes - 1; v += T)
-    if (!(bl[v] >= 0.0 && bl[v] <= DBL_MAX)) *bad = 1;
-  __syncthreads();
-  if (*bad) return false;
+  if (!checked_kids<T>(par, bl, nodes - 1, N, K, nullptr, bad)) return false;
   if ((tid >> 6) == 0) wave_max_times(K, bl, N, S, tid & 63);
   __syncthreads();
   for (int k = 2; k <= P; k <<= 1)
