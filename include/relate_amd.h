@@ -376,6 +376,18 @@ int rl_builder_build(rl_builder *b, float *d, const float *d_prior,
 int rl_builder_set_sample_ages(rl_builder *b, const double *ages, int n);
 int rl_builder_last_on_gpu(const rl_builder *b);
 void rl_builder_destroy(rl_builder *b);
+/* Test hook (host only): what the lists of the last tree the HOST builder of `b` built had to hold -- the first n of
+ * 9 counts: the most clusters rebuilt in one merge, merges with more than MM_UPD_LDS (256) of them; the most feasible
+ * pairs (draws) of one merge, merges with more than MM_PAIRS_LDS (320) and with more than MM_BUCKET_MIN (2048); the
+ * draws of the initialisation; the most mutually close partners b > a of one row a; the first merge taken from the
+ * symmetric matrix (-1: none) and how many were.  The device builder is the same algorithm with the same draws:
+ * whether its lists hold a tree follows from these (tests/builder_cases.py).  Returns 9. */
+int rl_builder_census(const rl_builder *b, long long *out, int n);
+/* Test hook (needs a device): the worker kernel that builds trees of N leaves (ages != 0: with sample ages) in this
+ * process -- where the per-cluster state lives (0 LDS, 1 global memory, 2 the candidates in LDS, 3 candidates and row
+ * minima in LDS), register slots per thread (4 / 10 / 20) and workgroups per CU (RELATE_AMD_BUILD_OCC is read once
+ * per process). */
+int rl_debug_builder_kind(int N, int ages, int *layout, int *slots, int *per_cu);
 /* Test hook (host only): the device builder's restatement of std::mt19937 +
  * libstdc++'s uniform_real_distribution<double> against the library itself,
  * n draws from `seed`; returns how many differ. */

@@ -560,6 +560,19 @@ class Builder:
     def last_on_gpu(self):
         return lib().rl_builder_last_on_gpu(C.c_void_p(self._h)) == 1
 
+    CENSUS = ("max_rebuilt", "merges_rebuilt_tail", "max_draws", "merges_draws_global", "merges_draws_bucketed",
+              "init_draws", "max_partners", "first_sym_merge", "sym_merges")
+
+    def census(self):
+        """rl_builder_census: what the lists of the last tree this builder's HOST code built had to hold"""
+        out = np.zeros(len(self.CENSUS), np.int64)
+        L = lib()
+        L.rl_builder_census.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
+        n = L.rl_builder_census(C.c_void_p(self._h), _p(out), len(out))
+        if n != len(out):
+            raise RelateError("rl_builder_census: %d counts, %d expected" % (n, len(out)))
+        return dict(zip(self.CENSUS, (int(x) for x in out)))
+
     def close(self):
         if self._h:
             lib().rl_builder_destroy(C.c_void_p(self._h))
@@ -567,6 +580,15 @@ class Builder:
 
     def __del__(self):
         self.close()
+
+
+def builder_kind(N, ages=False):
+    """rl_debug_builder_kind (needs a device) -> (layout, register slots per thread, workgroups per CU)"""
+    layout, slots, per_cu = C.c_int(-1), C.c_int(-1), C.c_int(-1)
+    L = lib()
+    L.rl_debug_builder_kind.argtypes = [C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]
+    _check(L.rl_debug_builder_kind(N, 1 if ages else 0, C.byref(layout), C.byref(slots), C.byref(per_cu)))
+    return layout.value, slots.value, per_cu.value
 
 
 def copying_weights_host(site, rpos, s_begin, s_end):

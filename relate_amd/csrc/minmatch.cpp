@@ -14,6 +14,7 @@
 #include <cstring>
 
 #include "common.h"
+#include "minmatch_params.h"
 
 namespace rl {
 
@@ -24,6 +25,15 @@ static constexpr int MAX_GATHER = 32;          // columns of updated clusters ga
 static const float INF = std::numeric_limits<float>::infinity();
 static inline double now_s() {
   return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count();
+}
+
+void BuildCensus::merged(long long rebuilt, long long draws_before) {
+  const long long m = draws - draws_before;
+  if (rebuilt > v[MAX_REBUILT]) v[MAX_REBUILT] = rebuilt;
+  v[MERGES_REBUILT_TAIL] += rebuilt > MM_UPD_LDS;
+  if (m > v[MAX_DRAWS]) v[MAX_DRAWS] = m;
+  v[MERGES_DRAWS_GLOBAL] += m > MM_PAIRS_LDS;
+  v[MERGES_DRAWS_BUCKETED] += m > MM_BUCKET_MIN;
 }
 
 // ---- helper threads --------------------------------------------------------
@@ -130,6 +140,7 @@ void MinMatch::consider(int x, int y) {
     sym_dist = d(y, x) + d(x, y);
   }
   dist_random = unif(rng);  // double narrowed to the float member (tree_builder.hpp:60)
+  census.draws++;
   Cand &a = mc[x];
   if (a.dist > sym_dist || (a.dist == sym_dist && a.dist2 > dist_random)) {
     a.lin1 = x; a.lin2 = y; a.dist = sym_dist; a.dist2 = dist_random;
@@ -192,10 +203,15 @@ void MinMatch::initialize() {
     pool.run(scan);
   else
     scan(0, 1);
+  int row = -1;
+  long long in_row = 0;  // (the pairs come row by row: the partners of the row at hand)
   for (int t = 0; t < T; t++)
     for (const auto &pr : pairs[t]) {
       const int a = pr.first, b = pr.second;
       if (min_values[b] >= d(b, a)) {
+        in_row = a == row ? in_row + 1 : 1;
+        row = a;
+        census.partners(in_row);
         consider(a, b);
         if (best.dist > mc[b].dist || (best.dist == mc[b].dist && best.dist2 > mc[b].dist2)) {
           best.lin1 = a; best.lin2 = b; best.dist = sym_dist; best.dist2 = mc[b].dist2;
@@ -210,6 +226,7 @@ void MinMatch::coalesce(int i, int j) {
   const float csi = cluster_size[i], csj = cluster_size[j];
   const size_t n = cluster_index.size();
   const double tp0 = now_s();
+  const long long draws0 = census.draws;
   float *cf = CF ? d_CF.data() : nullptr;
   const bool par = pool.size() > 1 && n >= min_parallel;
   const int T = par ? pool.size() : 1;
@@ -422,6 +439,7 @@ void MinMatch::coalesce(int i, int j) {
         }
       }
   if (best.dist > mc[j].dist || (best.dist == mc[j].dist && best.dist2 > mc[j].dist2)) best = mc[j];
+  census.merged(nupd, draws0);
   t_phase2 += now_s() - tp1;
 }
 
@@ -448,17 +466,20 @@ void MinMatch::quick_build(float *dmat, const float *prior, HostTree &tree) {
   best.dist = INF;
   best.dist2 = INF;
   sym.reset();
+  census.reset();
 
   {
     const double t0 = now_s();
     initialize();
     t_init += now_s() - t0;
   }
+  census.v[BuildCensus::INIT_DRAWS] = census.draws;
 
   for (int num_nodes = N; num_nodes < 2 * N - 1; num_nodes++) {
     int i, j;
     if (best.dist == INF) {  // no mutually closest pair: the smallest symmetric distance, from here on (sym_pairs.h)
       if (!sym.started()) sym.start(cluster_index, [&](int a, int b) { return d(a, b); });
+      census.symmetric(num_nodes - N);
       i = sym.closest().first;
       j = sym.closest().second;
     } else {

@@ -142,6 +142,35 @@ class BuildThreads {
 int build_threads();
 void set_build_threads(int T);
 
+// What the lists of one build had to hold, counted by the host builders (a handful of integer operations per merge
+// and per draw).  The device builder is the same algorithm and draws the same numbers: its rebuilt list, its pair
+// list and its need for a symmetric matrix are these counts (tests/builder_cases.py stays_on_device).
+struct BuildCensus {
+  enum {
+    MAX_REBUILT,           // the most clusters that rebuilt their candidates in one merge
+    MERGES_REBUILT_TAIL,   // merges with more than MM_UPD_LDS of them
+    MAX_DRAWS,             // the most feasible pairs (one draw each) of one merge
+    MERGES_DRAWS_GLOBAL,   // merges with more than MM_PAIRS_LDS
+    MERGES_DRAWS_BUCKETED, // merges with more than MM_BUCKET_MIN
+    INIT_DRAWS,            // feasible pairs of the initialisation
+    MAX_PARTNERS,          // the most mutually close partners b > a of one row a of the untouched matrix
+    FIRST_SYM_MERGE,       // the first merge taken from the symmetric matrix (-1: none)
+    SYM_MERGES,            // merges taken from it
+    COUNT
+  };
+  long long v[COUNT] = {0, 0, 0, 0, 0, 0, 0, -1, 0};
+  long long draws = 0;  // the build's draws so far
+  void reset() { *this = BuildCensus(); }
+  void partners(long long n) {
+    if (n > v[MAX_PARTNERS]) v[MAX_PARTNERS] = n;
+  }
+  void symmetric(long long merge) {
+    if (v[FIRST_SYM_MERGE] < 0) v[FIRST_SYM_MERGE] = merge;
+    v[SYM_MERGES]++;
+  }
+  void merged(long long rebuilt, long long draws_before);  // (minmatch.cpp: the thresholds are minmatch_params.h's)
+};
+
 class MinMatch {
   friend class DeviceMinMatch;
 
@@ -153,6 +182,7 @@ class MinMatch {
   // ordered half of the merges
   double t_init = 0, t_phase1 = 0, t_phase1a = 0, t_phase2 = 0;
   long long n_updated = 0, n_merges = 0;  // clusters that rebuilt their candidates / merges
+  BuildCensus census;                     // of the last quick_build
 
  private:
   struct Cand {
@@ -207,6 +237,7 @@ class MinMatchAges {
   void prepare_levels(const std::vector<double> &sample_ages);
   // d: N*N floats, destroyed.  prior: N*N floats or nullptr.  sample_ages: N values.
   void quick_build(float *d, const float *prior, const std::vector<double> &sample_ages, HostTree &tree);
+  BuildCensus census;  // of the last quick_build
 
  private:
   struct Cand {

@@ -61,6 +61,7 @@ void MinMatchAges::consider(int x, int y, float sym, const std::vector<double> &
   cand.dist = sym;
   cand.dist3 = std::max(ages[x], ages[y]);
   cand.dist2 = unif(rng);
+  census.draws++;
   offer(x, x, y);
   offer(y, x, y);
 }
@@ -102,9 +103,11 @@ void MinMatchAges::initialize(const std::vector<double> &ages) {
   const size_t n = cluster_index.size();
   for (size_t ia = 0; ia < n; ia++) {
     const int a = cluster_index[ia];
+    long long in_row = 0;
     for (size_t ib = ia + 1; ib < n; ib++) {
       const int b = cluster_index[ib];
       if (min_values[a] >= d(a, b) && min_values[b] >= d(b, a)) {
+        census.partners(++in_row);
         float sym;
         if (CF) {
           // (the initialisation with a prior keeps the pairs the prior agrees with and voids the others, :1792-1797 --
@@ -126,6 +129,7 @@ void MinMatchAges::coalesce(int i, int j, const std::vector<double> &ages) {
   const float added = cluster_size[i] + cluster_size[j];
   float min_value_j = INF;
   int updated = 0;
+  const long long draws0 = census.draws;
   best.dist = best.dist2 = best.dist3 = INF;
   best.replace = false;
   const size_t n = cluster_index.size();
@@ -199,6 +203,7 @@ void MinMatchAges::coalesce(int i, int j, const std::vector<double> &ages) {
       if (d(k, j) <= min_values[k])
         if (k != i && k != j) consider(k, j, sym_of(k, j), ages);
   take_best(mc[j]);
+  census.merged(updated, draws0);
 }
 
 // :1125-1152, once per builder
@@ -248,6 +253,7 @@ void MinMatchAges::quick_build(float *dmat, const float *prior, const std::vecto
   best.dist = best.dist2 = best.dist3 = INF;
   if (!prior) best.replace = false;  // (:1117 -- the build with a prior leaves the flag as the last build left it)
   sym.reset();
+  census.reset();
 
   prepare_levels(ages);
   int level = 0;
@@ -256,11 +262,13 @@ void MinMatchAges::quick_build(float *dmat, const float *prior, const std::vecto
   age = prior ? unique_ages[level] : unique_ages[level] + 2.0 / ((double)num_lins * (num_lins - 1.0)) * Ne;
 
   initialize(ages);
+  census.v[BuildCensus::INIT_DRAWS] = census.draws;
 
   for (int num_nodes = N; num_nodes < 2 * N - 1; num_nodes++) {
     int i, j;
     if (best.dist == INF) {  // (sym_pairs.h)
       if (!sym.started()) sym.start(cluster_index, [&](int a, int b) { return d(a, b); });
+      census.symmetric(num_nodes - N);
       i = sym.closest().first;
       j = sym.closest().second;
     } else {

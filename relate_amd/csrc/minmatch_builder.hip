@@ -958,4 +958,14 @@ int rl_builder_set_sample_ages(rl_builder *b, const double *ages, int n) {
 
 int rl_builder_last_on_gpu(const rl_builder *b) { return b ? b->last_on_gpu : RL_EINVAL; }
 
+int rl_builder_census(const rl_builder *b, long long *out, int n) {
+  if (!b || !out || n < 0) {
+    rl::set_error("rl_builder_census: bad arguments");
+    return RL_EINVAL;
+  }
+  const rl::BuildCensus &c = b->ages_tb ? b->ages_tb->census : b->tb.census;
+  for (int x = 0; x < n && x < rl::BuildCensus::COUNT; x++) out[x] = c.v[x];
+  return rl::BuildCensus::COUNT;
+}
+
 }  // extern "C"

@@ -8,7 +8,7 @@ namespace rl {
 
 constexpr int MM_BLOCK = 512;   // (8 waves; a thread keeps ~10 clusters of a merge in registers.  256 threads: 166 ms per N = 5000 tree, 1024: 156, 512: 110)
 constexpr int MM_WAVES = MM_BLOCK / 64;
-constexpr int MM_HITS = 64;       // mutually close pairs per row the weave keeps; more: the host builds the tree
+constexpr int MM_HITS = 64;       // mutually close pairs per row the weave keeps; more: the build scans that stretch of rows itself
 constexpr int MM_UPD_MAX = 512;   // rebuilt clusters of one merge; more: the host builds the tree (the AGES build keeps a longer list)
 constexpr int MM_UPD_LDS = 256;   // ... of which this many in LDS, the rest in global memory
 constexpr int MM_PAIRS_LDS = 320; // feasible pairs of one merge kept in LDS (8 per merge on average); more go through global scratch

@@ -212,6 +212,13 @@ static WorkerKind worker_kind(int N, bool ages) {
 }
 // workgroups of a tree's worker kernel a CU holds
 int device_builder_workers_per_cu(int N, bool ages) { return worker_kind(N, ages).occ; }
+int debug_worker_kind(int N, bool ages, int *layout, int *slots, int *per_cu) {
+  const WorkerKind k = worker_kind(N, ages);
+  *layout = k.layout;
+  *slots = k.maxq;
+  *per_cu = k.occ;
+  return 0;
+}
 int worker_layout(int N, bool ages) { return worker_kind(N, ages).layout; }
 
 // The builders of one device and one tree size hand their trees to WORKERS -- resident workgroups that pull
@@ -461,3 +468,16 @@ int device_builder_expect_add(int device, int N, int delta, bool ages) {
 }  // namespace rl
 
 extern "C" int rl_debug_rng_mismatches(unsigned seed, int n) { return rl::rng_restatement_mismatches(seed, n); }
+
+extern "C" int rl_debug_builder_kind(int N, int ages, int *layout, int *slots, int *per_cu) {
+  if (N < 2 || N > rl::MM_MAXN || !layout || !slots || !per_cu) {
+    rl::set_error("rl_debug_builder_kind: bad arguments (N=%d)", N);
+    return RL_EINVAL;
+  }
+  int devices = 0;  // (the choice depends on the kernels' static LDS, which the runtime tells with a device only)
+  if (hipGetDeviceCount(&devices) != hipSuccess || devices < 1) {
+    rl::set_error("rl_debug_builder_kind: no usable HIP device");
+    return RL_EHIP;
+  }
+  return rl::debug_worker_kind(N, ages != 0, layout, slots, per_cu);
+}

@@ -10,7 +10,7 @@ import numpy as np
 import pytest
 
 from relate_amd import api
-from test_builder_gpu import coalescent_matrix, split_tree_matrix, tied_matrix
+from builder_cases import coalescent_matrix, split_tree_matrix, stays_on_device, tied_matrix
 
 pytestmark = pytest.mark.gpu
 
@@ -27,15 +27,19 @@ def sample_ages(rng, N, levels):
 
 
 def run_sequence(N, ages, mats, theta=0.001, all_on_gpu=True):
+    """... and every tree built where the host builder's census of it says (builder_cases.stays_on_device: the
+    kernel's lists hold it, an equality)"""
     host, dev = api.Builder(N, theta), api.Builder(N, theta, device=0)
     host.set_sample_ages(ages)
     dev.set_sample_ages(ages)
     on_gpu = 0
     for t, (d, prior) in enumerate(mats):
         ref = host.build(d, prior)
+        census = host.census()
         got = dev.build(d, prior)
         on_gpu += dev.last_on_gpu
         assert dev.last_on_gpu or not all_on_gpu
+        assert dev.last_on_gpu == stays_on_device(census, N, ages=True), (t, census)
         for name, a, b in zip(("parent", "child_left", "child_right"), ref, got):
             assert np.array_equal(a, b), (t, name, int(np.argmax(a != b)))
     host.close()
@@ -59,8 +63,9 @@ def test_tied_matrices_with_and_without_prior(N, levels, seed):
         mats.append((tied_matrix(rng, N), priors(rng, N, t)))
     mats.append((tied_matrix(rng, N, 0.0), None))
     mats.append((tied_matrix(rng, N, 0.05), priors(rng, N, 1)))
-    # (from N = 130 on a row of these matrices has more partners than the pair scan keeps: such a tree is the host's,
-    #  and the device builder takes the state back for the next one)
+    # (from N = 260 on a row of these matrices has more partners than the pair scan keeps -- MM_HITS --, and the kernel
+    #  scans such rows itself; where a tree is built is a matter of its lists alone, tree by tree: run_sequence.  Below
+    #  N = 130 every tree is the device's.)
     run_sequence(N, ages, mats, all_on_gpu=N < 130)
 
 
@@ -89,7 +94,7 @@ def test_no_mutually_closest_pair_symmetric_fallback(N, levels, seed):
     mats = [(circ, None), (circ + rng.rand(N, N).astype(np.float32), None),
             (circ + np.floor(rng.rand(N, N) * 3).astype(np.float32), (np.floor(rng.rand(N, N) * 3) * 6.9).astype(np.float32)),
             (tied_matrix(rng, N), None)]
-    run_sequence(N, ages, mats, all_on_gpu=N < 130)
+    run_sequence(N, ages, mats, all_on_gpu=N < 130)  # (and tree by tree where the census says: run_sequence)
 
 
 @pytest.mark.parametrize("N", [5000, 5200])

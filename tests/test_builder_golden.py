@@ -25,11 +25,12 @@ def test_host_builder_gives_the_reference_trees(name):
 @pytest.mark.parametrize("name", sorted(builder_cases.CASES))
 def test_device_builder_gives_the_reference_trees(name):
     N, mats = builder_cases.CASES[name]()
-    b = api.Builder(N, device=0)
-    on_gpu = 0
+    b, host = api.Builder(N, device=0), api.Builder(N)
     for t, (d, prior) in enumerate(mats):
         assert np.array_equal(b.build(d, prior)[0], GOLD[name][t]), (name, t)
-        on_gpu += b.last_on_gpu
+        host.build(d, prior)
+        # (where the host builder's census says: at these sizes every tree fits the kernel's lists, the flat matrix's
+        #  too -- 300 leaves have fewer feasible pairs in a merge than MM_PAIRS_LDS + 8 N)
+        assert b.last_on_gpu == builder_cases.stays_on_device(host.census(), N) == 1, (name, t, host.census())
     b.close()
-    # (a tree whose lists the kernel cannot hold -- the flat matrix's -- is the host's, from the carried state)
-    assert on_gpu >= 1
+    host.close()

@@ -4,46 +4,24 @@ and child arrays, tree after tree, with the state MinMatch carries between build
 import numpy as np
 import pytest
 
+from builder_cases import coalescent_matrix, split_tree_matrix, stays_on_device, tied_matrix  # noqa: F401
 from relate_amd import api
 
 pytestmark = pytest.mark.gpu
 
 
-def tied_matrix(rng, N, ties=0.3):
-    d = (rng.rand(N, N) * 4 + rng.rand(N)[:, None]).astype(np.float32)
-    d[rng.rand(N, N) < ties] = 1.5  # plenty of exact ties: the random draws decide
-    np.fill_diagonal(d, 0)
-    return d
-
-
-def coalescent_matrix(rng, N):
-    """distances shaped like the path's: near-ultrametric from a random binary tree plus asymmetric noise"""
-    order = rng.permutation(N)
-    h = np.zeros((N, N), np.float32)
-    groups = [[int(x)] for x in order]
-    t = 0.0
-    while len(groups) > 1:
-        t += rng.exponential(1.0 / (len(groups) * (len(groups) - 1) / 2))
-        a, b = sorted(rng.choice(len(groups), 2, replace=False))
-        for x in groups[a]:
-            for y in groups[b]:
-                h[x, y] = h[y, x] = t
-        groups[a] = groups[a] + groups[b]
-        del groups[b]
-    d = (h * 20 + rng.rand(N, N) * 0.05).astype(np.float32)
-    d -= d.min(axis=1, keepdims=True)
-    np.fill_diagonal(d, 0)
-    return d
-
-
 def run_sequence(N, mats, theta=0.001, all_on_gpu=True):
+    """... and every tree built where the host builder's census of it says (builder_cases.stays_on_device: the
+    kernel's lists hold it, an equality)"""
     host, dev = api.Builder(N, theta), api.Builder(N, theta, device=0)
     on_gpu = 0
     for t, (d, prior) in enumerate(mats):
         ref = host.build(d, prior)
+        census = host.census()
         got = dev.build(d, prior)
         on_gpu += dev.last_on_gpu
         assert dev.last_on_gpu or not all_on_gpu  # (the symmetric fallback included)
+        assert dev.last_on_gpu == stays_on_device(census, N), (t, census)
         for name, a, b in zip(("parent", "child_left", "child_right"), ref, got):
             assert np.array_equal(a, b), (t, name, int(np.argmax(a != b)))
     host.close()
@@ -58,8 +36,9 @@ def test_tied_matrices_with_and_without_prior(N, seed):
     for t in range(3):  # row minima of the prior rise from tree to tree: the minima carried over stay below them
         mats.append((tied_matrix(rng, N), ((np.floor(rng.rand(N, N) * 4) + t) * 6.9).astype(np.float32)))
     mats.append((tied_matrix(rng, N, 0.0), None))
-    # (a quarter of all pairs are candidates in these matrices: from N = 130 on a row has more mutually close
-    #  partners than the pair scan keeps -- MM_HITS -- and such a tree is the host's)
+    # (a quarter of all pairs are candidates in these matrices: from N = 260 on a row has more mutually close
+    #  partners than the pair scan keeps -- MM_HITS --, and the kernel scans such rows itself; where a tree is built is
+    #  a matter of its lists alone, tree by tree: run_sequence.  Below N = 130 every tree is the device's.)
     run_sequence(N, mats, all_on_gpu=N < 130)
 
 
@@ -99,8 +78,9 @@ def test_no_mutually_closest_pair_symmetric_fallback(N, seed):
 
 
 def test_too_many_tied_candidates_go_to_the_host():
-    """a flat matrix: every pair is a candidate and every cluster rebuilds at the first merge -- more than the
-    kernel's lists hold (status 2): the host builds that tree from the carried state, the next one is the device's"""
+    """a flat matrix: every pair is a candidate -- few clusters rebuild in a merge (8 at the most), but the first merge
+    has 11,412 feasible pairs, more than the MM_PAIRS_LDS + 8 N the pair list holds (status 2): the host builds that
+    tree from the carried state, the next one is the device's"""
     N = 1300
     rng = np.random.RandomState(3)
     flat = np.full((N, N), 2.5, np.float32)
@@ -108,28 +88,6 @@ def test_too_many_tied_candidates_go_to_the_host():
     mats = [(coalescent_matrix(rng, N), None), (flat, None), (coalescent_matrix(rng, N), flat * 2),
             (coalescent_matrix(rng, N), None)]
     assert run_sequence(N, mats, all_on_gpu=False) == 3
-
-
-def split_tree_matrix(rng, N):
-    """near-ultrametric distances from random recursive splits of a random leaf order (cheap at N = 5000),
-    plus asymmetric noise -- the shape of the path's matrices"""
-    order = rng.permutation(N)
-    h = np.zeros((N, N), np.float32)
-    stack = [(0, N, 1.0)]
-    while stack:
-        lo, hi, t = stack.pop()
-        if hi - lo < 2:
-            continue
-        mid = lo + 1 + rng.randint(0, hi - lo - 1)
-        a, b = order[lo:mid], order[mid:hi]
-        h[np.ix_(a, b)] = t
-        h[np.ix_(b, a)] = t
-        stack.append((lo, mid, t * (0.55 + 0.4 * rng.rand())))
-        stack.append((mid, hi, t * (0.55 + 0.4 * rng.rand())))
-    d = (h * 20 + rng.rand(N, N) * 0.05).astype(np.float32)
-    d -= d.min(axis=1, keepdims=True)
-    np.fill_diagonal(d, 0)
-    return d
 
 
 @pytest.mark.parametrize("N", [5000, 5121, 5300])

@@ -368,30 +368,36 @@ def makechunks_fixture():
     print("makechunks fixture: %d entries, %.1f KB" % (len(data), os.path.getsize(os.path.join(GOLD, "makechunks.npz")) / 1e3))
 
 
+def reference_parents(N, mats):
+    """the parent arrays ONE MinMatch of the reference gives for the sequence (oracle/ref_harness quickbuild_seq)"""
+    work = tempfile.mkdtemp()
+    try:
+        args = [rlutil.REF_HARNESS, "quickbuild_seq", str(N), os.path.join(work, "p.bin")]
+        for t, (d, prior) in enumerate(mats):
+            d.tofile(os.path.join(work, "d%d.bin" % t))
+            args.append(os.path.join(work, "d%d.bin" % t))
+            if prior is None:
+                args.append("-")
+            else:
+                prior.tofile(os.path.join(work, "c%d.bin" % t))
+                args.append(os.path.join(work, "c%d.bin" % t))
+        subprocess.run(args, check=True)
+        return np.fromfile(os.path.join(work, "p.bin"), dtype=np.int32).reshape(len(mats), 2 * N - 1)
+    finally:
+        shutil.rmtree(work, ignore_errors=True)
+
+
 def builder_fixture():
     """tests/golden/builder_adversarial.npz: the parent arrays the reference's MinMatch (one object per sequence,
-    oracle/ref_harness quickbuild_seq) gives for the sequences of tests/builder_cases.py"""
+    oracle/ref_harness quickbuild_seq) gives for the sequences of tests/builder_cases.py; builder_lists.npz: the same for
+    the golden ones among its families (rebuilt lists of up to 513 clusters, the pair list's edges, a late symmetric
+    start)"""
     import builder_cases
-    data = {}
-    for name, make in builder_cases.CASES.items():
-        N, mats = make()
-        work = tempfile.mkdtemp()
-        try:
-            args = [rlutil.REF_HARNESS, "quickbuild_seq", str(N), os.path.join(work, "p.bin")]
-            for t, (d, prior) in enumerate(mats):
-                d.tofile(os.path.join(work, "d%d.bin" % t))
-                args.append(os.path.join(work, "d%d.bin" % t))
-                if prior is None:
-                    args.append("-")
-                else:
-                    prior.tofile(os.path.join(work, "c%d.bin" % t))
-                    args.append(os.path.join(work, "c%d.bin" % t))
-            subprocess.run(args, check=True)
-            data[name] = np.fromfile(os.path.join(work, "p.bin"), dtype=np.int32).reshape(len(mats), 2 * N - 1)
-        finally:
-            shutil.rmtree(work, ignore_errors=True)
-    np.savez_compressed(os.path.join(GOLD, "builder_adversarial.npz"), **data)
-    print("builder_adversarial", {k: v.shape for k, v in data.items()}, "%.1f KB" % (os.path.getsize(os.path.join(GOLD, "builder_adversarial.npz")) / 1e3))
+    for fn, cases in (("builder_adversarial.npz", {name: make() for name, make in builder_cases.CASES.items()}),
+                      ("builder_lists.npz", {f.name: (f.N, f.make()) for f in builder_cases.FAMILIES if f.golden})):
+        data = {name: reference_parents(N, mats) for name, (N, mats) in cases.items()}
+        np.savez_compressed(os.path.join(GOLD, fn), **data)
+        print(fn, {k: v.shape for k, v in data.items()}, "%.1f KB" % (os.path.getsize(os.path.join(GOLD, fn)) / 1e3))
 
 
 if __name__ == "__main__":
